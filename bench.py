@@ -14,6 +14,13 @@ torch.distributed.run with N ranks before touching the GPU; under a launcher, n_
 world size and a mismatch with --gpus is refused.
 
 Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) measures the headline only: set-up, W warm-up
+steps (and one more per batch in flight, so every handle is warm), the N timed greedy steps, the
+line.  `--full` adds everything else the line can carry: the serial and instrumented passes behind
+`greedy_serial`, `roofline` and `kernel_breakdown_ms`, the beam lines, BASELINE configs 1-5, the
+exact-f32 path and the CPU baselines.  `--dump-outputs DIR` writes the arrays the last timed
+headline step returned as DIR/<name>.npy (float32); the inputs are seeded, the same every run.
 """
 import argparse
 import gc
@@ -224,7 +231,18 @@ def main():
                     help="skip config 2's opt-in s16x1 perf-arithmetic side measurement (libcasr_hip_s16x1.so)")
     ap.add_argument("--graphs", type=int, default=0,
                     help="1: hipGraph replay of the decode loop (casr_set_graphs); default 0: eager launches")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the serial and instrumented greedy passes "
+                         "(roofline, per-class breakdown), the beam lines, BASELINE configs 1-5, the exact-f32 "
+                         "path and the CPU baselines (each still subject to its --no-* switch); without it only "
+                         "the headline's warm-up and timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed headline step returned (casr greedy: "
+                         "tokens, out_len, finished, accum) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    full = args.full
+    if not full:  # a plain run times the headline only
+        args.no_beam = args.no_configs = args.no_f32_compare = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch(args.gpus))
@@ -268,7 +286,8 @@ def main():
     # batches in flight on this GPU (casr.pipeline.StreamPipeline): handle i mod n on stream i mod n;
     # handle 0 is the serial loop's (n = 1) and runs every instrumented single step
     from casr.pipeline import StreamPipeline
-    pipe = StreamPipeline(cfg, packed, n=max(1, args.streams, args.beam_streams, args.config2_streams), device=dev)
+    n_handles = max(1, args.streams, args.beam_streams, args.config2_streams) if full else max(1, args.streams)
+    pipe = StreamPipeline(cfg, packed, n=n_handles, device=dev)
     pipe.set_precision(args.precision)
     pipe.set_graphs(2 | (1 if args.graphs else 0))
     eng = pipe.engines[0]
@@ -296,11 +315,23 @@ def main():
         h.copy_(t, non_blocking=True)
         return h
 
+    last = {}  # what the most recent greedy step returned (fresh device tensors every step)
+
     def step_greedy(e=None):
         e = e or eng
         e.encode_fbank(fb, frames)  # features + encoder (casr_encode_fbank)
-        out = e.greedy()
+        out = last["greedy"] = e.greedy()
         return to_host(out["tokens"], "greedy")
+
+    def dump_outputs():
+        """--dump-outputs: the result arrays of the headline's last timed step (called right after
+        its closing synchronize), one float32 .npy per array; ranks above 0 add their rank to the name."""
+        if not args.dump_outputs:
+            return
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name in ("tokens", "out_len", "finished", "accum"):
+            a = last["greedy"][name].cpu().numpy().astype(np.float32)
+            np.save(os.path.join(args.dump_outputs, name + (f".rank{rank}" if rank else "") + ".npy"), a)
 
     def barrier():
         if dist is not None:
@@ -349,11 +380,8 @@ def main():
     for _ in range(args.warmup):
         step_greedy()
     flags["warmup"] = eng.device_flags()
-    # one instrumented step: per-class launch times -> dominant kernel
-    eng.profile(CLASSES)
-    step_greedy()
-    breakdown = eng.profile_read()
-    dominant = max(breakdown, key=lambda c: breakdown[c][1])
+    # A plain run goes straight to (3), the line's `value`; --full measures all of these.
+    # One instrumented step: per-class launch times -> dominant kernel.
     # Timed regions of the same steps.  (1) Serial, one batch in flight, with the dominant class's
     # event pair around each of its launches, so `roofline` is the kernel's own launch duration (as
     # rocprof sees it in a serial run); the event records cost the step a few microseconds per launch
@@ -362,23 +390,32 @@ def main():
     # uninstrumented: the line's `value`, the whole-job throughput.  (4) The same with the dominant
     # class's events: a launch there shares the chip with the other batch's kernels, so its span is
     # longer (roofline.pipelined_avg_launch_us) while the chip does more work per second.
-    pipe.profile([dominant])
-    dt_serial_prof = timed(step_greedy, args.steps, "greedy_serial_profiled", n=1)
-    dom_launches, dom_ms = pipe.profile_read()[dominant]
-    pipe.profile([])
-    dt_serial = timed(step_greedy, args.steps, "greedy_serial", n=1)
+    if full:
+        eng.profile(CLASSES)
+        step_greedy()
+        breakdown = eng.profile_read()
+        dominant = max(breakdown, key=lambda c: breakdown[c][1])
+        pipe.profile([dominant])
+        dt_serial_prof = timed(step_greedy, args.steps, "greedy_serial_profiled", n=1)
+        dom_launches, dom_ms = pipe.profile_read()[dominant]
+        pipe.profile([])
+    if full or args.streams <= 1:
+        dt_serial = timed(step_greedy, args.steps, "greedy_serial", n=1)
     pl_dom = None
     if args.streams > 1:
         for _ in range(args.streams):  # every handle of the timed region warm
             pipe.submit(step_greedy, args.streams)
         flags["warmup_pipeline"] = pipe.device_flags()
         dt = timed(step_greedy, args.steps, "greedy", n=args.streams)
-        pipe.profile([dominant])
-        timed(step_greedy, args.steps, "greedy_pipelined_profiled", n=args.streams)
-        pl_dom = pipe.profile_read()[dominant]
-        pipe.profile([])
+        dump_outputs()
+        if full:
+            pipe.profile([dominant])
+            timed(step_greedy, args.steps, "greedy_pipelined_profiled", n=args.streams)
+            pl_dom = pipe.profile_read()[dominant]
+            pipe.profile([])
     else:
         dt = dt_serial
+        dump_outputs()
 
     Tp = T // 3
     value = B * world * args.steps / dt
@@ -389,7 +426,7 @@ def main():
         except Exception:
             return {}
     # committed PMC passes (tools/probes/profile_r03.sh): greedy step, and beam 8 at B = 256
-    pmc_greedy, pmc_beam = load_pmc("pmc_traffic.json"), load_pmc("pmc_traffic_beam.json")
+    pmc_greedy, pmc_beam = (load_pmc("pmc_traffic.json"), load_pmc("pmc_traffic_beam.json")) if full else ({}, {})
 
     def roof(cls, launches, ms, steps, Bc, Rc, pmc=pmc_greedy, fold=False):
         """Achieved rate of one kernel class: algorithmic work of `steps` steps over its launches'
@@ -419,14 +456,15 @@ def main():
     # the folded decode step ran when the instrumented step launched the LSTMCell GEMM once
     def folded(bd):
         return bd.get("dec_lstm", (0, 0.0))[0] == 1
-    fold = folded(breakdown)
-    dom = roof(dominant, dom_launches, dom_ms, args.steps, B, B, fold=fold)
-    pl_roof = roof(dominant, pl_dom[0], pl_dom[1], args.steps, B, B, fold=fold) if pl_dom else None
-    # every class of the instrumented step (one step: launches and ms of that step)
-    kernels = {c: roof(c, n, ms, 1, B, B, fold=fold) for c, (n, ms) in breakdown.items()}
-    achieved, peak, unit, bound = dom["achieved"], dom["peak"], dom["unit"], dom["bound"]
-    avg_launch_s = dom["avg_launch_us"] / 1e6
-    traffic = dom.get("traffic")
+    if full:
+        fold = folded(breakdown)
+        dom = roof(dominant, dom_launches, dom_ms, args.steps, B, B, fold=fold)
+        pl_roof = roof(dominant, pl_dom[0], pl_dom[1], args.steps, B, B, fold=fold) if pl_dom else None
+        # every class of the instrumented step (one step: launches and ms of that step)
+        kernels = {c: roof(c, n, ms, 1, B, B, fold=fold) for c, (n, ms) in breakdown.items()}
+        achieved, peak, unit, bound = dom["achieved"], dom["peak"], dom["unit"], dom["bound"]
+        avg_launch_s = dom["avg_launch_us"] / 1e6
+        traffic = dom.get("traffic")
 
     def beam_line(Bb, k, steps, tag, n=1):
         fbb = torch.from_numpy(fbank_batch(rank * Bb, Bb, T)).to(dev)
@@ -701,6 +739,14 @@ def main():
                        "global_batch": B * world, "seq_len": T, "parallelism": f"dp{world}"},
             "rtf": dt / args.steps / (B * world * AUDIO_S_PER_UTT),
             "batches_in_flight": args.streams,
+            "device_ms_per_step": step_stats("greedy"),
+            "device_ms_note": "per timed step, HIP events on the compute stream around each step (device "
+                              "time incl. any launch gaps; SURVEY 8d: median of the steps)",
+            "decode_launch": "hipGraph replay" if args.graphs else "eager launches",
+            "weights_bcast_s": weight_s,
+        }
+        # what --full measured beside the headline
+        rec.update({} if not full else {
             "greedy_serial": {"value": B * world * args.steps / dt_serial, "unit": "utt/s",
                               "ms_per_step": 1000.0 * dt_serial / args.steps,
                               "device_ms_per_step": step_stats("greedy_serial"),
@@ -708,10 +754,6 @@ def main():
                               "note": "the same steps with one batch in flight (the round-5 headline's loop); "
                                       "ms_per_step_with_dominant_events: the roofline's pass, an event pair "
                                       "around each launch of the dominant class"},
-            "device_ms_per_step": step_stats("greedy"),
-            "device_ms_note": "per timed step, HIP events on the compute stream around each step (device "
-                              "time incl. any launch gaps; SURVEY 8d: median of the steps)",
-            "decode_launch": "hipGraph replay" if args.graphs else "eager launches",
             "decode_step": "folded (2 launches per step: attention with the LSTM cell, fused projection | "
                            "gate GEMM)" if fold else "3 launches per step (LSTMCell, attention, projection)",
             "beam": beam,
@@ -743,11 +785,10 @@ def main():
             "config5_beam16_lm": sharded.get("config5"),
             "f32_exact_path": f32_cmp,
             "kernel_breakdown_ms": {k: round(v[1], 3) for k, v in breakdown.items()},
-            "weights_bcast_s": weight_s,
-            "device_flags": flags,
-            "device_flags_clean": all(v == 0 for v in flags.values()),
             "cpu_baseline": cpu,
-        }
+        })
+        # guard bits of every region that ran (read after each)
+        rec.update({"device_flags": flags, "device_flags_clean": all(v == 0 for v in flags.values())})
         if cpu:
             rec["speedup_vs_cpu"] = value / cpu["value"]
         print(json.dumps(rec), flush=True)

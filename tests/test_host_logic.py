@@ -251,7 +251,8 @@ def test_manifest_and_eval_dataset_host(tmp_path):
 
 
 # ---------------------------------------------------------------- vocabulary (a13, data.py:373-374)
-DICT_PKL = "/root/reference/dict.pkl"
+# the reference's vocabulary file, byte for byte (its sha256 below), kept as a fixture
+DICT_PKL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dict.pkl")
 DICT_PKL_SHA256 = "d81577bf8967efbfc587ad84e5653d95e2554ac980b469f1ca7814cce3b1d9d4"
 VOCAB_JSON_SHA256 = "513ac53677949db69de2bfb3f28c68d7e65c5fa2a09639e79bfb180372bde1dc"
 
@@ -269,7 +270,6 @@ def test_vocab_json_pinned():
     assert all(w2i[w] == i for i, w in i2w.items())
 
 
-@pytest.mark.skipif(not os.path.exists(DICT_PKL), reason="reference dict.pkl only in the build container")
 def test_vocab_json_equals_reference_dict_pkl():
     """Every entry of vocab.json and of its word2int against the reference's dict.pkl itself,
     read by the opcode-level parser (nothing unpickled), whose bytes are pinned by sha256."""

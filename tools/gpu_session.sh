@@ -9,8 +9,8 @@
 #   tests            pytest -m gpu on TESTS (files / node ids, default: the whole tests/ tree),
 #                    filtered by TESTS_K (pytest -k) when set
 #   suite            the whole -m gpu suite (as the driver runs it, -x)
-#   bench            python bench.py $BENCH_ARGS > $OUT/bench.json
-#   ab               interleaved A/B: for each of AB_ROUNDS rounds, bench.py $AB_ARGS once per
+#   bench            python bench.py --full $BENCH_ARGS > $OUT/bench.json
+#   ab               interleaved A/B: for each of AB_ROUNDS rounds, bench.py --full $AB_ARGS once per
 #                    CASR_OPTS value in AB_OPTS (';'-separated; "-" = defaults) -> $OUT/ab_<i>_<r>.json
 #   counters         rocprofv3 -L (the counters this box can collect) -> $OUT/counters.txt
 #   pmc              PMC passes of tools/probes/one_step.py (PMC_MODES: greedy and/or beam) with the
@@ -51,7 +51,7 @@ for s in $STAGES; do
       timeout -k 10 1000 $PYTEST -m gpu tests > $OUT/pytest_gpu.log 2>&1
       rc=$?; tail -1 $OUT/pytest_gpu.log; stop_on $rc suite $OUT/pytest_gpu.log ;;
     bench)
-      timeout -k 10 600 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; stop_on $rc bench $OUT/bench.err
       python tools/bench_line.py $OUT/bench.json ;;
     ab)
@@ -59,7 +59,7 @@ for s in $STAGES; do
       for r in $(seq 1 ${AB_ROUNDS:-2}); do
         for i in "${!opts[@]}"; do
           o="${opts[$i]}"; [ "$o" = "-" ] && o=""
-          CASR_OPTS="$o" timeout -k 10 300 python bench.py --steps ${AB_STEPS:-20} --warmup 3 --no-configs \
+          CASR_OPTS="$o" timeout -k 10 300 python bench.py --full --steps ${AB_STEPS:-20} --warmup 3 --no-configs \
             --no-cpu-baseline --no-f32-compare ${AB_ARGS} > $OUT/ab_${i}_$r.json 2> $OUT/ab.err
           rc=$?; stop_on $rc ab $OUT/ab.err
           echo -n "[$r] opts='$o' "; python tools/bench_line.py $OUT/ab_${i}_$r.json
@@ -110,7 +110,7 @@ for s in $STAGES; do
       rc=$?; tail -20 $OUT/rec_trace.txt; stop_on $rc trace $OUT/rec_trace.txt ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-        python3 bench.py --steps 20 --warmup 2 --streams 1 --no-beam --no-configs --no-f32-compare --no-cpu-baseline \
+        python3 bench.py --full --steps 20 --warmup 2 --streams 1 --no-beam --no-configs --no-f32-compare --no-cpu-baseline \
         > $OUT/prof_bench.json 2> $OUT/prof.err
       echo "rocprofv3 kernel trace of the default recurrence launch: exit status $?" | tee $OUT/prof_rc.txt
       python tools/prof_by_grid.py $OUT/prof/run_kernel_trace.csv 30 > $OUT/prof_by_grid.txt 2>&1

@@ -3,6 +3,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 i=0
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the breakdowns and the beam line are --full measurements
 for r in $(seq 1 ${ROUNDS:-2}); do
   for cfg in $SWEEP; do
     i=$((i+1))

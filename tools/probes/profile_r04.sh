@@ -31,7 +31,7 @@ python tools/prof_by_grid.py $O/prof_beam/run_kernel_trace.csv 30 > $O/prof_beam
 head -12 $O/prof_beam_by_grid.txt
 unset CASR_OPTS
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
-  python3 bench.py --steps 20 --warmup 2 --no-beam --no-configs --no-f32-compare --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err
+  python3 bench.py --full --steps 20 --warmup 2 --no-beam --no-configs --no-f32-compare --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err
 echo "rocprofv3 kernel trace of the default (cooperative) launch: exit status $?" | tee $O/prof_rc.txt
 python tools/prof_by_grid.py $O/prof/run_kernel_trace.csv 30 > $O/prof_by_grid.txt 2>&1
 head -12 $O/prof_by_grid.txt
