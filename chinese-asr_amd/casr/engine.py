@@ -209,6 +209,31 @@ class Engine:
         _lib.check(self.lib.casr_beam_records(self.handle, _ptr(rt), _ptr(rs), _ptr(rv), _stream()), self.handle)
         return rt, rs, rv
 
+    def score(self, targets, tgt_len, alignment=False, best=False, mean=False):
+        """Teacher-forced pass over the last encode (casr_score): targets [B, L] int (1 <= L <=
+        max_len), tgt_len [B] scored positions per utterance.  Returns token_logp [B, L] (0 past
+        tgt_len), total_logp [B], and on request best_token / best_logp [B, L], mean_logp [B, L]
+        (the label-smoothing term) and alignment [L, Tp, B].  Like greedy / beam it is the decode
+        half of run_checked (flag 32 raises, flag 128 re-runs at f32)."""
+        dev = self.device
+        targets = torch.as_tensor(targets).to(dev, torch.int32).contiguous()
+        tgt_len = torch.as_tensor(tgt_len).to(dev, torch.int32).contiguous()
+        if targets.dim() != 2 or targets.shape[0] != self._B or tgt_len.shape != (self._B,):
+            raise ValueError(f"score: targets must be [B={self._B}, L] and tgt_len [B]")
+        B, L = targets.shape
+        token_logp = torch.empty(B, L, dtype=torch.float32, device=dev)
+        total = torch.empty(B, dtype=torch.float32, device=dev)
+        best_token = torch.empty(B, L, dtype=torch.int32, device=dev) if best else None
+        best_logp = torch.empty(B, L, dtype=torch.float32, device=dev) if best else None
+        mean_logp = torch.empty(B, L, dtype=torch.float32, device=dev) if mean else None
+        align = torch.zeros(L, self._Tp, B, device=dev) if alignment else None
+        _lib.check(self.lib.casr_score(self.handle, _ptr(targets), _ptr(tgt_len), int(L), _ptr(token_logp), _ptr(total),
+                                       _ptr(best_token), _ptr(best_logp), _ptr(mean_logp), _ptr(align), _stream()),
+                   self.handle)
+        self._keep_score = (targets, tgt_len)  # read by the enqueued kernels
+        return dict(token_logp=token_logp, total_logp=total, best_token=best_token, best_logp=best_logp,
+                    mean_logp=mean_logp, alignment=align, tgt_len=tgt_len)
+
     def device_flags(self):
         """Guard bits raised since the previous read (read and clear: every encode / decode in
         between is covered; 0 = clean); synchronises the stream."""

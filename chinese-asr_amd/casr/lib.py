@@ -22,7 +22,7 @@ EXPORTS = [
     "casr_beam_records", "casr_profile_enable", "casr_profile_read", "casr_set_graphs",
     "casr_device_flags", "casr_set_persistent", "casr_recurrence_mode", "casr_log_mel",
     "casr_log_mel_frames", "casr_mel_filterbank", "casr_set_precision", "casr_get_precision",
-    "casr_set_option", "casr_get_option",
+    "casr_set_option", "casr_get_option", "casr_score",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -105,6 +105,7 @@ def load(path=None, variant=None):
         "casr_greedy": (i32, [vp, vp, vp, vp, vp, vp, vp]),
         "casr_beam": (i32, [vp, i32, f32, f32, vp, vp, vp, vp, vp]),
         "casr_beam_records": (i32, [vp, vp, vp, vp, vp]),
+        "casr_score": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
         "casr_profile_enable": (i32, [vp, ctypes.c_uint32]),
         "casr_set_graphs": (i32, [vp, i32]),
         "casr_device_flags": (i32, [vp, ctypes.POINTER(ctypes.c_int32), vp]),

@@ -12,6 +12,9 @@ EvalOutput = namedtuple('EvalOutput', ('pred_text', 'score', 'text', 'wer', 'n',
                                        'audio_feat_len', 'text_len'))
 EncoderOutput = namedtuple('EncoderOutput', ('out', 'out_lens', 'state'))
 DecoderOutput = namedtuple('DecoderOutput', ('logit', 'attn_hidden_state', 'alignment', 'cell_state'))
+# Model.score_one_batch (teacher-forced scoring; no reference counterpart)
+ScoreOutput = namedtuple('ScoreOutput', ('token_logp', 'score', 'loss', 'best_text', 'times', 'token_loss', 'ids',
+                                         'tgt_len'))
 
 
 def edit_distance(a, b):
@@ -171,3 +174,86 @@ def second_pass_arrays(rec_tokens, rec_score, rec_valid, int2word, lm_model, lm_
         out[b] = (full[i, :lens[i]].tolist(), scores[i])
     return out
 
+
+# ------------------------------------------------------------------ teacher-forced scoring (Engine.score)
+def encode_targets(texts, word2int, eos, unk, V=None, max_len=None):
+    """Transcripts (strings or lists of words) -> (ids [B, L] int32 padded with 0, lens [B] int32).
+    Unknown words become ``unk``; ``eos`` (None: nothing) is appended to every transcript, so it is
+    scored as the reference's targets are (data.py:192-193).  L is the longest row (at least 1).
+    An id outside [0, V) raises ValueError here, on the host, instead of the device's clamp and
+    guard bit (V defaults to one past the largest id of word2int); so does a row longer than
+    ``max_len``."""
+    V = (max(word2int.values()) + 1 if word2int else 0) if V is None else int(V)
+    rows = []
+    for t in texts:
+        ids = [word2int.get(w, unk) for w in t]
+        if eos is not None:
+            ids.append(eos)
+        rows.append(ids)
+    for b, ids in enumerate(rows):
+        bad = [i for i in ids if not (isinstance(i, (int, np.integer)) and 0 <= i < V)]
+        if bad:
+            raise ValueError(f"transcript {b}: token id {bad[0]} outside [0, {V})")
+        if max_len is not None and len(ids) > max_len:
+            raise ValueError(f"transcript {b}: {len(ids)} tokens > max_len {max_len}")
+    L = max([len(r) for r in rows] + [1])
+    out = np.zeros((len(rows), L), np.int32)
+    for b, ids in enumerate(rows):
+        out[b, :len(ids)] = ids
+    return out, np.array([len(r) for r in rows], np.int32)
+
+
+def score_outputs(token_logp, tgt_len, finished):
+    """Per-utterance totals of a teacher-forced pass, and the score in the form greedy decoding
+    reports (model.py:593): sum / (len + finished), where tgt_len = len + finished counts the
+    scored eos of a finished hypothesis, and 0.0 for an empty transcript (len == 0), as
+    greedy_outputs.  Host numpy inputs; returns (totals float32 [B], scores list[float])."""
+    token_logp = np.asarray(token_logp, np.float32)
+    tgt_len = np.asarray(tgt_len).astype(np.int64)
+    fin = np.asarray(finished).astype(np.int64)
+    totals = np.zeros(token_logp.shape[0], np.float32)
+    score = []
+    for b in range(token_logp.shape[0]):
+        acc = np.float32(0.0)
+        for l in range(int(tgt_len[b])):  # ascending, f32: the device's total_logp
+            acc = np.float32(acc + token_logp[b, l])
+        totals[b] = acc
+        n = int(tgt_len[b]) - int(fin[b])
+        score.append(0.0 if n <= 0 else float(acc) / (n + int(fin[b])))
+    return totals, score
+
+
+def label_smoothed_loss(token_logp, mean_logp, tgt_len, V, ls):
+    """util.py:265-279 per scored token, from the two log-probability terms the device returns:
+    with lp_t = logit_t - lse and mean_logp = sum(logits) / V - lse,
+        loss = -[(1 - ls) lp_t + ls / (V - 1) (V mean_logp - lp_t)]
+    (the reference's (1 - ls) logit_t + ls / (V - 1) (sum(logits) - logit_t) - lse, negated).
+    Returns float32 [B, L], 0 past tgt_len; the reference's criterion then takes the mean over the
+    scored tokens."""
+    lp = np.asarray(token_logp, np.float64)
+    mp = np.asarray(mean_logp, np.float64)
+    loss = -((1.0 - ls) * lp + (ls / (V - 1)) * (V * mp - lp))
+    mask = np.arange(lp.shape[1])[None, :] < np.asarray(tgt_len).reshape(-1, 1)
+    return np.where(mask, loss, 0.0).astype(np.float32)
+
+
+def token_times(align, enc_lens, tgt_len, sample_rate=16000):
+    """Where each scored token sits in the audio, from the attention weights of a teacher-forced
+    pass: align [L, Tp, B] (Engine.score(alignment=True)), enc_lens [B] encoder frames per
+    utterance, tgt_len [B].  Per scored token: ``frame`` the attention's argmax frame (the first of
+    equal maxima) and ``expect`` the expectation sum_t t alpha_t, both over the utterance's own
+    frames; ``frame_s`` / ``expect_s`` the same in seconds (one encoder frame = 3 stacked frames x
+    160 samples = 30 ms at 16 kHz).  Arrays [B, L]; positions past tgt_len hold -1 / 0."""
+    align = np.asarray(align)
+    L, _, B = align.shape
+    frame = np.full((B, L), -1, np.int64)
+    expect = np.zeros((B, L), np.float64)
+    for b in range(B):
+        n, T = min(int(tgt_len[b]), L), int(enc_lens[b])
+        if n == 0 or T == 0:
+            continue
+        a = align[:n, :T, b].astype(np.float64)
+        frame[b, :n] = a.argmax(axis=1)
+        expect[b, :n] = a @ np.arange(T, dtype=np.float64)
+    sec = 3 * 160 / float(sample_rate)
+    return dict(frame=frame, expect=expect, frame_s=np.where(frame >= 0, frame * sec, 0.0), expect_s=expect * sec)

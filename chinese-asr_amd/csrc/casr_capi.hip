@@ -195,6 +195,7 @@ struct casr_handle {
   DevBuf st, logits, small, bp, tk, rec, beam_small;
   DevBuf ksbuf;  // the greedy folded GEMM's k-split sums and counters (R <= 32, CASR_OPT_DEC_KSPLIT)
   DevBuf asbuf;  // the split greedy attention's partials and counters (R <= 64, CASR_OPT_ATTN_SPLIT)
+  DevBuf scorebuf;  // casr_score: state history, row partials, token feed (score_workspace_bytes)
   DecodeBufs d{};
   DevBuf gout;  // internal decode outputs written by captured graphs
   Profiler prof;
@@ -544,7 +545,7 @@ void casr_destroy(casr_handle* h) {
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->beam_small, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
-                    &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf})
+                    &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf})
     b->release();
   delete h;
 }
@@ -1109,6 +1110,27 @@ int casr_beam_records(casr_handle* h, int32_t* rec_tokens, float* rec_score, uin
   int rc = prepare_decode(h, h->dec_k, a, false);
   if (rc) return rc;
   HIP_OK(h, run_beam_records(a, h->d, rec_tokens, rec_score, rec_valid, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, int L, float* token_logp,
+               float* total_logp, int32_t* best_token, float* best_logp, float* mean_logp, float* align,
+               void* stream) {
+  if (!h || !targets || !tgt_len || !token_logp || !total_logp)
+    return fail(h, CASR_ERR_ARG, "casr_score: NULL handle, targets, tgt_len, token_logp or total_logp");
+  if (!h->W) return fail(h, CASR_ERR_STATE, "casr_score before casr_bind_weights");
+  if (!h->encoded) return fail(h, CASR_ERR_STATE, "casr_score before casr_encode");
+  if (L < 1 || L > h->cfg.max_len) return fail(h, CASR_ERR_ARG, "casr_score: L = %d not in [1, %d]", L, h->cfg.max_len);
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeArgs a{};
+  int rc = prepare_decode(h, 1, a, true);
+  if (rc) return rc;
+  if (score_col_blocks(a) > GP_NB)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_score: %d projection column blocks > %d row partials", score_col_blocks(a), GP_NB);
+  HIP_OK(h, h->scorebuf.ensure(score_workspace_bytes(h->B, L)));
+  const ScoreBufs sb = score_carve(h->scorebuf.p, h->B, L);
+  HIP_OK(h, run_score(a, h->d, sb, targets, tgt_len, L, token_logp, total_logp, best_token, best_logp, mean_logp, align,
+                      (hipStream_t)stream));
   return CASR_OK;
 }
 

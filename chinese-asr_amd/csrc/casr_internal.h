@@ -492,4 +492,29 @@ hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float l
 hipError_t run_beam_records(const DecodeArgs& a, DecodeBufs& d, int32_t* rec_tokens,
                             float* rec_score, uint8_t* rec_valid, hipStream_t s);
 
+// Teacher-forced scoring (casr_score, score.hip).  L steps of the three-launch step without its
+// projection (decoder.hip score_steps), every step's state slab kept in a history, then ONE
+// projection GEMM over the R = L B rows [ctx | h] of slabs 1..L (score_project) whose epilogue
+// writes per row and 80-column block the greedy partials, the block's sum of logits and the
+// target's logit; score_rows_kernel combines them.  Row i = l B + b everywhere.
+struct ScoreBufs {
+  float* hist;      // [L + 1][B][ST] state slabs: slab 0 the initial state, slab l + 1 step l's
+  GreedyPart part;  // [L B][GP_NB] (tmx unused)
+  float* xsum;      // [L B][GP_NB] sum of the block's logits over columns n < V
+  float* tl;        // [L B] the target's logit (rows with a scored target only)
+  int32_t* feed;    // [L][B] decoder input of step l: sos, then targets[b][l - 1] (eos past tgt_len)
+  int32_t* tgt;     // [L][B] targets[b][l] clamped to [0, V), or -1 at l >= tgt_len[b]
+};
+size_t score_workspace_bytes(int B, int L);
+ScoreBufs score_carve(void* base, int B, int L);
+// projection column blocks with row partials (the three-launch step's, whatever a.fold says)
+int score_col_blocks(const DecodeArgs& a);
+// decoder.hip: the step loop (a.k == 1, a.fold == 0, a.greedy_run == 1) and the batched projection
+hipError_t score_steps(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, int L, float* align, hipStream_t s);
+hipError_t score_project(const DecodeArgs& a, const DecodeBufs& d, const ScoreBufs& sb, int L, hipStream_t s);
+// score.hip
+hipError_t run_score(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, const int32_t* targets,
+                     const int32_t* tgt_len, int L, float* token_logp, float* total_logp, int32_t* best_token,
+                     float* best_logp, float* mean_logp, float* align, hipStream_t s);
+
 }  // namespace casr

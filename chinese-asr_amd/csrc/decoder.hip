@@ -961,6 +961,61 @@ struct ProjEpi {
   }
 };
 
+// Epilogue of the batched teacher-forced projection (casr_score, casr_internal.h ScoreBufs): no
+// logits are stored.  Per row and 80-column block: the greedy partials exactly as ProjEpi's
+// (proj_row_partials), the sum of the block's logits over columns n < V (the label-smoothing
+// term), and the target's logit, stored by the one lane of the whole grid that holds column
+// tgt[row] of that row (tgt < 0: a masked position, no writer).
+struct ScoreEpi {
+  static constexpr int kTraceClass = 1;
+  static constexpr bool kPreRowFree = true;  // the column biases
+  static constexpr bool kScratch = false;
+  const float* bias;
+  int R, V;
+  int32_t* err;
+  GreedyPart gp;
+  float* xsum;         // [R][GP_NB]
+  const int32_t* tgt;  // [R]
+  float* tl;           // [R]
+  struct Pre {
+    float bn[16];
+  };
+  __device__ __forceinline__ int32_t* err_flags() const { return err; }
+  __device__ __forceinline__ bool skip() const { return false; }
+  template <int NTN>
+  __device__ __forceinline__ void prefetch(Pre& p, int, int nb, int u, int&) const {
+    static_assert(NTN <= 16, "bias prefetch slots");
+#pragma unroll
+    for (int tn = 0; tn < NTN; ++tn) {
+      const int n = (nb * NTN + tn) * 16 + u;
+      p.bn[tn] = n < V ? bias[n] : 0.f;
+    }
+  }
+  template <int NTN>
+  __device__ __forceinline__ void late(Pre&, int, int, int) const {}
+  template <int NTN = 5>
+  __device__ __forceinline__ void run(const f32x4 (&acc)[NTN], int row0, int nb, int u, const Pre& p, float*) const {
+    int t[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t[e] = row0 + e < R ? tgt[row0 + e] : -1;
+    proj_row_partials<NTN>(acc, p.bn, row0, nb, u, gp, R, V);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int row = row0 + e;
+      float sx = 0.f;
+#pragma unroll
+      for (int tn = 0; tn < NTN; ++tn) {
+        const int n = (nb * NTN + tn) * 16 + u;
+        const float x = acc[tn][e] + p.bn[tn];  // proj_row_partials' logit
+        if (n < V) sx += x;
+        if (n == t[e] && n < V) tl[row] = x;  // (t >= 0 only at row < R)
+      }
+      sx = row16_sum(sx);
+      if (u == 0 && row < R) xsum[(size_t)row * GP_NB + nb] = sx;
+    }
+  }
+};
+
 // Epilogue of the folded step's GEMM (casr_internal.h KB): columns are 16-column tiles of the
 // fused image, vocabulary tiles T < VT first (greedy partials exactly as ProjEpi's, over the
 // tile's columns n < V), then the LSTM gate tiles gt = T - VT of the next step, stored raw into
@@ -1787,6 +1842,48 @@ hipError_t run_greedy(const DecodeArgs& a_in, DecodeBufs& d, int32_t* tokens, in
                          accum, tokens, d.newdone, d.err);
     }
   }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ teacher-forced scoring (casr_score)
+int score_col_blocks(const DecodeArgs& a) { return (a.L.VP / 16 + 4) / 5; }
+
+// L steps of the three-launch step without its projection: the LSTMCell GEMM and the attention,
+// unchanged.  Step l reads slab l of the history and writes slab l + 1 (every word of a state row
+// is written by the two launches), feeds row l of sb.feed with the identity predecessor, and is
+// never skipped (the early-exit counters stay 0).  sb.feed holds valid ids only (score.hip).
+hipError_t score_steps(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, int L, float* align, hipStream_t s) {
+  const int R = a.B;
+  if (a.k != 1 || a.fold || !a.greedy_run) return hipErrorInvalidValue;
+  FillList fl;
+  fl.add32(d.newdone, 0, a.max_len);
+  hipError_t e = fill_multi(fl, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, sb.hist, a.hfin, a.cfin, a.B, 1, a.sos, d.tok[0],
+                     d.src[0], d.score[0], nullptr);
+  DecodeBufs ds = d;
+  for (int l = 0; l < L; ++l) {
+    ds.st[l & 1] = sb.hist + (size_t)l * R * ST;
+    ds.st[(l + 1) & 1] = sb.hist + (size_t)(l + 1) * R * ST;
+    ds.tok[l & 1] = sb.feed + (size_t)l * R;
+    ds.src[l & 1] = d.src[0];
+    e = decode_step(a, ds, l, R, align ? align + (size_t)l * a.Tp * R : nullptr, s, nullptr, false);
+    if (e != hipSuccess) return e;
+  }
+  return hipGetLastError();
+}
+
+// one projection GEMM over the L B rows [ctx | h] of slabs 1..L: row i = l B + b is state row B + i
+// of the history, so the step projection's A source (ProjA) serves unchanged
+hipError_t score_project(const DecodeArgs& a, const DecodeBufs& d, const ScoreBufs& sb, int L, hipStream_t s) {
+  const int R = L * a.B;
+  if (score_col_blocks(a) > GP_NB) return hipErrorInvalidValue;
+  ProfScope ps(a.prof, CASR_K_PROJ, s);
+  ProjA asrc{sb.hist + (size_t)a.B * ST, R, a.s16};
+  GreedyPart gp = sb.part;
+  gp.tmx = nullptr;
+  ScoreEpi epi{a.W + a.L.proj_b, R, a.V, d.err, gp, sb.xsum, sb.tgt, sb.tl};
+  launch_proj(R, a.L.VP / 16, a.W + (a.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.s16, a.proj_small, s);
   return hipGetLastError();
 }
 

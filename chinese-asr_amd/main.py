@@ -2,7 +2,8 @@
 """Drop-in for the reference's ``main.py`` (main.py:19-102) on the MI355X path.
 
 ``parse(path, model, audio_base, lm_model, bw)`` and ``ASR(lm_path=None, bw=None)(path)`` keep
-the reference signatures and results.  The chain wav -> log-mel -> delta/stack -> CMVN
+the reference signatures and results; ``align(path, text, model, audio_base)`` is this path's own
+addition (forced alignment of a given transcript).  The chain wav -> log-mel -> delta/stack -> CMVN
 (eps 1e-6, main.py:37) -> encoder -> greedy / beam (+ second pass with a KenLM-like
 ``lm_model.score(s, bos=True)``) runs on the GPU through the casr C ABI.  Format conversion
 (``convert_audio``: ffmpeg + sox, main.py:19-24) stays an external tool: it is used when present,
@@ -61,6 +62,17 @@ def parse(path, model, audio_base, lm_model, bw):
     else:
         res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, text)
     return res.pred_text[0]
+
+
+def align(path, text, model, audio_base):
+    """Forced alignment of a known transcript: one file and its text -> [(char, start_s, logp)],
+    the attention's argmax frame of each character in seconds and its teacher-forced
+    log-probability (Model.score_one_batch; the closing eos is scored but not listed)."""
+    audio = path if not isinstance(path, (str, os.PathLike)) else fast_read(convert_audio(path))
+    data, lens = features_for([audio])
+    res = model.score_one_batch(model.device, data, lens, [text], audio_base.word2int, audio_base.int2word)
+    start = res.times['frame_s'][0]
+    return [(ch, float(start[i]), float(res.token_logp[0][i])) for i, ch in enumerate(text)]
 
 
 def parse_batch(paths, model, audio_base, lm_model=None, bw=None):

@@ -13,7 +13,8 @@ from gpd import gpd
 from casr.config import config_from_gpd
 from casr.engine import Engine
 from casr.lib import pack_weights
-from casr.results import EvalOutput, get_wer, greedy_outputs, greedy_steps, second_pass_arrays
+from casr.results import (EvalOutput, ScoreOutput, encode_targets, get_wer, greedy_outputs, greedy_steps,
+                          label_smoothed_loss, score_outputs, second_pass_arrays, token_times)
 from casr.vocab import load_vocab
 from casr.weights import check_state_dicts, load_checkpoint, save_checkpoint, synthetic_state_dicts
 
@@ -152,3 +153,34 @@ class Model(object):
             wer = np.mean([get_wer(p, t) for p, t in zip(pred_text, text)])
         return EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=None,
                           audio_feat_len=None, text_len=None)
+
+    @torch.no_grad()
+    def score_one_batch(self, device, data, lens, text, word2int=None, int2word=None, eos=True):
+        """Teacher-forced scoring of given transcripts (the reference's training-time forward,
+        model.py:405-469, and its label-smoothed criterion, util.py:265-279, as an evaluation):
+        ``text`` one transcript per utterance (a string or a list of words; or lists of ids when
+        ``word2int`` is False).  With ``eos`` every transcript is scored with its closing eos.
+        Returns a ScoreOutput: token_logp (one list per utterance), score (sum / scored tokens, the
+        form greedy reports), loss (label-smoothed with gpd['label_smooth'] if present, else 0: the
+        mean over all scored tokens), best_text (the per-step argmax), times (token_times)."""
+        self.model.eval()
+        if word2int is False:
+            w2i = {i: i for i in range(self.cfg.vocab)}
+        else:
+            w2i = word2int if word2int is not None else load_vocab()[0]
+        unk = gpd.get('unk', 3)
+        ids, n = encode_targets(text, w2i, self.cfg.eos if eos else None, unk, V=self.cfg.vocab,
+                                max_len=self.cfg.max_len)
+        bsz, lens, out = self._run(data, lens, lambda: self.engine.score(ids, n, alignment=True, best=True, mean=True))
+        lp = out['token_logp'].cpu().numpy()
+        fin = np.full(bsz, 1 if eos else 0)
+        _, score = score_outputs(lp, n, fin)
+        V, ls = self.cfg.vocab, float(gpd.get('label_smooth', 0.0))
+        tok_loss = label_smoothed_loss(lp, out['mean_logp'].cpu().numpy(), n, V, ls)
+        loss = float(tok_loss.sum(dtype=np.float64) / max(int(n.sum()), 1))
+        i2w = self._int2word(int2word)
+        bt = out['best_token'].cpu().numpy()
+        best_text = [''.join(i2w[int(e)] for e in bt[b, :n[b] - (1 if eos else 0)]) for b in range(bsz)]
+        times = token_times(out['alignment'].cpu().numpy(), np.asarray(lens), n, gpd.get('sample_rate', 16000))
+        return ScoreOutput(token_logp=[lp[b, :n[b]].tolist() for b in range(bsz)], score=score, loss=loss,
+                           best_text=best_text, times=times, token_loss=tok_loss, ids=ids, tgt_len=n)

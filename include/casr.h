@@ -172,6 +172,35 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
 int casr_beam_records(casr_handle* h, int32_t* rec_tokens, float* rec_score, uint8_t* rec_valid,
                       void* stream);
 
+/* Teacher-forced pass over the last encode (model.py:405-469: steps with compute_logit=False, one
+ * batched projection, util.py:265-279 for the loss terms).  Step l feeds sos (l = 0) or
+ * targets[b][l-1], and scores targets[b][l].
+ *   targets    [B][L] int32 (device), tgt_len [B] (0..L) scored positions per utterance; the caller
+ *              appends eos itself where it wants it scored.  1 <= L <= max_len.
+ *   token_logp [B][L]  log-softmax value of targets[b][l]; exactly 0 for l >= tgt_len[b]
+ *   total_logp [B]     sum over l < tgt_len[b], added in ascending l (deterministic, no float atomics)
+ *   best_token [B][L], best_logp [B][L]  NULL or: first-index argmax of the step's logits and its
+ *              log-prob (each may be NULL on its own); -1 and 0 for l >= tgt_len[b]
+ *   mean_logp  [B][L]  NULL or: (sum_v logit_v)/V - logsumexp  (the label-smoothing term); 0 for
+ *              l >= tgt_len[b]
+ *   align      NULL or [L][Tp][B] attention weights per step (the greedy alignment layout)
+ * Entries of targets at l >= tgt_len[b] are never used as data: any value, negative included, gives
+ * the same outputs and raises no guard bit (steps past an utterance's scored positions feed eos).
+ * An id outside [0, V) at l < tgt_len[b] is clamped to 0 and reported as guard bit 1, as everywhere
+ * else.  The steps are the three-launch decode step's LSTMCell GEMM and attention (the arithmetic of
+ * greedy decoding with CASR_OPT_DEC_FOLD = 0), in the handle's current precision; the projection is
+ * one GEMM over the L B rows of every step, which stores no logits.  Workspace (handle-owned, grows
+ * on demand): (L + 1) B state rows of 10 KB plus 1 KB of row partials per scored row (118 MB at
+ * B = 256, L = 40).  Never replayed as a hipGraph; the timed classes CASR_K_DEC_LSTM, _ATTENTION,
+ * _PROJ and _SELECT cover its launches.  Returns after enqueueing; does not disturb the encode: a
+ * greedy or beam decode after it gives the bits it gives without it.
+ * CASR_ERR_STATE before an encode or before weights are bound; CASR_ERR_ARG for a NULL handle,
+ * targets, tgt_len, token_logp or total_logp, or L out of range; CASR_ERR_UNSUPPORTED when the
+ * vocabulary needs more than 64 projection column blocks (V > 5120). */
+int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, int L,
+               float* token_logp, float* total_logp, int32_t* best_token, float* best_logp,
+               float* mean_logp, float* align, void* stream);
+
 /* Guard bits raised by the device since the previous casr_device_flags call (read and clear;
  * they accumulate over every encode / decode / log-mel call in between, so one read after a
  * series of calls vouches for all of them; 0 = clean): a data-dependent index out of range (1 token, 2 predecessor row, 4 NaN logit
