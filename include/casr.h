@@ -226,7 +226,11 @@ int casr_set_persistent(casr_handle* h, int enable);
  *   CASR_PREC_F32    v_mfma_f32_16x16x4_f32, exact f32 products in k order;
  *   CASR_PREC_S16X3  every f32 operand split as hi + 2^-11 lo (two f16), three f16 MFMAs per
  *                    product (hi.hi + 2^-11 (hi.lo + lo.hi)) on the 16x-faster f16 pipes; 22
- *                    significant operand bits, measured error no larger than the f32 path's.
+ *                    significant operand bits.  Measured per stage against float64
+ *                    (tests/test_gpu_accuracy.py, profiles/accuracy/accuracy_budget.json): at most
+ *                    2.0 times the float32 oracle's own error, and at or below the F32 path's
+ *                    (at most 3.6 times) at every stage but the greedy accum (1.42 against 1.26
+ *                    times, both within the rounding of a 40-term f32 sum).
  *   CASR_PREC_S16X1  (round 6, an opt-in perf arithmetic, never the headline: BASELINE config 2's
  *                    "bf16 perf mode") the hi.hi MFMA of every split product only:
  *                    one f16 MFMA instead of three, 11 significant operand bits (bf16 keeps 8),

@@ -1,0 +1,53 @@
+"""The "[acc]" lines of `pytest -m gpu tests/test_gpu_accuracy.py -s` -> profiles/accuracy/accuracy_budget.json
+and the per-stage table of that test's docstring.
+
+  python tools/acc_lines.py pytest.log [out.json]
+
+Each line reads "[acc] stage shape arithmetic what max_ratio=.. rms_ratio=.. e_ref_max=.. e_max=..": the
+ratio of the device's error to the float32 reference's, both against float64 (tests/f64_ref.py)."""
+import json
+import re
+import sys
+
+LINE = re.compile(r"\[acc\] (\S+) (\S+) (s16x3|f32) (\S+) max_ratio=(\S+) rms_ratio=(\S+) e_ref_max=(\S+) e_max=(\S+)")
+
+
+def parse(text):
+    rows = []
+    for m in LINE.finditer(text):
+        stage, shape, arith, what = m.group(1, 2, 3, 4)
+        mx, rms, eref, emax = (float(x) for x in m.group(5, 6, 7, 8))
+        rows.append(dict(stage=stage, shape=shape, arithmetic=arith, what=what, max_ratio=mx, rms_ratio=rms,
+                         e_ref_max=eref, e_max=emax))
+    return rows
+
+
+def table(rows):
+    """Per stage and quantity, the largest ratios over the shapes, one column pair per arithmetic."""
+    keys = []
+    best = {}
+    for r in rows:
+        k = (r["stage"], r["what"])
+        if k not in keys:
+            keys.append(k)
+        b = best.setdefault(k + (r["arithmetic"],), dict(max_ratio=0.0, rms_ratio=0.0, shape=None, n=0))
+        b["n"] += 1
+        b["rms_ratio"] = max(b["rms_ratio"], r["rms_ratio"])
+        if r["max_ratio"] >= b["max_ratio"]:
+            b["max_ratio"], b["shape"] = r["max_ratio"], r["shape"]
+    out = [f"  {'stage':9s}{'quantity':12s}{'cases':>6s}  {'s16x3 max':>9s} {'rms':>6s}  {'f32 max':>9s} {'rms':>6s}  worst shape (s16x3 / f32)"]
+    for k in keys:
+        a, b = best.get(k + ("s16x3",)), best.get(k + ("f32",))
+        out.append(f"  {k[0]:9s}{k[1]:12s}{a['n']:6d}  {a['max_ratio']:9.2f} {a['rms_ratio']:6.2f}  "
+                   f"{b['max_ratio']:9.2f} {b['rms_ratio']:6.2f}  {a['shape']} / {b['shape']}")
+    return "\n".join(out)
+
+
+if __name__ == "__main__":
+    rows = parse(open(sys.argv[1], encoding="utf-8").read())
+    if len(sys.argv) > 2:
+        with open(sys.argv[2], "w", encoding="utf-8") as f:
+            json.dump(dict(margin=8, reference="float64 (tests/f64_ref.py); ratios are to the float32 oracle's error "
+                           "on the same stage inputs", device="MI355X (gfx950)", cases=rows), f, indent=1)
+            f.write("\n")
+    print(table(rows))
