@@ -34,39 +34,9 @@
 
 namespace casr {
 
-constexpr int AT_THREADS = 512;
 constexpr int AT_WAVES = AT_THREADS / 64;
 constexpr int AT_NQ = HD / 16;  // query partials per row at most (dec_q_slots: one per LSTMCell column block)
-constexpr int AT_MAXG = 8;      // a-groups of the score phase
-constexpr int AT_CH = 20;       // keys rows in flight per score batch (apg = 19 at Tp = 266)
-constexpr int AT_APAD = A + AT_CH;  // q / v rows in LDS, zero-padded so a batch never branches
-
-__host__ __device__ constexpr int attn_tq(int Tp) { return (Tp + 3) & ~3; }
-
-template <int KPB, int MAXG = AT_MAXG>
-__host__ __device__ constexpr int attn_scratch_floats(int Tq) {
-  // score partials [MAXG][KPB][Tq] | context partials [4][KPB][C]
-  return MAXG * KPB * Tq > 4 * KPB * C ? MAXG * KPB * Tq : 4 * KPB * C;
-}
-// (round 6) the split folded greedy attention (attention_kernel<1, 1, true>): a block takes Tq / S
-// steps, so its score phase can use up to 32 a-groups of 4 keys rows (the unsplit form's 8 groups of
-// 16 rows would leave most of the block's threads idle on a short range)
-constexpr int AT_MAXG_SPLIT = 32;
-
-// the folded step's cell phase (CELL): h [HD] | query slices [AT_QS][A]
-constexpr int AT_QS = AT_THREADS / (A / 4);  // 16 unit slices of HD / AT_QS = 32 units
-constexpr int AT_CELL_FLOATS = HD + AT_QS * A;
-static_assert(AT_QS * A >= 4 * HD, "the token's gate-table row fits the query slice area (CELL 1)");
-
-// LDS: qs, eqs [AT_APAD][KPB] | vs, v2s [A] | (AT_MAXG unused) | scratch | es [Tq][KPB] | (CELL: h,
-// query slices) | value rows
-// (CELL 2, the beam cell phase, keeps its h rows and query slices in the score scratch instead)
-template <int KPB, int CELL = 0, bool TSPLIT = false>
-__host__ __device__ constexpr size_t attn_smem_floats(int Tp) {
-  return (size_t)2 * KPB * AT_APAD + 2 * A + AT_MAXG +
-         attn_scratch_floats<KPB, TSPLIT ? AT_MAXG_SPLIT : AT_MAXG>(attn_tq(Tp)) + KPB * attn_tq(Tp) +
-         (CELL == 1 ? AT_CELL_FLOATS : 0);
-}
+// (the LDS layout arithmetic, attn_tq .. attn_smem_floats: attention_lds.h, shared with the decode plan)
 
 // Split exponential form of the score tanh.  tanh(k + q) = 1 - 2 / (1 + e^{2k} e^{2q}): with
 // ek = exp(2k) computed once per encode (KeysEpi, next to the keys) and eq = exp(2q) once per row
@@ -910,7 +880,7 @@ static int attn_npf(int Tp) {
   const size_t budget = attn_lds_budget();
   const size_t room = fixed < budget ? budget - fixed : 0;
   const int rows = (int)(room / (C * sizeof(float))) & ~3;
-  return rows < Tp ? rows : (Tp + 3) & ~3;
+  return rows < Tp ? rows : attn_tq(Tp);
 }
 
 template <int KPB, int CELL = 0>
@@ -928,7 +898,7 @@ static hipError_t launch_kpb(const DecodeArgs& a, float* st, const float* qpart,
   dim3 grid(a.B, (a.k + KPB - 1) / KPB);
   const float* ekT = a.keysT + (size_t)a.B * A * attn_tq(a.Tp);  // KeysEpi: [keys | exp(2 keys)]
   hipLaunchKernelGGL((attention_kernel<KPB, CELL>), grid, dim3(AT_THREADS), shm, s, st, qpart, a.keysT, ekT, a.enc,
-                     a.lens, a.W + a.L.v, a.B * a.k, a.k, a.Tp, align, newdone, l, total, npf, a.attn_direct,
+                     a.lens, a.W + a.L.v, a.B * a.k, a.k, a.Tp, align, newdone, l, total, npf, a.plan.attn_direct,
                      dec_q_slots(a.B * a.k), a.V, cell);
   return hipGetLastError();
 }
@@ -951,7 +921,7 @@ static hipError_t launch_greedy_split(const DecodeArgs& a, float* st, int32_t* n
   const float* ekT = a.keysT + (size_t)a.B * A * attn_tq(a.Tp);
   hipLaunchKernelGGL((attention_kernel<1, 1, true>), dim3(a.B, cell.split), dim3(AT_THREADS), shm, s, st, nullptr,
                      a.keysT, ekT, a.enc, a.lens, a.W + a.L.v, a.B, 1, a.Tp, nullptr, newdone, l, total, npf,
-                     a.attn_direct, dec_q_slots(a.B), a.V, cell);
+                     a.plan.attn_direct, dec_q_slots(a.B), a.V, cell);
   return hipGetLastError();
 }
 
@@ -959,7 +929,7 @@ hipError_t launch_attention_cell_step(const DecodeArgs& a, float* st, const Attn
                                       int32_t* newdone, int l, int total, hipStream_t s) {
   if (a.k == 1 && cell.split > 1 && !align) return launch_greedy_split(a, st, newdone, l, total, s, cell);
   if (a.k == 1) return launch_kpb<1, 1>(a, st, nullptr, align, newdone, l, total, s, cell);
-  switch (attention_kpb(a.B, a.k, a.attn_kpb)) {
+  switch (a.plan.kpb) {
     case 4:
       if (cell.bsel)
         return a.k == 4 ? launch_kpb<4, 3>(a, st, nullptr, align, newdone, l, total, s, cell)
@@ -973,21 +943,9 @@ hipError_t launch_attention_cell_step(const DecodeArgs& a, float* st, const Attn
   }
 }
 
-// beam rows per block at k > 2 (CASR_OPT_ATTN_KPB, 0 = auto).  4 rows per block at B < 256: 8 rows
-// per block (one block per utterance, half the grid at B = 128) measured 3.68 ms vs 2.87 ms per
-// B = 128, k = 8 batch, and 2 or 1 rows per block 2.81 / 3.57 ms against 2.80 (round 2).  At B >= 256
-// one block per utterance already covers the CUs and streams each utterance's keys and values once
-// per step instead of k / 4 times (auto: 8 rows per block there).
-int attention_kpb(int B, int k, int opt) {
-  if (k == 1) return 1;
-  if (k == 2) return 2;
-  if (opt == 4 || opt == 8) return opt;
-  return B >= 256 && k >= 8 ? 8 : 4;
-}
-
 hipError_t launch_attention_step(const DecodeArgs& a, float* st, const float* qpart, float* align,
                                  int32_t* newdone, int l, int total, hipStream_t s) {
-  switch (attention_kpb(a.B, a.k, a.attn_kpb)) {
+  switch (a.plan.kpb) {
     case 1: return launch_kpb<1>(a, st, qpart, align, newdone, l, total, s);
     case 2: return launch_kpb<2>(a, st, qpart, align, newdone, l, total, s);
     case 8: return launch_kpb<8>(a, st, qpart, align, newdone, l, total, s);
@@ -995,28 +953,19 @@ hipError_t launch_attention_step(const DecodeArgs& a, float* st, const float* qp
   }
 }
 
-// the kernel's static LDS (its __shared__ words: 256-336 B), read once from the code object
+// a kernel form's static LDS (its __shared__ words: 256-336 B), from the code object
+// (a template, so the forms are instantiated after the launchers': the code object keeps its order)
 template <int KPB, int CELL = 0>
-static size_t attn_static_bytes() {
-  static const size_t v = [] {
-    hipFuncAttributes fa{};
-    const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(attention_kernel<KPB, CELL>));
-    return e == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)1024;
-  }();
-  return v;
+static int attn_static_bytes() {
+  hipFuncAttributes fa{};
+  const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(attention_kernel<KPB, CELL>));
+  return e == hipSuccess ? (int)fa.sharedSizeBytes : 1024;
 }
-
-// LDS of one attention block without the value prefetch (which takes what is left): the dynamic
-// area plus the kernel's static words, against the 160 KiB a workgroup may hold
-size_t attention_smem_bytes(int B, int k, int Tp, int opt, int cell) {
-  switch (attention_kpb(B, k, opt)) {
-    case 1:
-      return cell == 1 ? attn_smem_floats<1, 1>(Tp) * sizeof(float) + attn_static_bytes<1, 1>()
-                       : attn_smem_floats<1>(Tp) * sizeof(float) + attn_static_bytes<1>();
-    case 2: return attn_smem_floats<2>(Tp) * sizeof(float) + attn_static_bytes<2>();
-    case 8: return attn_smem_floats<8>(Tp) * sizeof(float) + attn_static_bytes<8>();
-    default: return attn_smem_floats<4>(Tp) * sizeof(float) + attn_static_bytes<4>();
-  }
+// read once per process
+AttnStaticLds attention_static_lds() {
+  static const AttnStaticLds v{attn_static_bytes<1>(), attn_static_bytes<1, 1>(), attn_static_bytes<2>(),
+                               attn_static_bytes<4>(), attn_static_bytes<8>()};
+  return v;
 }
 
 void attn_trace_bind(uint32_t* buf) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_at_trace), &buf, sizeof(buf)); }

@@ -192,7 +192,7 @@ struct casr_handle {
   bool encoded = false;
   float* enc_out = nullptr;  // out0 or out1
   // decoder workspace
-  DevBuf st, logits, small, bp, tk, rec, beam_small;
+  DevBuf st, logits, small, bp, tk, rec;
   DevBuf ksbuf;  // the greedy folded GEMM's k-split sums and counters (R <= 32, CASR_OPT_DEC_KSPLIT)
   DevBuf asbuf;  // the split greedy attention's partials and counters (R <= 64, CASR_OPT_ATTN_SPLIT)
   DevBuf scorebuf;  // casr_score: state history, row partials, token feed (score_workspace_bytes)
@@ -544,7 +544,7 @@ void casr_destroy(casr_handle* h) {
   }
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
-                    &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->beam_small, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
+                    &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf})
     b->release();
   delete h;
@@ -579,12 +579,9 @@ int casr_recurrence_mode(const casr_handle* h, int B) {
 int casr_set_option(casr_handle* h, int option, int value) {
   if (!h) return fail(h, CASR_ERR_ARG, "handle NULL");
   if (option < 0 || option >= CASR_OPT_COUNT) return fail(h, CASR_ERR_ARG, "unknown option %d", option);
-  static const int lo[CASR_OPT_COUNT] = {0, 0, 0, -1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  static const int hi[CASR_OPT_COUNT] = {1, 3, 1, 16, 8, 2, 2, 2, 8, 1, 1, CASR_MAX_LAYERS, (1 << CASR_K_COUNT) - 1, 1, 1, 1, 1, 1, AT_SPLIT_MAX};
-  if (option == CASR_OPT_ATTN_KPB && value != 0 && value != 4 && value != 8)
-    return fail(h, CASR_ERR_ARG, "CASR_OPT_ATTN_KPB: 0 (auto), 4 or 8");
-  if (value < lo[option] || value > hi[option])
-    return fail(h, CASR_ERR_ARG, "option %d: value %d not in [%d, %d]", option, value, lo[option], hi[option]);
+  if (!option_value_ok(option, value))
+    return fail(h, CASR_ERR_ARG, "CASR_OPT_%s: value %d not in [%d, %d]%s", OPTIONS[option].name, value, OPTIONS[option].lo,
+                OPTIONS[option].hi, option == CASR_OPT_ATTN_KPB ? ": 0 (auto), 4 or 8" : "");
   if (option == CASR_OPT_DIAG_COLD) {
     if (value) {
       HIP_OK(h, hipSetDevice(h->device));
@@ -672,7 +669,7 @@ static int encode_impl(casr_handle* h, const float* feat, const int32_t* lens, i
   HIP_OK(h, h->hbuf.ensure((size_t)2 * 2 * B * H * sizeof(float)));
   HIP_OK(h, h->cst.ensure((size_t)2 * B * H * sizeof(float)));
   HIP_OK(h, h->hfin.ensure((size_t)2 * B * H * sizeof(float)));
-  const int Tq = (Tp + 3) & ~3;  // keysT row stride (16 B aligned rows for the attention)
+  const int Tq = attn_tq(Tp);  // keysT row stride (16 B aligned rows for the attention)
   HIP_OK(h, h->keysT.ensure(2 * (size_t)B * A * Tq * sizeof(float)));  // [keys | exp(2 keys)] (KeysEpi)
   HIP_OK(h, h->lens.ensure((size_t)B * sizeof(int32_t)));
   if (!fb) HIP_OK(h, hipMemcpyAsync(h->lens.p, lens, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
@@ -894,7 +891,7 @@ int casr_encoder_results(casr_handle* h, float* enc, float* h_final, float* c_fi
     HIP_OK(h, hipMemcpy2DAsync(c_final + H, C * sizeof(float), h->cst.as<float>() + (size_t)B * H,
                                H * sizeof(float), H * sizeof(float), B, hipMemcpyDeviceToDevice, s));
   if (keys)
-    HIP_OK(h, hipMemcpy2DAsync(keys, Tp * sizeof(float), h->keysT.p, ((Tp + 3) & ~3) * sizeof(float),
+    HIP_OK(h, hipMemcpy2DAsync(keys, Tp * sizeof(float), h->keysT.p, attn_tq(Tp) * sizeof(float),
                                Tp * sizeof(float), (size_t)B * A, hipMemcpyDeviceToDevice, s));
   return CASR_OK;
 }
@@ -906,111 +903,109 @@ static bool decode_graph_ok(const casr_handle* h) {
   return (h->graph_mode & CASR_GRAPHS_DECODE) && !(h->prof.mask & dec);
 }
 
-static int prepare_decode(casr_handle* h, int k, DecodeArgs& a, bool greedy) {
+// Every device buffer a decode's launchers read or write.  prepare_decode fills this one list from
+// the handle; DecodeArgs, DecodeBufs and FoldBufs are filled from the list alone, and the list is
+// the pointer part of the decode's hipGraph key (decode_graph_key), so a buffer added here is keyed.
+enum {
+  DP_W, DP_ENC, DP_KEYS, DP_HFIN, DP_CFIN, DP_LENS, DP_ERR,            // weights, the encode, guard words
+  DP_STATE, DP_LOGITS, DP_SMALL, DP_BP, DP_TK, DP_RECORDS,             // decode workspaces
+  DP_KSPLIT, DP_ATTN_SPLIT,                                            // plan.ksplit / plan.split only
+  DP_WFOLD, DP_EMB_GATES, DP_WQ16, DP_GATES,                           // plan.fold only
+  DP_OUT,                                                              // graph replay: the handle-owned outputs
+  DP_COUNT
+};
+struct DecodeCall {
+  DecodeArgs a{};
+  void* buf[DP_COUNT] = {};
+  std::vector<uint64_t> key(int kind, std::initializer_list<float> scalars) const {
+    return decode_graph_key(kind, a.plan, scalars.begin(), (int)scalars.size(), buf, DP_COUNT);
+  }
+};
+
+// One API call's decode: the plan (decode_plan.h), the workspaces it needs, and the launchers' arguments
+static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, DecodeCall& c) {
   if (!h->encoded) return fail(h, CASR_ERR_STATE, "decode before casr_encode");
-  if (k < 1 || k > KMAX_BEAM) return fail(h, CASR_ERR_ARG, "beam width %d not in [1, %d]", k, KMAX_BEAM);
   const int B = h->B, Tp = h->Tp, L = h->cfg.max_len, V = h->cfg.vocab;
-  const int R = B * k;
-  const size_t smem = attention_smem_bytes(B, k, Tp, h->tune[CASR_OPT_ATTN_KPB]);
-  if (smem > 160 * 1024)
-    return fail(h, CASR_ERR_UNSUPPORTED, "attention needs %zu B of LDS (k=%d, Tp=%d) > 160 KiB", smem, k, Tp);
-  HIP_OK(h, h->st.ensure(((size_t)2 * R * ST + (size_t)dec_q_slots(R) * R * A) * sizeof(float)));
-  HIP_OK(h, h->logits.ensure(((size_t)R * V + (size_t)3 * R * GP_NB + (size_t)R * GP_NT) * sizeof(float)));
-  HIP_OK(h, h->small.ensure((size_t)(6 * R + L + B + R + 1) * sizeof(int32_t) + 256));
+  const BlobFacts blob{h->s16(), h->fold_ready, h->proj_small, h->dec_small};
+  const DecodePlan plan = plan_decode(caller, B, Tp, k, want_align, h->cfg, h->L.VP, h->tune, blob, attention_static_lds());
+  switch (plan.status) {
+    case PLAN_BAD_K: return fail(h, CASR_ERR_ARG, "beam width %d not in [1, %d]", k, KMAX_BEAM);
+    case PLAN_LDS:
+      return fail(h, CASR_ERR_UNSUPPORTED, "attention needs %d B of LDS (k=%d, Tp=%d) > 160 KiB", plan.lds_bytes, k, Tp);
+    case PLAN_VOCAB:
+      return fail(h, CASR_ERR_UNSUPPORTED, "casr_score: the vocabulary's projection column blocks > %d row partials", GP_NB);
+    default: break;
+  }
+  if (plan.build_fold32) {
+    const int rc = ensure_fold32(h);
+    if (rc) return rc;
+  }
+  const int R = plan.R;
+  DecodeBufs& d = h->d;
+  d = DecodeBufs{};
+  HIP_OK(h, h->st.ensure(carve_state(nullptr, R, d)));
+  HIP_OK(h, h->logits.ensure(carve_logits(nullptr, R, V, d)));
+  HIP_OK(h, h->small.ensure(carve_small(nullptr, B, R, L, d)));
   HIP_OK(h, h->bp.ensure((size_t)L * R * sizeof(int32_t)));
   HIP_OK(h, h->tk.ensure((size_t)L * R * sizeof(int32_t)));
-  HIP_OK(h, h->rec.ensure((size_t)B * L * k * (sizeof(float) + sizeof(int32_t) + 1) + 256));
-  DecodeBufs& d = h->d;
-  d.st[0] = h->st.as<float>();
-  d.st[1] = d.st[0] + (size_t)R * ST;
-  d.qpart = d.st[1] + (size_t)R * ST;
-  d.logits = h->logits.as<float>();
-  d.part.mx = d.logits + (size_t)R * V;
-  d.part.se = d.part.mx + (size_t)R * GP_NB;
-  d.part.ix = reinterpret_cast<int32_t*>(d.part.se + (size_t)R * GP_NB);
-  d.part.tmx = reinterpret_cast<float*>(d.part.ix + (size_t)R * GP_NB);
-  int32_t* sp = h->small.as<int32_t>();
-  d.tok[0] = sp;
-  d.tok[1] = sp + R;
-  d.src[0] = sp + 2 * R;
-  d.src[1] = sp + 3 * R;
-  d.score[0] = reinterpret_cast<float*>(sp + 4 * R);
-  d.score[1] = reinterpret_cast<float*>(sp + 5 * R);
-  d.newdone = sp + 6 * R;
-  d.topfin = reinterpret_cast<uint8_t*>(sp + 6 * R + L);
-  d.fin = reinterpret_cast<uint8_t*>(sp + 6 * R + L + B);
+  HIP_OK(h, h->rec.ensure(carve_records(nullptr, B, L, plan.k, d)));
+  if (plan.ksplit || plan.ksplit_last) HIP_OK(h, h->ksbuf.ensure(carve_ksplit(nullptr, d)));
+  if (plan.split) HIP_OK(h, h->asbuf.ensure(carve_attn_split(nullptr, R, d)));
+  if (plan.fold) HIP_OK(h, h->fgates.ensure((size_t)R * 4 * HD * sizeof(float)));
   if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "decode: guard words not allocated");
-  d.err = GUARD(h, 0);
-  d.bp = h->bp.as<int32_t>();
-  d.tk = h->tk.as<int32_t>();
-  d.rec_score = h->rec.as<float>();
-  d.rec_src = reinterpret_cast<int32_t*>(d.rec_score + (size_t)B * L * k);
-  d.rec_valid = reinterpret_cast<uint8_t*>(d.rec_src + (size_t)B * L * k);
-  d.aspart = nullptr;
-  d.ascnt = nullptr;
-  d.asplit = 0;
-  if (greedy && R <= 64 && h->tune[CASR_OPT_ATTN_SPLIT]) {
-    const size_t part = (size_t)R * AT_SPLIT_MAX * (C + 4) * sizeof(float);
-    HIP_OK(h, h->asbuf.ensure(part + (size_t)R * sizeof(int32_t)));
-    d.aspart = h->asbuf.as<float>();
-    d.ascnt = reinterpret_cast<int32_t*>(h->asbuf.as<char>() + part);
-    const int o = h->tune[CASR_OPT_ATTN_SPLIT];
-    d.asplit = o == 1 ? (R <= 32 ? 8 : 4) : o;  // 1: by R; 2..AT_SPLIT_MAX: that many
+
+  void** buf = c.buf;
+  buf[DP_W] = const_cast<float*>(h->W);
+  buf[DP_ENC] = h->enc_out;
+  buf[DP_KEYS] = h->keysT.p;
+  buf[DP_HFIN] = h->hfin.p;
+  buf[DP_CFIN] = h->cst.p;
+  buf[DP_LENS] = h->lens.p;
+  buf[DP_ERR] = GUARD(h, 0);
+  buf[DP_STATE] = h->st.p;
+  buf[DP_LOGITS] = h->logits.p;
+  buf[DP_SMALL] = h->small.p;
+  buf[DP_BP] = h->bp.p;
+  buf[DP_TK] = h->tk.p;
+  buf[DP_RECORDS] = h->rec.p;
+  if (plan.ksplit || plan.ksplit_last) buf[DP_KSPLIT] = h->ksbuf.p;
+  if (plan.split) buf[DP_ATTN_SPLIT] = h->asbuf.p;
+  if (plan.fold) {
+    buf[DP_WFOLD] = plan.s16 ? h->wfold.p : h->wfold32.p;
+    buf[DP_EMB_GATES] = h->egates.p;
+    buf[DP_WQ16] = h->wq16.p;
+    buf[DP_GATES] = h->fgates.p;
   }
-  d.kspart = nullptr;
-  d.kscnt = nullptr;
-  if (greedy && R <= 32 && h->tune[CASR_OPT_DEC_KSPLIT]) {
-    HIP_OK(h, h->ksbuf.ensure(DG_KS_PART_BYTES + DG_KS_COUNTERS * sizeof(int32_t)));
-    d.kspart = h->ksbuf.as<float>();
-    d.kscnt = reinterpret_cast<int32_t*>(h->ksbuf.as<char>() + DG_KS_PART_BYTES);
-  }
-  a.W = h->W;
+
+  carve_state(buf[DP_STATE], R, d);
+  carve_logits(buf[DP_LOGITS], R, V, d);
+  carve_small(buf[DP_SMALL], B, R, L, d);
+  carve_records(buf[DP_RECORDS], B, L, plan.k, d);
+  if (buf[DP_KSPLIT]) carve_ksplit(buf[DP_KSPLIT], d);
+  if (buf[DP_ATTN_SPLIT]) carve_attn_split(buf[DP_ATTN_SPLIT], R, d);
+  d.err = static_cast<int32_t*>(buf[DP_ERR]);
+  d.bp = static_cast<int32_t*>(buf[DP_BP]);
+  d.tk = static_cast<int32_t*>(buf[DP_TK]);
+  DecodeArgs& a = c.a;
+  a.W = static_cast<const float*>(buf[DP_W]);
   a.L = h->L;
-  a.enc = h->enc_out;
-  a.keysT = h->keysT.as<float>();
-  a.hfin = h->hfin.as<float>();
-  a.cfin = h->cst.as<float>();
-  a.lens = h->lens.as<int32_t>();
+  a.enc = static_cast<const float*>(buf[DP_ENC]);
+  a.keysT = static_cast<const float*>(buf[DP_KEYS]);
+  a.hfin = static_cast<const float*>(buf[DP_HFIN]);
+  a.cfin = static_cast<const float*>(buf[DP_CFIN]);
+  a.lens = static_cast<const int32_t*>(buf[DP_LENS]);
   a.B = B;
   a.Tp = Tp;
-  a.k = k;
+  a.k = plan.k;
   a.V = V;
   a.max_len = L;
   a.sos = h->cfg.sos;
   a.eos = h->cfg.eos;
   a.temperature = h->cfg.temperature;
-  a.s16 = h->s16() ? 1 : 0;
   a.prof = &h->prof;
-  a.fuse_select = h->tune[CASR_OPT_FUSE_SELECT];
-  a.attn_kpb = h->tune[CASR_OPT_ATTN_KPB];
-  a.attn_direct = h->tune[CASR_OPT_ATTN_DIRECT];
-  a.proj_small = h->proj_small;
-  // the folded step: greedy (casr_greedy), or beam at R >= 1024 rows with 4 or 8 beam rows per
-  // attention block and every projection / LSTM weight < 16 (the fused GEMM's one-accumulator
-  // beam shapes, decoder.hip launch_fold_gemm).  casr_beam at k = 1 is a beam caller: it takes
-  // the beam guards, never the greedy clause (its fused GEMM would pick the one-accumulator shapes)
-  const bool fold_beam = !greedy && R >= 1024 && h->proj_small && h->dec_small &&
-                         attention_kpb(B, k, h->tune[CASR_OPT_ATTN_KPB]) >= 4;
-  // (a vocabulary beyond the 64 seven-tile partial blocks of the fused GEMM keeps the three-launch step)
-  const bool fold_vocab = (fold_vtiles(V) + FOLD_NT - 1) / FOLD_NT <= GP_NB;
-  // the folded greedy attention (attention_kernel<1, 1>) holds its cell-phase area on top of the
-  // three-launch step's LDS: at Tp where only the latter fits, greedy keeps the three-launch step
-  const bool fold_lds = !greedy || attention_smem_bytes(B, k, Tp, h->tune[CASR_OPT_ATTN_KPB], 1) <= 160 * 1024;
-  // the folded greedy attention reads the early-exit counters of steps 0..max_len-1 one per lane
-  const bool fold_len = !greedy || L <= 64;
-  // greedy folds in either arithmetic (round 4: the exact-f32 MFMAs on the f32 fused image); the
-  // beam fold's one-accumulator shapes and its s16 query need the s16 images
-  if (!a.s16 && greedy && h->W && h->tune[CASR_OPT_DEC_FOLD] && fold_vocab && fold_lds && fold_len) {
-    const int rc = ensure_fold32(h);
-    if (rc) return rc;
-  }
-  const bool fold_arith = a.s16 ? h->fold_ready : (greedy && h->fold32_ready);
-  a.fold = (greedy || fold_beam) && fold_vocab && fold_lds && fold_len && fold_arith && h->tune[CASR_OPT_DEC_FOLD] ? 1 : 0;
-  if (a.fold) {
-    HIP_OK(h, h->fgates.ensure((size_t)R * 4 * HD * sizeof(float)));
-    a.fb = FoldBufs{a.s16 ? h->wfold.as<float>() : h->wfold32.as<float>(), h->egates.as<float>(), h->wq16.as<float>(),
-                    h->fgates.as<float>()};
-  }
+  a.plan = plan;
+  a.fb = FoldBufs{static_cast<const float*>(buf[DP_WFOLD]), static_cast<const float*>(buf[DP_EMB_GATES]),
+                  static_cast<const float*>(buf[DP_WQ16]), static_cast<float*>(buf[DP_GATES])};
   return CASR_OK;
 }
 
@@ -1018,9 +1013,10 @@ int casr_greedy(casr_handle* h, int32_t* tokens, int32_t* out_len, uint8_t* fini
                 float* align, void* stream) {
   if (!h || !tokens || !out_len || !finished || !accum) return fail(h, CASR_ERR_ARG, "casr_greedy: NULL output");
   HIP_OK(h, hipSetDevice(h->device));
-  DecodeArgs a{};
-  int rc = prepare_decode(h, 1, a, true);
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_GREEDY, 1, align != nullptr, c);
   if (rc) return rc;
+  DecodeArgs& a = c.a;
   hipStream_t s = (hipStream_t)stream;
   if (!decode_graph_ok(h)) {
     dg_trace_init();  // CASR_DG_TRACE diagnostics only
@@ -1031,26 +1027,21 @@ int casr_greedy(casr_handle* h, int32_t* tokens, int32_t* out_len, uint8_t* fini
   // graph replay into handle-owned outputs, then copies to the caller's buffers
   const int B = h->B, L = h->cfg.max_len;
   const size_t nal = align ? (size_t)L * h->Tp * B : 0;
-  HIP_OK(h, h->gout.ensure(sizeof(int32_t) * ((size_t)B * L + B) + sizeof(float) * (B + nal) + B + 64));
-  int32_t* itok = h->gout.as<int32_t>();
-  int32_t* ilen = itok + (size_t)B * L;
-  float* iacc = reinterpret_cast<float*>(ilen + B);
-  float* ial = align ? iacc + B : nullptr;
-  uint8_t* ifin = reinterpret_cast<uint8_t*>(iacc + B + nal);
+  GreedyOut o{};
+  HIP_OK(h, h->gout.ensure(carve_greedy_out(nullptr, B, L, nal, o)));
+  carve_greedy_out(c.buf[DP_OUT] = h->gout.p, B, L, nal, o);
   a.prof = nullptr;
-  const std::vector<uint64_t> key = {2, (uint64_t)a.s16, (uint64_t)(h->d.kspart != nullptr), (uint64_t)h->d.asplit, (uint64_t)h->asbuf.p, (uint64_t)a.fuse_select, (uint64_t)a.attn_kpb, (uint64_t)a.attn_direct, (uint64_t)a.fold, (uint64_t)h->fgates.p, (uint64_t)a.fb.wfold, (uint64_t)B, (uint64_t)h->Tp, (uint64_t)h->W, (uint64_t)h->gout.p,
-                                     (uint64_t)(align != nullptr), (uint64_t)h->st.p, (uint64_t)h->logits.p,
-                                     (uint64_t)h->small.p, (uint64_t)h->enc_out, (uint64_t)h->keysT.p,
-                                     (uint64_t)h->hfin.p, (uint64_t)h->cst.p, (uint64_t)h->lens.p};
   dg_trace_init();  // CASR_DG_TRACE diagnostics only (outside any capture)
-  HIP_OK(h, run_graph(h, key, s, [&](hipStream_t cs) { return run_greedy(a, h->d, itok, ilen, ifin, iacc, ial, cs); }));
+  HIP_OK(h, run_graph(h, c.key(2, {}), s, [&](hipStream_t cs) {
+    return run_greedy(a, h->d, o.tokens, o.len, o.fin, o.accum, o.align, cs);
+  }));
   dg_trace_dump();  // CASR_DG_TRACE diagnostics only (no-op otherwise)
   CopyList cl;  // the graph's outputs to the caller's buffers in one launch
-  cl.add(tokens, itok, sizeof(int32_t) * B * L);
-  cl.add(out_len, ilen, sizeof(int32_t) * B);
-  cl.add(finished, ifin, B);
-  cl.add(accum, iacc, sizeof(float) * B);
-  if (align) cl.add(align, ial, sizeof(float) * nal);
+  cl.add(tokens, o.tokens, sizeof(int32_t) * B * L);
+  cl.add(out_len, o.len, sizeof(int32_t) * B);
+  cl.add(finished, o.fin, B);
+  cl.add(accum, o.accum, sizeof(float) * B);
+  if (align) cl.add(align, o.align, sizeof(float) * nal);
   HIP_OK(h, copy_multi(cl, s));
   return CASR_OK;
 }
@@ -1060,9 +1051,10 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
   if (!h || !best_tokens || !best_len || !best_score || !steps)
     return fail(h, CASR_ERR_ARG, "casr_beam: NULL output");
   HIP_OK(h, hipSetDevice(h->device));
-  DecodeArgs a{};
-  int rc = prepare_decode(h, k, a, false);
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_BEAM, k, false, c);
   if (rc) return rc;
+  DecodeArgs& a = c.a;
   hipStream_t s = (hipStream_t)stream;
   h->dec_k = k;
   h->beam_done = true;
@@ -1073,30 +1065,20 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
     return CASR_OK;
   }
   const int B = h->B, L = h->cfg.max_len;
-  HIP_OK(h, h->gout.ensure(sizeof(int32_t) * ((size_t)B * L + B + 1) + sizeof(float) * B + 64));
-  int32_t* itok = h->gout.as<int32_t>();
-  int32_t* ilen = itok + (size_t)B * L;
-  int32_t* istp = ilen + B;
-  float* isc = reinterpret_cast<float*>(istp + 1);
+  BeamOut o{};
+  HIP_OK(h, h->gout.ensure(carve_beam_out(nullptr, B, L, o)));
+  carve_beam_out(c.buf[DP_OUT] = h->gout.p, B, L, o);
   a.prof = nullptr;
-  uint32_t lmw, lw;
-  std::memcpy(&lmw, &lm_weight, 4);
-  std::memcpy(&lw, &length_weight, 4);
-  const std::vector<uint64_t> key = {3, (uint64_t)a.s16, (uint64_t)a.attn_kpb, (uint64_t)a.attn_direct, (uint64_t)a.fold, (uint64_t)h->fgates.p, (uint64_t)B, (uint64_t)h->Tp, (uint64_t)k, lmw, lw, (uint64_t)h->W,
-                                     (uint64_t)h->gout.p, (uint64_t)h->st.p, (uint64_t)h->logits.p,
-                                     (uint64_t)h->small.p, (uint64_t)h->bp.p, (uint64_t)h->tk.p, (uint64_t)h->rec.p,
-                                     (uint64_t)h->enc_out, (uint64_t)h->keysT.p, (uint64_t)h->hfin.p,
-                                     (uint64_t)h->cst.p, (uint64_t)h->lens.p};
   dg_trace_init();  // CASR_DG_TRACE diagnostics only (outside any capture)
-  HIP_OK(h, run_graph(h, key, s, [&](hipStream_t cs) {
-    return run_beam(a, h->d, lm_weight, length_weight, itok, ilen, isc, istp, cs);
+  HIP_OK(h, run_graph(h, c.key(3, {lm_weight, length_weight}), s, [&](hipStream_t cs) {
+    return run_beam(a, h->d, lm_weight, length_weight, o.tokens, o.len, o.score, o.steps, cs);
   }));
   dg_trace_dump();
   CopyList cl;  // the graph's outputs to the caller's buffers in one launch
-  cl.add(best_tokens, itok, sizeof(int32_t) * B * L);
-  cl.add(best_len, ilen, sizeof(int32_t) * B);
-  cl.add(best_score, isc, sizeof(float) * B);
-  cl.add(steps, istp, sizeof(int32_t));
+  cl.add(best_tokens, o.tokens, sizeof(int32_t) * B * L);
+  cl.add(best_len, o.len, sizeof(int32_t) * B);
+  cl.add(best_score, o.score, sizeof(float) * B);
+  cl.add(steps, o.steps, sizeof(int32_t));
   HIP_OK(h, copy_multi(cl, s));
   return CASR_OK;
 }
@@ -1106,10 +1088,10 @@ int casr_beam_records(casr_handle* h, int32_t* rec_tokens, float* rec_score, uin
   if (!h || !h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_records before casr_beam");
   if (!rec_tokens || !rec_score || !rec_valid) return fail(h, CASR_ERR_ARG, "casr_beam_records: NULL output");
   HIP_OK(h, hipSetDevice(h->device));
-  DecodeArgs a{};
-  int rc = prepare_decode(h, h->dec_k, a, false);
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
   if (rc) return rc;
-  HIP_OK(h, run_beam_records(a, h->d, rec_tokens, rec_score, rec_valid, (hipStream_t)stream));
+  HIP_OK(h, run_beam_records(c.a, h->d, rec_tokens, rec_score, rec_valid, (hipStream_t)stream));
   return CASR_OK;
 }
 
@@ -1122,14 +1104,12 @@ int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, i
   if (!h->encoded) return fail(h, CASR_ERR_STATE, "casr_score before casr_encode");
   if (L < 1 || L > h->cfg.max_len) return fail(h, CASR_ERR_ARG, "casr_score: L = %d not in [1, %d]", L, h->cfg.max_len);
   HIP_OK(h, hipSetDevice(h->device));
-  DecodeArgs a{};
-  int rc = prepare_decode(h, 1, a, true);
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_SCORE, 1, false, c);
   if (rc) return rc;
-  if (score_col_blocks(a) > GP_NB)
-    return fail(h, CASR_ERR_UNSUPPORTED, "casr_score: %d projection column blocks > %d row partials", score_col_blocks(a), GP_NB);
   HIP_OK(h, h->scorebuf.ensure(score_workspace_bytes(h->B, L)));
   const ScoreBufs sb = score_carve(h->scorebuf.p, h->B, L);
-  HIP_OK(h, run_score(a, h->d, sb, targets, tgt_len, L, token_logp, total_logp, best_token, best_logp, mean_logp, align,
+  HIP_OK(h, run_score(c.a, h->d, sb, targets, tgt_len, L, token_logp, total_logp, best_token, best_logp, mean_logp, align,
                       (hipStream_t)stream));
   return CASR_OK;
 }

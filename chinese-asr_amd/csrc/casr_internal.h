@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "casr.h"
+#include "decode_plan.h"
 
 // the s16 arithmetic of this build (casr_common.h CASR_S16_ONE: the s16x1 build)
 #ifndef CASR_S16_ONE
@@ -16,20 +17,7 @@ constexpr int CASR_PREC_S16 = CASR_S16_ONE ? CASR_PREC_S16X1 : CASR_PREC_S16X3;
 
 namespace casr {
 
-// Dimensions of the deployed configuration (gpd.py), fixed at compile time so every
-// tile loop unrolls.  casr_create rejects any other configuration (CASR_ERR_UNSUPPORTED).
-constexpr int F = 80;     // n_mels
-constexpr int D = 720;    // encoder input (3 ch x 3 frames x 80)
-constexpr int H = 256;    // encoder hidden per direction
-constexpr int C = 512;    // encoder output / context size (2H)
-constexpr int HD = 512;   // decoder hidden
-constexpr int E = 256;    // embedding
-constexpr int A = 128;    // attention size
-constexpr int KDEC = E + C + HD;  // 1280: decoder LSTM contraction [emb | ctx | h]
-constexpr int KPROJ = C + HD;     // 1024: projection contraction [ctx | h]
-constexpr int ST16 = C + HD + HD;  // offset of the s16 split words [ctx16 | h16] in a state row
-constexpr int ST = ST16 + C + HD;  // 2560: per-row decoder state [ctx | h | c | ctx16 | h16]
-constexpr int KMAX_BEAM = 16;
+// (the dimensions of the deployed configuration: casr_dims.h)
 
 // Device guard bits: a data-dependent index (token id, predecessor row, back-pointer) out of
 // range is clamped to a valid one and reported here instead of faulting the GPU.
@@ -73,13 +61,6 @@ struct Layout {
 };
 
 Layout make_layout(const casr_config& cfg);
-
-// Tuning options of a handle (include/casr.h CASR_OPT_*): speed only, every value gives the same
-// bits (CASR_OPT_ATTN_DIRECT: a numerics variant within the attention tolerance).
-struct Tuning {
-  int v[CASR_OPT_COUNT] = {1, 0, 1, -1, 2, 2, 2, 2, 0, 0, 1, 0, 0, 1, 1, 1, 1, 0, 0};
-  int operator[](int i) const { return v[i]; }
-};
 
 // Packed row index of (gate g, unit u) for a gate-interleaved LSTM matrix with hidden
 // size n_hidden: blocks of 16 units, each block = 4 gates x 16 units.
@@ -288,15 +269,7 @@ hipError_t launch_keys(const float* enc, int B, int Tp, const float* wencT, cons
                        float* keysT, hipStream_t s);
 
 // decoder.hip
-// projection column blocks (5 x 16 columns each) whose per-row partials the selects combine: V <= 5120
-constexpr int GP_NB = 64;
-struct GreedyPart {
-  float* mx;    // [R][GP_NB] block maximum of the row's logits
-  float* se;    // [R][GP_NB] sum exp(x - block maximum)
-  int32_t* ix;  // [R][GP_NB] first column of the block maximum
-  float* tmx;   // [R][GP_NT] maximum of each 16-column tile (beam at temperature 1), or nullptr
-};
-constexpr int GP_NT = 320;  // 16-column tiles per row (V <= 5120)
+// (GreedyPart, GP_NB, GP_NT and the fused image's tiling, FOLD_*: decode_plan.h)
 
 // a beam select's operands and outputs (beam_select.h; beam_select_kernel's argument, and the
 // folded beam attention's prologue select, AttnCell::bs)
@@ -365,13 +338,6 @@ __device__ __forceinline__ void greedy_book(const GreedySel& gs, int r, int t, f
 //      fragment image: the vocabulary tiles (greedy partials) and the LSTM gate tiles of the next
 //      step (K = 1024: the ctx | h part of the LSTM contraction, decoder.py:104-114), one GEMM
 //      over the same A rows.
-constexpr int FOLD_GT = 4 * HD / 16;  // LSTM gate tiles (16 gate rows each) in the fused image
-constexpr int FOLD_NT = 7;            // 16-column tiles per fused GEMM block (112 columns)
-inline int fold_vtiles(int V) { return (V + 15) / 16; }
-// (round 4) the gate tiles of the fused image start at the vocabulary tiles rounded up to a whole
-// 7-tile wave column (zero tiles between): no wave column holds both vocabulary and gate tiles, so
-// the fused GEMM's epilogue has no mixed column, the one that ended last
-inline int fold_gtile0(int V) { return (fold_vtiles(V) + FOLD_NT - 1) / FOLD_NT * FOLD_NT; }
 // bytes of one fused image (s16 or f32: the same tiling)
 inline size_t fold_image_bytes(int V) { return (size_t)(fold_gtile0(V) + FOLD_GT) * (KPROJ / 64) * FRAG * sizeof(float); }
 constexpr size_t FOLD_WQ16_FLOATS = (size_t)A * HD;  // the W_hidden fragment image (beam query)
@@ -388,38 +354,7 @@ struct FoldBufs {
 hipError_t build_fold(const float* W, const Layout& L, int V, float* wfold, float* emb_gates, float* wq16,
                       float* wfold32, hipStream_t s);
 
-// the greedy folded GEMM's k split at R <= 32 (decoder.hip dgemm_kernel KS): DG_KS blocks per
-// output block, at most DG_KS_GROUPS output blocks of 2 epilogue waves
-constexpr int DG_KS = 4, DG_KS_GROUPS = 64, DG_KS_COUNTERS = 2 * DG_KS_GROUPS;
-constexpr size_t DG_KS_PART_BYTES = (size_t)DG_KS_COUNTERS * DG_KS * FOLD_NT * 64 * 16;  // f32x4 per lane
-
-struct DecodeBufs {
-  float* st[2];          // [R][ST]
-  float* logits;         // [R][V]
-  GreedyPart part;       // per-block row partials of the projection (after the logits)
-  float* qpart;          // [dec_q_slots(R)][R][A] attention query partials, one per LSTMCell column block
-  int32_t* tok[2];       // [R]
-  int32_t* src[2];       // [R]
-  float* score[2];       // [R]
-  int32_t* newdone;      // [max_len] rows/utterances newly finished at each step
-  int32_t* err;          // [1] CASR_DEV_* guard bits set by kernels (casr_debug_flags)
-  // greedy
-  uint8_t* fin;          // [R]
-  // beam
-  uint8_t* topfin;       // [B]
-  int32_t* bp;           // [L][R]
-  int32_t* tk;           // [L][R]
-  float* rec_score;      // [B][L][k]
-  int32_t* rec_src;      // [B][L][k]
-  uint8_t* rec_valid;    // [B][L][k]
-  // greedy at R <= 32 with CASR_OPT_DEC_KSPLIT: the k-range sums and arrival counters (else nullptr)
-  float* kspart;         // [groups][2 waves][DG_KS][FOLD_NT tiles][64 lanes] x 4 floats
-  int32_t* kscnt;
-  // greedy at R <= 64 with CASR_OPT_ATTN_SPLIT: the split attention's partials and counters (else nullptr)
-  float* aspart;         // [R][AT_SPLIT_MAX][C + 4]
-  int32_t* ascnt;        // [R]
-  int asplit;            // splits asked for (8 at R <= 32, 4 at R <= 64)
-};
+// (DecodeBufs and the workspaces' layouts: decode_plan.h)
 
 struct DecodeArgs {
   const float* W;        // packed blob base
@@ -431,24 +366,12 @@ struct DecodeArgs {
   const int32_t* lens;   // [B]
   int B, Tp, k, V, max_len, sos, eos;
   float temperature;
-  int s16;               // decoder GEMMs on the s16x3 images (casr_set_precision)
   Profiler* prof;        // may be null
-  int greedy_run;        // set by run_greedy: the projection writes per-block argmax partials
-  int fuse_select;       // CASR_OPT_FUSE_SELECT
-  int attn_kpb;          // CASR_OPT_ATTN_KPB (0 auto)
-  int attn_direct;       // CASR_OPT_ATTN_DIRECT
-  int proj_small;        // every |W_p| < 16 (blob info word 4): the one-accumulator s16x3 projection
-  int fold;              // CASR_OPT_DEC_FOLD in effect (greedy, s16x3, tables built)
-  FoldBufs fb;           // fold tables and the gates buffer (fold only)
+  DecodePlan plan;       // every path decision of this call (decode_plan.h plan_decode)
+  FoldBufs fb;           // fold tables and the gates buffer (plan.fold only)
 };
 
 // attention.hip: one decode step's additive attention for all R rows (writes ctx into st)
-// decode rows at which the LSTMCell (128 x 128) and projection (256 x 160) blocks of decoder.hip
-// fill the CUs in one round; below it the narrower blocks do
-inline bool dec_wide(int R) { return R >= 2048; }
-// attention query partials per decoder row: one per LSTMCell column block (decoder.hip
-// launch_dec_lstm), 16 units each, 32 units at dec_wide(R)
-inline int dec_q_slots(int R) { return dec_wide(R) ? HD / 32 : HD / 16; }
 hipError_t launch_attention_step(const DecodeArgs& a, float* st, const float* qpart, float* align,
                                  int32_t* newdone, int l, int total, hipStream_t s);
 // the folded step's attention (KA above): st_old supplies c, st receives h, c and ctx.  Greedy
@@ -473,13 +396,10 @@ struct AttnCell {
   float* spart;
   int32_t* scnt;
 };
-constexpr int AT_SPLIT_MAX = 8;
 hipError_t launch_attention_cell_step(const DecodeArgs& a, float* st, const AttnCell& cell, float* align,
                                       int32_t* newdone, int l, int total, hipStream_t s);
-// fixed LDS of the attention launch; cell = 1: the folded greedy step's attention_kernel<1, 1>
-// (its cell-phase area on top; CELL 2 keeps its cell data in the score scratch)
-size_t attention_smem_bytes(int B, int k, int Tp, int opt, int cell = 0);
-int attention_kpb(int B, int k, int opt);  // beam rows per attention block
+// the static LDS of the attention kernel forms, read once from the code object (plan_decode's input)
+AttnStaticLds attention_static_lds();
 void attn_trace_bind(uint32_t* buf);  // CASR_DG_TRACE diagnostics (attention.hip)
 
 void dg_trace_init();  // decoder.hip, CASR_DG_TRACE diagnostics
@@ -507,9 +427,7 @@ struct ScoreBufs {
 };
 size_t score_workspace_bytes(int B, int L);
 ScoreBufs score_carve(void* base, int B, int L);
-// projection column blocks with row partials (the three-launch step's, whatever a.fold says)
-int score_col_blocks(const DecodeArgs& a);
-// decoder.hip: the step loop (a.k == 1, a.fold == 0, a.greedy_run == 1) and the batched projection
+// decoder.hip: the step loop (a.plan: the PLAN_SCORE caller's) and the batched projection
 hipError_t score_steps(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, int L, float* align, hipStream_t s);
 hipError_t score_project(const DecodeArgs& a, const DecodeBufs& d, const ScoreBufs& sb, int L, hipStream_t s);
 // score.hip

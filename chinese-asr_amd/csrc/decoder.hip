@@ -1613,8 +1613,9 @@ static void launch_fold_gemm(int R, bool beam, int NB, int ntiles, const float* 
                              int s16, hipStream_t s, f32x4* kspart = nullptr, int* kscnt = nullptr) {
   const int nkt = KPROJ / DG_BK;
   if (!beam) {  // (greedy: s16x3, or the exact-f32 MFMAs on the f32 fused image)
-    // R <= 32 with a k-split buffer (CASR_OPT_DEC_KSPLIT): DG_KS blocks per 32 x 112 output block
-    if (R <= 32 && kspart && NB <= DG_KS_GROUPS && nkt % DG_KS == 0)
+    // the k split (DecodePlan::ksplit, R <= 32, NB <= DG_KS_GROUPS): DG_KS blocks per 32 x 112 output block
+    static_assert(DG_BK == 64, "decode_plan.h checks KPROJ / 64 % DG_KS");
+    if (kspart)
       launch_dg<2, FOLD_NT, 3, 1, 1, false, 64, false, 3, DG_KS>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s, kspart, kscnt);
     else if (R <= 32) launch_dg<2, FOLD_NT, 3>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
     else launch_dg<4, FOLD_NT, 3>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
@@ -1628,20 +1629,13 @@ static void launch_fold_gemm(int R, bool beam, int NB, int ntiles, const float* 
 }
 
 // ------------------------------------------------------------------ host drivers
-// per-block row partials from the projection epilogue: the vocabulary must fit the 64 partial
-// blocks; beam search uses them at temperature 1 only (they are of x, not x / T)
-static int fold_col_blocks(int V) { return (fold_vtiles(V) + FOLD_NT - 1) / FOLD_NT; }
-static int proj_col_blocks(const DecodeArgs& a) {
-  // the folded step's partials: one per 7-tile wave column in every shape
-  if (a.fold) return fold_col_blocks(a.V);
-  const int nt = a.L.VP / 16, R = a.B * a.k;
-  // the column block of a wave (ProjEpi's partial index): 5 tiles in every launch_proj shape (the
-  // beam blocks' two wave columns), so the select's partial sums do not depend on R
-  (void)R;
-  return (nt + 4) / 5;
-}
-static bool row_partials(const DecodeArgs& a) {
-  return proj_col_blocks(a) <= GP_NB && (a.greedy_run || a.temperature == 1.0f);
+// Which path a decode takes is decided once per API call by plan_decode (decode_plan.h): the
+// drivers below read a.plan.
+// the projection epilogue's row partials (and, beam, tile maxima) where the plan has them written
+static GreedyPart plan_partials(const DecodeArgs& a, const DecodeBufs& d) {
+  GreedyPart gp = a.plan.partials ? d.part : GreedyPart{nullptr, nullptr, nullptr, nullptr};
+  if (!a.plan.tile_max) gp.tmx = nullptr;
+  return gp;
 }
 
 // proj = false: LSTMCell and attention only (the folded step's step 0: its GEMM follows)
@@ -1652,14 +1646,14 @@ static hipError_t decode_step(const DecodeArgs& a, DecodeBufs& d, int l, int tot
   float* st_new = d.st[(l + 1) & 1];
   {
     ProfScope ps(a.prof, CASR_K_DEC_LSTM, s);
-    DecLstmA asrc{a.W + (a.s16 ? a.L.emb16 : a.L.emb), st_old, d.tok[l & 1], d.src[l & 1], d.err, R, a.V, a.s16};
+    DecLstmA asrc{a.W + (a.plan.s16 ? a.L.emb16 : a.L.emb), st_old, d.tok[l & 1], d.src[l & 1], d.err, R, a.V, a.plan.s16};
     if (gsel) {
       asrc.sel = 1;
       asrc.gs = *gsel;
     }
     DecLstmEpi epi{a.W + a.L.dec_b, st_old, st_new, asrc, d.newdone, a.W + a.L.w_hidden, d.qpart, R, l, total};
-    epi.hw = a.s16;
-    launch_dec_lstm(R, a.W + (a.s16 ? a.L.dec_w16 : a.L.dec_w), asrc, epi, a.s16, s);
+    epi.hw = a.plan.s16;
+    launch_dec_lstm(R, a.W + (a.plan.s16 ? a.L.dec_w16 : a.L.dec_w), asrc, epi, a.plan.s16, s);
   }
   hipError_t e;
   {
@@ -1669,13 +1663,11 @@ static hipError_t decode_step(const DecodeArgs& a, DecodeBufs& d, int l, int tot
   if (e != hipSuccess) return e;
   if (proj) {
     ProfScope ps(a.prof, CASR_K_PROJ, s);
-    ProjA asrc{st_new, R, a.s16};
+    ProjA asrc{st_new, R, a.plan.s16};
     // greedy: per-block partials instead of logits; beam at temperature 1: logits and partials
-    const bool parts = row_partials(a);
-    GreedyPart gp = parts ? d.part : GreedyPart{nullptr, nullptr, nullptr, nullptr};
-    if (a.greedy_run || a.V > 16 * GP_NT) gp.tmx = nullptr;  // tile maxima: beam only
-    ProjEpi epi{a.W + a.L.proj_b, a.greedy_run && parts ? nullptr : d.logits, d.newdone, R, a.V, l, total, d.err, gp};
-    launch_proj(R, a.L.VP / 16, a.W + (a.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.s16, a.proj_small, s);
+    ProjEpi epi{a.W + a.L.proj_b, a.plan.store_logits ? d.logits : nullptr, d.newdone, R, a.V, l, total, d.err,
+                plan_partials(a, d)};
+    launch_proj(R, a.L.VP / 16, a.W + (a.plan.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.plan.s16, a.plan.proj_small, s);
   }
   return hipGetLastError();
 }
@@ -1732,18 +1724,18 @@ void dg_trace_dump() {
 // beam: logits, and at temperature 1 the row partials and tile maxima, as decode_step's projection
 static void fold_gemm_step(const DecodeArgs& a, DecodeBufs& d, int l, int total, hipStream_t s) {
   const int R = a.B * a.k;
-  const bool beam = !a.greedy_run;
+  const bool beam = a.plan.caller == PLAN_BEAM;
   const int VT = fold_vtiles(a.V), VG = fold_gtile0(a.V), NT = beam ? FOLD_NT_BEAM : FOLD_NT;
   const bool gates = l + 1 < a.max_len;
   const int ntiles = VG + FOLD_GT;
   const int NB = ((gates ? ntiles : VT) + NT - 1) / NT;
   ProfScope ps(a.prof, CASR_K_PROJ, s);
-  ProjA asrc{d.st[(l + 1) & 1], R, a.s16};
-  GreedyPart gp = row_partials(a) ? d.part : GreedyPart{nullptr, nullptr, nullptr, nullptr};
-  if (!beam || a.V > 16 * GP_NT) gp.tmx = nullptr;  // tile maxima: beam only
-  FoldEpi epi{a.W + a.L.proj_b, d.newdone, R, a.V, VT, l, total, d.err, gp, a.fb.gates, beam ? d.logits : nullptr, VG};
+  ProjA asrc{d.st[(l + 1) & 1], R, a.plan.s16};
+  FoldEpi epi{a.W + a.L.proj_b, d.newdone, R, a.V, VT, l, total, d.err, plan_partials(a, d), a.fb.gates,
+              a.plan.store_logits ? d.logits : nullptr, VG};
+  const bool ks = gates ? a.plan.ksplit : a.plan.ksplit_last;
   dg_trace_step_gate(l, true, s);
-  launch_fold_gemm(R, beam, NB, ntiles, a.fb.wfold, asrc, epi, a.s16, s, beam ? nullptr : reinterpret_cast<f32x4*>(d.kspart), d.kscnt);
+  launch_fold_gemm(R, beam, NB, ntiles, a.fb.wfold, asrc, epi, a.plan.s16, s, ks ? reinterpret_cast<f32x4*>(d.kspart) : nullptr, d.kscnt);
   dg_trace_step_gate(l, false, s);
 }
 
@@ -1766,10 +1758,9 @@ static hipError_t fold_attention_step(const DecodeArgs& a, DecodeBufs& d, int l,
   if (bs) {
     cell.bsel = 1;
     cell.bs = *bs;
-  } else if (d.aspart && !align) {  // greedy, CASR_OPT_ATTN_SPLIT: d.asplit ranges of a multiple of 4 steps
-    const int tq = (a.Tp + 3) & ~3;  // (attention.hip's attn_tq)
-    cell.tc = ((tq + d.asplit - 1) / d.asplit + 3) & ~3;
-    cell.split = (tq + cell.tc - 1) / cell.tc;  // (< 2 at short inputs: the unsplit form)
+  } else if (a.plan.split) {  // greedy, CASR_OPT_ATTN_SPLIT: ranges of a multiple of 4 steps
+    cell.tc = a.plan.tc;
+    cell.split = a.plan.split;
     cell.spart = d.aspart;
     cell.scnt = d.ascnt;
   }
@@ -1780,10 +1771,8 @@ static hipError_t fold_attention_step(const DecodeArgs& a, DecodeBufs& d, int l,
 // partials), then the fused GEMM at every step and the cell inside the attention from step 1 on
 static hipError_t run_greedy_fold(const DecodeArgs& a, DecodeBufs& d, int32_t* tokens, int32_t* out_len,
                                   uint8_t* finished, float* accum, float* align, hipStream_t s) {
-  const int R = a.B;
-  const int nbp = fold_col_blocks(a.V);
-  if (nbp > GP_NB) return hipErrorInvalidValue;
-  const bool fuse = a.fuse_select != 0;
+  const int R = a.B, nbp = a.plan.nbp;
+  const bool fuse = a.plan.fuse_select;
   hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, 1, a.sos, d.tok[0],
                      d.src[0], d.score[0], nullptr);
   for (int l = 0; l < a.max_len; ++l) {
@@ -1802,10 +1791,8 @@ static hipError_t run_greedy_fold(const DecodeArgs& a, DecodeBufs& d, int32_t* t
   return hipGetLastError();
 }
 
-hipError_t run_greedy(const DecodeArgs& a_in, DecodeBufs& d, int32_t* tokens, int32_t* out_len,
+hipError_t run_greedy(const DecodeArgs& a, DecodeBufs& d, int32_t* tokens, int32_t* out_len,
                       uint8_t* finished, float* accum, float* align, hipStream_t s) {
-  DecodeArgs a = a_in;
-  a.greedy_run = 1;
   const int R = a.B;
   // fill kernels, not hipMemsetAsync: this sequence is captured into a replayed graph
   FillList fl;
@@ -1818,22 +1805,22 @@ hipError_t run_greedy(const DecodeArgs& a_in, DecodeBufs& d, int32_t* tokens, in
   if (d.ascnt) fl.add32(d.ascnt, 0, R);
   hipError_t e0 = fill_multi(fl, s);
   if (e0 != hipSuccess) return e0;
-  if (a.fold) return run_greedy_fold(a, d, tokens, out_len, finished, accum, align, s);
+  if (a.plan.fold) return run_greedy_fold(a, d, tokens, out_len, finished, accum, align, s);
   // the select of step l runs inside step l+1's LSTMCell (GreedySel) when the projection writes
   // per-block partials; the last step's select is a launch of its own.  CASR_OPT_FUSE_SELECT = 0
   // keeps every select a launch (the same bits either way)
-  const bool fuse = a.fuse_select && row_partials(a);
+  const bool fuse = a.plan.fuse_select;
   hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, 1,
                      a.sos, d.tok[0], d.src[0], d.score[0], fuse ? d.src[1] : nullptr);
   for (int l = 0; l < a.max_len; ++l) {
-    GreedySel gs{d.part, proj_col_blocks(a), l - 1, a.max_len, a.eos, finished, out_len, accum, tokens, d.newdone};
+    GreedySel gs{d.part, a.plan.nbp, l - 1, a.max_len, a.eos, finished, out_len, accum, tokens, d.newdone};
     hipError_t e = decode_step(a, d, l, R, align ? align + (size_t)l * a.Tp * R : nullptr, s,
                                fuse && l > 0 ? &gs : nullptr);
     if (e != hipSuccess) return e;
     if (fuse && l + 1 < a.max_len) continue;
     ProfScope ps(a.prof, CASR_K_SELECT, s);
-    if (row_partials(a)) {
-      hipLaunchKernelGGL(greedy_select_part_kernel, dim3((R + 3) / 4), dim3(256), 0, s, d.part, proj_col_blocks(a), a.V,
+    if (a.plan.partials) {
+      hipLaunchKernelGGL(greedy_select_part_kernel, dim3((R + 3) / 4), dim3(256), 0, s, d.part, a.plan.nbp, a.V,
                          R, l, a.max_len, a.eos, d.tok[(l + 1) & 1], d.src[(l + 1) & 1], finished, out_len, accum,
                          tokens, d.newdone, d.err);
     } else {
@@ -1846,15 +1833,13 @@ hipError_t run_greedy(const DecodeArgs& a_in, DecodeBufs& d, int32_t* tokens, in
 }
 
 // ------------------------------------------------------------------ teacher-forced scoring (casr_score)
-int score_col_blocks(const DecodeArgs& a) { return (a.L.VP / 16 + 4) / 5; }
-
 // L steps of the three-launch step without its projection: the LSTMCell GEMM and the attention,
 // unchanged.  Step l reads slab l of the history and writes slab l + 1 (every word of a state row
 // is written by the two launches), feeds row l of sb.feed with the identity predecessor, and is
 // never skipped (the early-exit counters stay 0).  sb.feed holds valid ids only (score.hip).
 hipError_t score_steps(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, int L, float* align, hipStream_t s) {
   const int R = a.B;
-  if (a.k != 1 || a.fold || !a.greedy_run) return hipErrorInvalidValue;
+  if (a.plan.caller != PLAN_SCORE) return hipErrorInvalidValue;
   FillList fl;
   fl.add32(d.newdone, 0, a.max_len);
   hipError_t e = fill_multi(fl, s);
@@ -1877,13 +1862,12 @@ hipError_t score_steps(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, 
 // of the history, so the step projection's A source (ProjA) serves unchanged
 hipError_t score_project(const DecodeArgs& a, const DecodeBufs& d, const ScoreBufs& sb, int L, hipStream_t s) {
   const int R = L * a.B;
-  if (score_col_blocks(a) > GP_NB) return hipErrorInvalidValue;
   ProfScope ps(a.prof, CASR_K_PROJ, s);
-  ProjA asrc{sb.hist + (size_t)a.B * ST, R, a.s16};
+  ProjA asrc{sb.hist + (size_t)a.B * ST, R, a.plan.s16};
   GreedyPart gp = sb.part;
   gp.tmx = nullptr;
   ScoreEpi epi{a.W + a.L.proj_b, R, a.V, d.err, gp, sb.xsum, sb.tgt, sb.tl};
-  launch_proj(R, a.L.VP / 16, a.W + (a.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.s16, a.proj_small, s);
+  launch_proj(R, a.L.VP / 16, a.W + (a.plan.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.plan.s16, a.plan.proj_small, s);
   return hipGetLastError();
 }
 
@@ -1893,7 +1877,7 @@ static BeamSelArgs beam_sel_args(const DecodeArgs& a, const DecodeBufs& d, int l
   return BeamSelArgs{d.logits, a.V, a.B, a.k, l, a.max_len, a.eos, a.temperature, d.score[l & 1],
                      d.score[(l + 1) & 1], d.tok[(l + 1) & 1], d.src[(l + 1) & 1], d.topfin, d.bp, d.tk,
                      d.rec_score, d.rec_src, d.rec_valid, d.newdone, d.err, d.part,
-                     row_partials(a) ? proj_col_blocks(a) : 0};
+                     a.plan.nbp};
 }
 
 template <int K2>
@@ -1917,13 +1901,12 @@ hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float l
   // of step l - 1 runs in step l's attention prologue (CASR_OPT_FUSE_SELECT; the last step's select
   // is a launch of its own)
   // (k = 8 at 4 rows per attention block: both blocks of an utterance run the select, CELL 4)
-  const int fkpb = attention_kpb(a.B, a.k, a.attn_kpb);
-  const bool fsel = a.fold && a.fuse_select && (a.k == 4 || a.k == 8) && (fkpb == a.k || (a.k == 8 && fkpb == 4));
+  const bool fsel = a.plan.fuse_select;
   for (int l = 0; l < a.max_len; ++l) {
     // the folded step (CASR_OPT_DEC_FOLD): step 0's LSTMCell + attention, then per step the
     // attention with the cell prologue (l >= 1) and the fused GEMM
     hipError_t e;
-    if (!a.fold) {
+    if (!a.plan.fold) {
       e = decode_step(a, d, l, a.B, nullptr, s);
     } else if (l == 0) {
       e = decode_step(a, d, 0, a.B, nullptr, s, nullptr, false);
@@ -1932,17 +1915,18 @@ hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float l
       e = fold_attention_step(a, d, l, a.B, nullptr, false, GreedySel{}, s, fsel ? &bs : nullptr);
     }
     if (e != hipSuccess) return e;
-    if (a.fold) fold_gemm_step(a, d, l, a.B, s);
+    if (a.plan.fold) fold_gemm_step(a, d, l, a.B, s);
     if (fsel && l + 1 < a.max_len) continue;
     ProfScope ps(a.prof, CASR_K_SELECT, s);
-    if (a.k <= 2) launch_beam_select<4>(a, d, l, s);
-    else if (a.k <= 4) launch_beam_select<8>(a, d, l, s);
-    else if (a.k <= 8) launch_beam_select<16>(a, d, l, s);
-    else launch_beam_select<32>(a, d, l, s);
+    switch (a.plan.K2) {
+      case 4: launch_beam_select<4>(a, d, l, s); break;
+      case 8: launch_beam_select<8>(a, d, l, s); break;
+      case 16: launch_beam_select<16>(a, d, l, s); break;
+      default: launch_beam_select<32>(a, d, l, s);
+    }
   }
-  const size_t fin_lds = (size_t)((a.max_len * a.k + 7) & ~7) * (3 * sizeof(int32_t) + 1) + 16;
-  if (fin_lds <= 64 * 1024)
-    hipLaunchKernelGGL(beam_finalize_wave_kernel, dim3(a.B), dim3(64), fin_lds, s, a.B, a.k, a.max_len,
+  if (a.plan.fin_lds)
+    hipLaunchKernelGGL(beam_finalize_wave_kernel, dim3(a.B), dim3(64), a.plan.fin_lds, s, a.B, a.k, a.max_len,
                        lm_weight, length_weight, d.score[0], d.score[1], d.bp, d.tk, d.rec_score, d.rec_src,
                        d.rec_valid, d.newdone, best_tokens, best_len, best_score, steps, d.err);
   else  // (a max_len x k past the LDS: the thread-per-utterance form)

@@ -394,7 +394,7 @@ hipError_t launch_keys(const float* enc, int B, int Tp, const float* wencT, cons
                        float* keysT, hipStream_t s) {
   const int M = B * Tp;
   if (M <= 0) return hipErrorInvalidValue;
-  KeysEpi epi{keysT, b_attn, Tp, (Tp + 3) & ~3, B};
+  KeysEpi epi{keysT, b_attn, Tp, attn_tq(Tp), B};
   const TileOrder order = tile_order(A / GB_N, (M + GB_M - 1) / GB_M, C);
   hipLaunchKernelGGL(gemm_nt_kernel<KeysEpi>, dim3(order.blocks()), dim3(256), 0, s, enc, C, wencT,
                      C, M, A, C, order, epi);
@@ -562,13 +562,13 @@ hipError_t launch_keys_s16(const float* enc16, int B, int Tp, const float* wenc1
       (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
       return v > 0 ? v : 256;
     }();
-    const int Tq = (Tp + 3) & ~3, NI = B * ((Tp + KR_G - 1) / KR_G);
+    const int Tq = attn_tq(Tp), NI = B * ((Tp + KR_G - 1) / KR_G);
     if ((size_t)2 * B * A * Tq * 4 >= 0xFFFFFFF0u) return hipErrorInvalidValue;  // 32-bit buffer offsets
     hipLaunchKernelGGL(keys16_kernel, dim3(std::min(NI, ncu)), dim3(512), 0, s, enc16, wenc16, b_attn, keysT, B, Tp,
                        Tq, km);
     return hipGetLastError();
   }
-  KeysEpi epi{keysT, b_attn, Tp, (Tp + 3) & ~3, B};
+  KeysEpi epi{keysT, b_attn, Tp, attn_tq(Tp), B};
   const TileOrder order = tile_order(A / GB_N, (M + GB_M - 1) / GB_M, C);
   hipLaunchKernelGGL((gemm_nt_kernel<KeysEpi, true>), dim3(order.blocks()), dim3(256), 0, s, enc16, C, wenc16,
                      C, M, A, C, order, epi);

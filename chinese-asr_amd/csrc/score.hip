@@ -126,13 +126,9 @@ __global__ void score_total_kernel(const float* __restrict__ token_logp, const i
   total_logp[b] = acc;
 }
 
-hipError_t run_score(const DecodeArgs& a_in, DecodeBufs& d, const ScoreBufs& sb, const int32_t* targets,
+hipError_t run_score(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, const int32_t* targets,
                      const int32_t* tgt_len, int L, float* token_logp, float* total_logp, int32_t* best_token,
                      float* best_logp, float* mean_logp, float* align, hipStream_t s) {
-  DecodeArgs a = a_in;
-  a.greedy_run = 1;
-  a.fold = 0;
-  a.k = 1;
   const int B = a.B, R = L * B;
   hipLaunchKernelGGL(score_prep_kernel, dim3((R + 255) / 256), dim3(256), 0, s, targets, tgt_len, B, L, a.V, a.sos,
                      a.eos, sb.feed, sb.tgt, d.err);
@@ -143,7 +139,7 @@ hipError_t run_score(const DecodeArgs& a_in, DecodeBufs& d, const ScoreBufs& sb,
   {
     ProfScope ps(a.prof, CASR_K_SELECT, s);
     hipLaunchKernelGGL(score_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, sb.part, sb.xsum, sb.tl, sb.tgt,
-                       score_col_blocks(a), a.V, B, L, token_logp, best_token, best_logp, mean_logp, d.err);
+                       a.plan.nbp, a.V, B, L, token_logp, best_token, best_logp, mean_logp, d.err);
     hipLaunchKernelGGL(score_total_kernel, dim3((B + 63) / 64), dim3(64), 0, s, token_logp, tgt_len, B, L, total_logp);
   }
   return hipGetLastError();

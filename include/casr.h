@@ -252,8 +252,9 @@ int casr_recurrence_mode(const casr_handle* h, int B);
 
 /* Tuning options of one handle.  The defaults are the measured fastest variants;
  * every value of every option gives the same results bit for bit (tests/test_gpu_parity.py sweeps
- * them), so an option only ever changes speed.  Options are read at each call and are part of the
- * keys of the captured hipGraphs, so changing one between calls takes effect at the next call.
+ * them), so an option only ever changes speed.  Options are read at each call, and every decode path
+ * decision derived from them is part of the key of a captured decode hipGraph, so changing one
+ * between calls takes effect at the next call.
  *   CASR_OPT_FUSE_SELECT     1 (default): the select of step l runs inside a kernel of step l + 1:
  *                            greedy, the LSTMCell (three-launch step) or the attention (folded
  *                            step); beam 4 or 8 with one attention block per utterance, or beam 8

@@ -1,0 +1,338 @@
+// Host check of the decode plan (chinese-asr_amd/csrc/decode_plan.h): built from that header alone
+// with clang AddressSanitizer + UndefinedBehaviorSanitizer and run as a program by
+// tests/test_decode_plan_host.py; no GPU, no HIP runtime.
+//
+// The expected values are the decisions the drivers made before the plan existed (prepare_decode,
+// decoder.hip's row_partials / proj_col_blocks / fsel, attention.hip's attention_kpb), read from that
+// code and worked out by hand here; the sizes in check_carving are that code's allocation formulas.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "decode_plan.h"
+
+using namespace casr;
+
+#define EXPECT(c)                                                                  \
+  do {                                                                             \
+    if (!(c)) {                                                                    \
+      std::fprintf(stderr, "plan_check: %s:%d: %s\n", __FILE__, __LINE__, #c);     \
+      std::exit(3);                                                                \
+    }                                                                              \
+  } while (0)
+
+// the table's inputs "unless a row says otherwise"
+struct In {
+  int caller = PLAN_GREEDY, B = 256, Tp = 266, k = 1;
+  bool align = false;
+  int V = 5004, L = 40;
+  float T = 1.f;
+  Tuning t;
+  BlobFacts blob{1, 1, 1, 1};
+  In& opt(int o, int v) {
+    t.v[o] = v;
+    return *this;
+  }
+};
+static In greedy(int B = 256) {
+  In in;
+  in.B = B;
+  return in;
+}
+static In beam(int B, int k) {
+  In in;
+  in.caller = PLAN_BEAM;
+  in.B = B;
+  in.k = k;
+  return in;
+}
+static const AttnStaticLds kLds{336, 336, 336, 336, 336};
+static DecodePlan plan(const In& in) {
+  casr_config cfg{};
+  cfg.vocab = in.V;
+  cfg.max_len = in.L;
+  cfg.temperature = in.T;
+  return plan_decode(in.caller, in.B, in.Tp, in.k, in.align, cfg, (in.V + 63) / 64 * 64, in.t, in.blob, kLds);
+}
+
+static void check_greedy() {
+  DecodePlan p = plan(greedy());
+  EXPECT(p.status == PLAN_OK && p.R == 256 && p.fold && p.fuse_select && p.partials && p.nbp == 45);
+  EXPECT(!p.ksplit && !p.ksplit_last && !p.split && p.kpb == 1 && !p.store_logits && !p.tile_max && !p.build_fold32);
+  p = plan(greedy().opt(CASR_OPT_DEC_FOLD, 0));
+  EXPECT(!p.fold && p.partials && p.nbp == 64 && p.fuse_select && !p.store_logits);
+  {  // V = 5204 (VP = 5248): 66 five-tile blocks > 64
+    In in = greedy().opt(CASR_OPT_DEC_FOLD, 0);
+    in.V = 5204;
+    p = plan(in);
+    EXPECT(p.status == PLAN_OK && !p.fold && !p.partials && p.nbp == 0 && !p.fuse_select && p.store_logits);
+    in = greedy();
+    in.V = 5204;
+    p = plan(in);
+    EXPECT(p.fold && p.partials && p.nbp == 47 && p.fuse_select);
+  }
+  for (int L : {64, 65}) {
+    In in = greedy();
+    in.L = L;
+    EXPECT(plan(in).status == PLAN_OK && plan(in).fold == (L <= 64));
+  }
+  // the folded attention's LDS: 560 + 9 Tq floats + 2560 cell floats + 336 static bytes
+  EXPECT(attention_lds_bytes(1, 4180, kLds, true) == 163296 && attention_lds_bytes(1, 4200, kLds, true) == 164016);
+  EXPECT(LDS_LIMIT_BYTES == 163840);
+  for (int Tp : {4180, 4200, 4300, 4600}) {
+    In in = greedy();
+    in.Tp = Tp;
+    p = plan(in);
+    if (Tp == 4600) {
+      EXPECT(p.status == PLAN_LDS && (size_t)p.lds_bytes > LDS_LIMIT_BYTES);
+    } else {
+      EXPECT(p.status == PLAN_OK && p.fold == (Tp == 4180) && p.partials && p.fuse_select);
+    }
+  }
+  {  // f32 in effect, and s16 requested on a blob without valid s16 images: the same plan
+    In f32 = greedy(), inval = greedy();
+    f32.blob = BlobFacts{0, 1, 1, 1};
+    inval.blob = BlobFacts{0, 0, 1, 1};
+    p = plan(f32);
+    EXPECT(p.fold && p.build_fold32 && !p.s16 && p.nbp == 45);
+    const DecodePlan q = plan(inval);
+    EXPECT(std::memcmp(&p, &q, sizeof p) == 0);
+    // (s16 in effect but the tables not built: no fold)
+    In odd = greedy();
+    odd.blob = BlobFacts{1, 0, 1, 1};
+    EXPECT(!plan(odd).fold && !plan(odd).build_fold32);
+  }
+  // the k split: R <= 32, and the launch's column blocks within the 64 arrival-counter groups
+  p = plan(greedy(32));
+  EXPECT(p.fold && p.ksplit && p.ksplit_last);  // 443 tiles / 7 = 64 blocks; last step 45
+  EXPECT(!plan(greedy(33)).ksplit && !plan(greedy(33)).ksplit_last);
+  EXPECT(!plan(greedy(32).opt(CASR_OPT_DEC_KSPLIT, 0)).ksplit && !plan(greedy(32).opt(CASR_OPT_DEC_KSPLIT, 0)).ksplit_last);
+  EXPECT(!plan(greedy(32).opt(CASR_OPT_DEC_FOLD, 0)).ksplit);
+  {
+    In in = greedy(32);
+    in.V = 5204;  // 457 tiles / 7 = 66 blocks > 64; the last step's 47 vocabulary blocks fit (as before the plan)
+    p = plan(in);
+    EXPECT(p.fold && !p.ksplit && p.ksplit_last);
+  }
+  // the split attention
+  p = plan(greedy(32).opt(CASR_OPT_ATTN_SPLIT, 1));
+  EXPECT(p.asplit == 8 && p.tc == 36 && p.split == 8);
+  p = plan(greedy(64).opt(CASR_OPT_ATTN_SPLIT, 1));
+  EXPECT(p.asplit == 4 && p.tc == 68 && p.split == 4);
+  p = plan(greedy(65).opt(CASR_OPT_ATTN_SPLIT, 1));
+  EXPECT(!p.asplit && !p.tc && !p.split);
+  {
+    In in = greedy(32).opt(CASR_OPT_ATTN_SPLIT, 1);
+    in.Tp = 4;
+    EXPECT(!plan(in).split && plan(in).fold);
+    in = greedy(32).opt(CASR_OPT_ATTN_SPLIT, 1);
+    in.align = true;
+    EXPECT(!plan(in).split && plan(in).align && plan(in).fold);
+  }
+  p = plan(greedy(48).opt(CASR_OPT_ATTN_SPLIT, 3));
+  EXPECT(p.asplit == 3 && p.tc == 92 && p.split == 3);
+}
+
+static void check_beam() {
+  DecodePlan p = plan(beam(256, 8));
+  EXPECT(p.status == PLAN_OK && p.R == 2048 && p.kpb == 8 && p.fold && p.fuse_select && p.K2 == 16);
+  EXPECT(p.partials && p.nbp == 45 && p.tile_max && p.store_logits && !p.ksplit && !p.split && !p.build_fold32);
+  p = plan(beam(128, 8));
+  EXPECT(p.kpb == 4 && p.fold && p.fuse_select);
+  p = plan(beam(128, 8).opt(CASR_OPT_ATTN_KPB, 8));
+  EXPECT(p.kpb == 8 && p.fold && p.fuse_select);
+  p = plan(beam(256, 4));
+  EXPECT(p.kpb == 4 && p.fold && p.fuse_select && p.K2 == 8);
+  p = plan(beam(64, 16));
+  EXPECT(p.kpb == 4 && p.fold && !p.fuse_select && p.K2 == 32);
+  p = plan(beam(127, 8));
+  EXPECT(p.R == 1016 && !p.fold && p.nbp == 64 && !p.fuse_select);
+  p = plan(beam(512, 2));
+  EXPECT(p.kpb == 2 && !p.fold && p.K2 == 4);
+  p = plan(beam(1024, 1));
+  EXPECT(p.status == PLAN_OK && p.kpb == 1 && !p.fold && p.K2 == 4 && p.store_logits);
+  {
+    In in = beam(256, 8);
+    in.blob.proj_small = 0;
+    EXPECT(!plan(in).fold);
+    in = beam(256, 8);
+    in.blob.dec_small = 0;
+    EXPECT(!plan(in).fold);
+    in = beam(256, 8);
+    in.blob = BlobFacts{0, 1, 1, 1};
+    EXPECT(!plan(in).fold && !plan(in).build_fold32);
+  }
+  p = plan(beam(256, 8).opt(CASR_OPT_FUSE_SELECT, 0));
+  EXPECT(p.fold && !p.fuse_select);
+  {
+    In in = beam(256, 8);
+    in.T = 0.7f;
+    p = plan(in);
+    EXPECT(p.fold && p.fuse_select && !p.partials && p.nbp == 0 && !p.tile_max && p.store_logits);
+    in = beam(256, 8);
+    in.V = 5204;
+    p = plan(in);
+    EXPECT(p.fold && p.partials && p.nbp == 47 && !p.tile_max);
+  }
+  EXPECT(plan(beam(256, 0)).status == PLAN_BAD_K && plan(beam(256, 17)).status == PLAN_BAD_K);
+  EXPECT(plan(beam(256, 1)).status == PLAN_OK && plan(beam(256, 16)).status == PLAN_OK);
+  p = plan(beam(256, 16));
+  EXPECT(p.fin_lds == 8336);
+  {
+    In in = beam(256, 16);
+    in.L = 320;  // 66,576 B > 64 KiB: the thread-per-utterance finalize
+    EXPECT(plan(in).status == PLAN_OK && plan(in).fin_lds == 0);
+  }
+}
+
+static void check_score() {
+  for (int s16 = 0; s16 < 2; ++s16) {
+    In in;
+    in.caller = PLAN_SCORE;
+    in.blob = BlobFacts{s16, s16, 1, 1};
+    const DecodePlan p = plan(in);
+    EXPECT(p.status == PLAN_OK && p.k == 1 && p.R == 256 && !p.fold && !p.build_fold32 && !p.fuse_select);
+    EXPECT(p.partials && p.nbp == 64 && !p.ksplit && !p.split && p.s16 == s16);
+  }
+  In in;
+  in.caller = PLAN_SCORE;
+  in.V = 5204;
+  EXPECT(plan(in).status == PLAN_VOCAB);
+}
+
+static void check_keys() {
+  const DecodePlan p = plan(beam(256, 8));
+  const float sc[2] = {0.25f, 0.5f};
+  int x = 0, y = 0;
+  const void* bufs[2] = {&x, &y};
+  const std::vector<uint64_t> base = decode_graph_key(3, p, sc, 2, bufs, 2);
+  EXPECT(base == decode_graph_key(3, p, sc, 2, bufs, 2));
+  for (size_t i = 0; i < sizeof(DecodePlan) / sizeof(int32_t); ++i) {  // any one field
+    DecodePlan q = p;
+    int32_t w;
+    std::memcpy(&w, reinterpret_cast<char*>(&q) + 4 * i, 4);
+    w ^= 1;
+    std::memcpy(reinterpret_cast<char*>(&q) + 4 * i, &w, 4);
+    EXPECT(decode_graph_key(3, q, sc, 2, bufs, 2) != base);
+  }
+  const DecodePlan nofuse = plan(beam(256, 8).opt(CASR_OPT_FUSE_SELECT, 0));
+  EXPECT(nofuse.fuse_select != p.fuse_select && decode_graph_key(3, nofuse, sc, 2, bufs, 2) != base);
+  EXPECT(decode_graph_key(2, p, sc, 2, bufs, 2) != base);
+  const float sc2[2] = {0.25f, 0.75f};
+  EXPECT(decode_graph_key(3, p, sc2, 2, bufs, 2) != base);
+  const void* bufs2[2] = {&x, &x};
+  EXPECT(decode_graph_key(3, p, sc, 2, bufs2, 2) != base);
+}
+
+// one carved workspace: its regions (pointer, bytes, required alignment) inside [base, base + size)
+struct Region {
+  const void* p;
+  size_t bytes, align;
+};
+static void check_regions(char* base, size_t size, size_t at_least, const std::vector<Region>& rs) {
+  EXPECT(size >= at_least);
+  for (size_t i = 0; i < rs.size(); ++i) {
+    const char* p = static_cast<const char*>(rs[i].p);
+    EXPECT(p >= base && p + rs[i].bytes <= base + size);
+    EXPECT((size_t)(p - base) % rs[i].align == 0 && (uintptr_t)p % rs[i].align == 0);
+    std::memset(const_cast<char*>(p), (int)i + 1, rs[i].bytes);  // (under ASan: inside the allocation)
+    for (size_t j = 0; j < i; ++j) {
+      const char* q = static_cast<const char*>(rs[j].p);
+      EXPECT(p + rs[i].bytes <= q || q + rs[j].bytes <= p);
+    }
+  }
+}
+// sizing pass, then the carve of an exact-size 16 B-aligned allocation
+template <class Carve>
+static char* carved(Carve carve, size_t* size) {
+  *size = carve(nullptr);
+  char* base = static_cast<char*>(std::aligned_alloc(256, (*size + 255) / 256 * 256));
+  EXPECT(base && carve(base) == *size);
+  return base;
+}
+
+static void check_carving() {
+  const int cases[4][4] = {{1, 1, 1, 4}, {3, 16, 40, 5004}, {256, 8, 40, 5004}, {5, 2, 64, 5204}};
+  const int Tp = 266;
+  for (const auto& cs : cases) {
+    const int B = cs[0], k = cs[1], L = cs[2], V = cs[3];
+    const size_t R = (size_t)B * k, f = sizeof(float);
+    DecodeBufs d{};
+    size_t size;
+    char* base = carved([&](void* p) { return carve_state(p, (int)R, d); }, &size);
+    const size_t slots = R >= 2048 ? HD / 32 : HD / 16;
+    check_regions(base, size, (2 * R * ST + slots * R * A) * f,
+                  {{d.st[0], R * ST * f, 16}, {d.st[1], R * ST * f, 16}, {d.qpart, slots * R * A * f, 16}});
+    std::free(base);
+
+    base = carved([&](void* p) { return carve_logits(p, (int)R, V, d); }, &size);
+    check_regions(base, size, (R * V + 3 * R * 64 + R * 320) * f,
+                  {{d.logits, R * V * f, 16}, {d.part.mx, R * 64 * f, 16}, {d.part.se, R * 64 * f, 16},
+                   {d.part.ix, R * 64 * 4, 16}, {d.part.tmx, R * 320 * f, 16}});
+    std::free(base);
+
+    base = carved([&](void* p) { return carve_small(p, B, (int)R, L, d); }, &size);
+    check_regions(base, size, (6 * R + L + B + R + 1) * 4 + 256,
+                  {{d.tok[0], R * 4, 4}, {d.tok[1], R * 4, 4}, {d.src[0], R * 4, 4}, {d.src[1], R * 4, 4},
+                   {d.score[0], R * f, 4}, {d.score[1], R * f, 4}, {d.newdone, (size_t)L * 4, 4},
+                   {d.topfin, (size_t)B, 1}, {d.fin, R, 1}});
+    std::free(base);
+
+    const size_t n = (size_t)B * L * k;
+    base = carved([&](void* p) { return carve_records(p, B, L, k, d); }, &size);
+    check_regions(base, size, n * (f + 4 + 1) + 256, {{d.rec_score, n * f, 4}, {d.rec_src, n * 4, 4}, {d.rec_valid, n, 1}});
+    std::free(base);
+
+    base = carved([&](void* p) { return carve_ksplit(p, d); }, &size);
+    check_regions(base, size, DG_KS_PART_BYTES + DG_KS_COUNTERS * 4,
+                  {{d.kspart, (size_t)128 * 4 * 7 * 64 * 16, 16}, {d.kscnt, 128 * 4, 4}});
+    std::free(base);
+
+    base = carved([&](void* p) { return carve_attn_split(p, (int)R, d); }, &size);
+    check_regions(base, size, R * 8 * (C + 4) * f + R * 4, {{d.aspart, R * 8 * (C + 4) * f, 16}, {d.ascnt, R * 4, 4}});
+    std::free(base);
+
+    for (size_t nal : {(size_t)0, (size_t)L * Tp * B}) {
+      GreedyOut o{};
+      base = carved([&](void* p) { return carve_greedy_out(p, B, L, nal, o); }, &size);
+      std::vector<Region> rs = {{o.tokens, (size_t)B * L * 4, 4}, {o.len, (size_t)B * 4, 4}, {o.accum, B * f, 4},
+                                {o.fin, (size_t)B, 1}};
+      EXPECT((o.align != nullptr) == (nal != 0));
+      if (nal) rs.push_back({o.align, nal * f, 4});
+      check_regions(base, size, 4 * ((size_t)B * L + B) + f * (B + nal) + B + 64, rs);
+      std::free(base);
+    }
+    BeamOut o{};
+    base = carved([&](void* p) { return carve_beam_out(p, B, L, o); }, &size);
+    check_regions(base, size, 4 * ((size_t)B * L + B + 1) + f * B + 64,
+                  {{o.tokens, (size_t)B * L * 4, 4}, {o.len, (size_t)B * 4, 4}, {o.steps, 4, 4}, {o.score, B * f, 4}});
+    std::free(base);
+  }
+}
+
+static void check_options() {
+  const int defaults[CASR_OPT_COUNT] = {1, 0, 1, -1, 2, 2, 2, 2, 0, 0, 1, 0, 0, 1, 1, 1, 1, 0, 0};
+  const Tuning t;
+  for (int o = 0; o < CASR_OPT_COUNT; ++o) {
+    EXPECT(OPTIONS[o].id == o && t[o] == defaults[o] && OPTIONS[o].def == defaults[o]);
+    EXPECT(OPTIONS[o].lo <= OPTIONS[o].def && OPTIONS[o].def <= OPTIONS[o].hi);
+    EXPECT(option_value_ok(o, OPTIONS[o].lo) && option_value_ok(o, OPTIONS[o].hi) && option_value_ok(o, OPTIONS[o].def));
+    EXPECT(!option_value_ok(o, OPTIONS[o].lo - 1) && !option_value_ok(o, OPTIONS[o].hi + 1));
+  }
+  for (int v : {1, 2, 3, 5, 6, 7}) EXPECT(!option_value_ok(CASR_OPT_ATTN_KPB, v));
+  EXPECT(option_value_ok(CASR_OPT_ATTN_KPB, 4));
+  EXPECT(!option_value_ok(-1, 0) && !option_value_ok(CASR_OPT_COUNT, 0));
+  EXPECT(OPTIONS[CASR_OPT_ATTN_SPLIT].hi == AT_SPLIT_MAX && OPTIONS[CASR_OPT_REC_SLEEP].hi == 16);
+}
+
+int main() {
+  check_greedy();
+  check_beam();
+  check_score();
+  check_keys();
+  check_carving();
+  check_options();
+  std::puts("plan_check ok");
+  return 0;
+}

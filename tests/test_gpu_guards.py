@@ -1,5 +1,5 @@
-"""The guards that send a decode back to the three-launch step (casr_capi.hip prepare_decode), and
-the select paths of vocabularies past the projection's partial blocks, against the CPU oracle.
+"""The guards that send a decode back to the three-launch step (the decode plan, csrc/decode_plan.h
+plan_decode; its rules alone are checked on the host by test_decode_plan_host.py), and the select paths of vocabularies past the projection's partial blocks, against the CPU oracle.
 
 Each guard is a shape the folded step cannot take; a regression in one of them would not fail
 loudly but give wrong tokens (a counter read past the prologue's 64 lanes, an LDS area past
