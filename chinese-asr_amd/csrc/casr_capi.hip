@@ -629,6 +629,13 @@ int casr_log_mel(casr_handle* h, const float* wav, const int32_t* n_samples, int
                  float preemphasis, float* fbank, int32_t* frames, void* stream) {
   if (!h || !wav || !n_samples || !fbank || !frames || B <= 0 || n_max <= 0 || t_max <= 0)
     return fail(h, CASR_ERR_ARG, "casr_log_mel: bad arguments");
+  // the reference skips the filter there and keeps all n samples (data.py:201-202): another
+  // operation (no one-sample shift, another frame count) than y[m] = x[m+1] - pre x[m]
+  if (!(preemphasis > 0.f))
+    return fail(h, CASR_ERR_ARG,
+                "casr_log_mel: preemphasis %g <= 0 is the reference's unfiltered form (data.py:201-202), "
+                "which is not implemented",
+                (double)preemphasis);
   if (t_max < frontend_frames(n_max))
     return fail(h, CASR_ERR_ARG, "casr_log_mel: t_max %d < %d frames of n_max %d samples", t_max,
                 frontend_frames(n_max), n_max);

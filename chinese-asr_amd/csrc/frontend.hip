@@ -46,6 +46,11 @@ CASR_DEV float preemph_win(float w, float x1, float x0, float pre) {
   return w * (x1 - pre * x0);
 }
 
+// log rounded from double: the device's logf is up to 1.75 float32 steps off near 475 (the peak band
+// of a 1 kHz tone, where torch's log lands 0.06 from the exact value), and exp of that error is the
+// whole linear-domain budget of such a frame (tests/test_gpu_accuracy.py).  80 per frame
+CASR_DEV float log_rn(float x) { return (float)log((double)x); }
+
 // exchange slot of FFT position p (conflict-free for the four stage patterns)
 CASR_DEV int fe_slot(int p) { return p ^ ((p >> 2) & 31); }
 // base-4 digit reversal of an 8-bit index: after the four DIF stages X[k] sits at position rev4(k)
@@ -236,7 +241,7 @@ __global__ __launch_bounds__(256) void log_mel_kernel(const float* __restrict__ 
       float acc = 0.f;
 #pragma unroll
       for (int i = 0; i < W; ++i) acc = fmaf(pv[i], wv[i], acc);  // matmul: fused
-      o[m] = logf(acc == 0.f ? 1.1920928955078125e-07f : acc);
+      o[m] = log_rn(acc == 0.f ? 1.1920928955078125e-07f : acc);
     };
     mel(std::integral_constant<int, FE_W0>{}, lane, fw0);
     if (lane + 64 < F) mel(std::integral_constant<int, FE_W1>{}, lane + 64, fw1);
@@ -293,9 +298,10 @@ __global__ __launch_bounds__(64 * FQ_Q / 4) void log_mel_q16_kernel(const float*
   float2* z = zs[qd];
   float* p = pw[qd];
   // the samples of a frame: point m = l + 16 r needs x[2m .. 2m + 2] (x[512] at most: inside the
-  // signal for every frame f < L); loaded one frame ahead, so a frame's loads fly while the previous
-  // frame computes.  All points are loaded, from one lane pointer with immediate offsets: the window
-  // zeroes the ones outside it, as the reference's full-frame product does
+  // signal for every frame f < L; a frame that is not live loads frame 0 of its row, x[0..512], inside
+  // the row because launch_log_mel sends Nmax < 513 elsewhere); loaded one frame ahead, so a frame's
+  // loads fly while the previous frame computes.  All points are loaded, from one lane pointer with
+  // immediate offsets: the window zeroes the ones outside it, as the reference's full-frame product does
   float xs[16][3];
   auto load_frame = [&](int f) {
     const bool live = f < L && f < Tmax;
@@ -397,7 +403,7 @@ __global__ __launch_bounds__(64 * FQ_Q / 4) void log_mel_q16_kernel(const float*
       float acc = 0.f;
 #pragma unroll
       for (int i = 0; i < W; ++i) acc = fmaf(pv[i], wv[i], acc);  // matmul: fused
-      o[m] = logf(acc == 0.f ? 1.1920928955078125e-07f : acc);
+      o[m] = log_rn(acc == 0.f ? 1.1920928955078125e-07f : acc);
     };
 #pragma unroll
     for (int i = 0; i < 4; ++i) mel(std::integral_constant<int, FE_W0>{}, l + 16 * i);
@@ -405,17 +411,36 @@ __global__ __launch_bounds__(64 * FQ_Q / 4) void log_mel_q16_kernel(const float*
     lds_fence();  // this frame's pw / z reads are done before the next frame's writes
   }
 }
+
+// Nmax < 513: no utterance holds a frame (torch.stft raises, data.py:204), and a row of wav is
+// shorter than the 513 samples log_mel_q16_kernel loads for a frame that is not live.  Zero rows,
+// frames 0 and the flag (every n is < 513 or > Nmax); wav and nsamp are not read
+__global__ __launch_bounds__(256) void log_mel_short_kernel(int Tmax, float* __restrict__ out,
+                                                            int32_t* __restrict__ frames, int32_t* __restrict__ err) {
+  const int b = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, n = (size_t)Tmax * F;
+  if (i < n) out[b * n + i] = 0.f;
+  if (i == 0) {
+    frames[b] = 0;
+    if (b == 0) atomicOr(err, CASR_DEV_BAD_AUDIO);
+  }
+}
 }  // namespace
 
 // create_fb_matrix (data.py:21-57) in float32 like the reference's torch ops, including the
 // quirk stft_freqs = linspace(f_min, f_max, n_stft) (data.py:43).  fb is [n_stft][n_mels].
+// A weight is a difference of two frequencies near 7 kHz over a band width of 30 to 250 Hz, so one
+// last bit of a mel point moves it by 1e-5.  Two operations therefore follow torch to the bit:
+// linspace's start + step i is one rounding (a fused multiply-add), and log10 is the correctly
+// rounded one (log10f(1 + 80 / 700) is one bit above it).  With them the matrix equals the one torch
+// builds for the reference bit for bit (tests/test_capi_host.py, against tests/golden/golden.npz)
 void mel_filterbank(int n_stft, float f_min, float f_max, int n_mels, float* fb) {
   auto linspace = [](float a, float e, int n, int i) -> float {  // torch CPU linspace (symmetric)
     if (n == 1) return a;
     const float step = (e - a) / (float)(n - 1);
-    return i < n / 2 ? a + step * (float)i : e - step * (float)(n - 1 - i);
+    return i < n / 2 ? fmaf(step, (float)i, a) : fmaf(-step, (float)(n - 1 - i), e);
   };
-  auto hz2mel = [](float f) { return 2595.f * log10f(1.f + f / 700.f); };
+  auto hz2mel = [](float f) { return 2595.f * (float)log10((double)(1.f + f / 700.f)); };
   auto mel2hz = [](float m) { return 700.f * (powf(10.f, m / 2595.f) - 1.f); };
   const float m_min = f_min == 0.f ? 0.f : hz2mel(f_min), m_max = hz2mel(f_max);
   std::vector<float> f_pts(n_mels + 2), f_diff(n_mels + 1);
@@ -453,8 +478,17 @@ void build_frontend_const(FrontendConst* c) {
     c->hi[m] = hi;
     for (int q = lo; q < hi; ++q) c->fb[m][q - lo] = fb[q * F + m];
   }
-  // torch.hann_window(400) (periodic): 0.5 - 0.5 cos(2 pi j / 400), evaluated in float32
-  for (int j = 0; j < WIN; ++j) c->win[j] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * j / WIN));
+  // torch.hann_window(400) (periodic, data.py:381-382), evaluated in float32 the way torch does:
+  // arange(400) times the float32 of 2 pi / 400, cos, times -0.5, plus 0.5.  The rounded argument
+  // moves a value by up to 2.4e-7 from the double-precision window, and a frame whose mel bands
+  // hold only the leakage of a component below them (a DC stretch) follows the window's last bits:
+  // 18 times a float32 evaluation's error on the golden wav0 with the window rounded from double
+  // (tests/test_accuracy_budget_host.py).  What is left is the last bit of cosf against torch's
+  {
+#pragma clang fp contract(off)
+    const float step = (float)(2.0 * M_PI / WIN);
+    for (int j = 0; j < WIN; ++j) c->win[j] = 0.5f + -0.5f * cosf((float)j * step);
+  }
   for (int i = 0; i < NC; ++i) {
     c->tw256r[i] = (float)cos(-2.0 * M_PI * i / NC);
     c->tw256i[i] = (float)sin(-2.0 * M_PI * i / NC);
@@ -472,7 +506,11 @@ int frontend_frames(int n_samples) {
 hipError_t launch_log_mel(const float* wav, const int32_t* nsamp, int B, int Nmax, int Tmax, float pre,
                           const FrontendConst* k, float* out, int32_t* frames, int32_t* err, hipStream_t s,
                           int form) {
-  if (form == 0) {  // the one-wave-per-frame form (round 4), kept for comparison: the same bits
+  if (Nmax < NFFT + 1) {  // no frame anywhere: neither kernel below runs (q16 would read past a row)
+    const size_t n = (size_t)Tmax * F;
+    hipLaunchKernelGGL(log_mel_short_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, s, Tmax, out, frames,
+                       err);
+  } else if (form == 0) {  // the one-wave-per-frame form (round 4), kept for comparison: the same bits
     constexpr int FPB = FE_WAVES * FE_FPW;  // frames per block
     dim3 grid((Tmax + FPB - 1) / FPB > 0 ? (Tmax + FPB - 1) / FPB : 1, B);
     hipLaunchKernelGGL(log_mel_kernel<>, grid, dim3(256), 0, s, wav, nsamp, Nmax, Tmax, pre, k, out, frames, err);

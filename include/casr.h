@@ -114,7 +114,12 @@ int casr_features(casr_handle* h, const float* fbank, const int32_t* frames, int
  *   fbank     [B][t_max][80] log-mel, rows past frames[b] zero
  *   frames    [B] = 1 + (n_samples[b] - 1 - 512) / 160  (0 and device flag 64 when
  *             n_samples[b] < 513, where torch.stft raises, data.py:204)
- * t_max must be >= casr_log_mel_frames(n_max). */
+ * t_max must be >= casr_log_mel_frames(n_max).  Any n_max > 0 is accepted: below 513 no row
+ * holds a frame, wav is not read, every frames[b] is 0, fbank is all zeros and flag 64 is set.
+ * preemphasis must be > 0 (the reference's value is 0.97): at preemphasis <= 0 the reference
+ * skips the filter and keeps all n samples (data.py:201-202), which is another operation (no
+ * one-sample shift, 1 + (n - 512) / 160 frames) and is not implemented; CASR_ERR_ARG, nothing
+ * is launched or written. */
 int casr_log_mel(casr_handle* h, const float* wav, const int32_t* n_samples, int B, int n_max, int t_max,
                  float preemphasis, float* fbank, int32_t* frames, void* stream);
 
@@ -122,7 +127,9 @@ int casr_log_mel(casr_handle* h, const float* wav, const int32_t* n_samples, int
 int casr_log_mel_frames(int n_samples);
 
 /* The mel filterbank [n_stft][n_mels] casr_log_mel uses (create_fb_matrix, data.py:21-57,
- * float32).  Host only, no device needed. */
+ * float32).  Equal bit for bit to the matrix torch builds for the reference: linspace's
+ * start + step i is one fused rounding and log10 the correctly rounded one, as torch's are
+ * (a weight follows the last bit of the mel points).  Host only, no device needed. */
 int casr_mel_filterbank(int n_stft, float f_min, float f_max, int n_mels, float* fb_host);
 
 /* The list-of-tensors boundary of Model.eval_one_batch_* (model.py:514-516): gather B
@@ -228,9 +235,10 @@ int casr_set_persistent(casr_handle* h, int enable);
  *                    product (hi.hi + 2^-11 (hi.lo + lo.hi)) on the 16x-faster f16 pipes; 22
  *                    significant operand bits.  Measured per stage against float64
  *                    (tests/test_gpu_accuracy.py, profiles/accuracy/accuracy_budget.json): at most
- *                    2.0 times the float32 oracle's own error, and at or below the F32 path's
- *                    (at most 3.6 times) at every stage but the greedy accum (1.42 against 1.26
- *                    times, both within the rounding of a 40-term f32 sum).
+ *                    3.1 times the float32 oracle's own error (the beam score at R = 2048, k = 8;
+ *                    2.6 everywhere else), and at or below the F32 path's (at most 3.6 times) at
+ *                    every stage but two 40-term f32 sums, both within such a sum's rounding: the
+ *                    greedy accum (1.42 against 1.26 times) and the beam score (3.05 against 2.50).
  *   CASR_PREC_S16X1  (round 6, an opt-in perf arithmetic, never the headline: BASELINE config 2's
  *                    "bf16 perf mode") the hi.hi MFMA of every split product only:
  *                    one f16 MFMA instead of three, 11 significant operand bits (bf16 keeps 8),

@@ -21,6 +21,24 @@ from . import casr_oracle as O
 F32 = torch.float32
 
 
+def log_mel(wav, preemphasis=0.97, fb=None, window=None, floor=True):
+    """data.py:167-224 (inference: no dither, no augmentation), float32 throughout: wav [n] ->
+    log-mel [L, 80] (a tensor), L = 1 + (n - 1 - 512) // 160.  The float32 reference of the log-mel
+    accuracy budget (casr_oracle.log_mel takes its FFT in float64).  fb, window (win_length =
+    its length) and floor are there for the budget's seeded defects."""
+    a = np.asarray(wav, np.float32)
+    a = a[1:] - np.float32(preemphasis) * a[:-1]             # data.py:201-202 (numpy float32)
+    window = torch.hann_window(400) if window is None else torch.as_tensor(window, dtype=F32)   # data.py:381-382
+    spec = torch.stft(torch.from_numpy(a).view(1, -1), n_fft=512, hop_length=160, win_length=window.shape[0],
+                      window=window, center=False, normalized=False, onesided=True, return_complex=True)
+    power = torch.view_as_real(spec).transpose(1, 2).pow(2).sum(-1)      # data.py:220-221, [1, L, 257]
+    fb = torch.as_tensor(O.create_fb_matrix() if fb is None else np.asarray(fb, np.float32))
+    mel = torch.matmul(power, fb)                            # data.py:80, :222
+    if floor:
+        mel.masked_fill_(mel == 0., torch.finfo(F32).eps)    # data.py:223
+    return torch.log(mel[0])                                 # data.py:224
+
+
 def features_from_fbank(fbank, eps=1e-6):
     """data.py:226-249 (deltas, 3-frame stacking) + main.py:37 (CMVN): fbank [T, 80] -> [T//3, 720]."""
     x = torch.as_tensor(np.asarray(fbank, np.float32))

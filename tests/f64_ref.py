@@ -12,6 +12,8 @@ Layouts are the reference's (time-major): enc [T, B, 2H], keys [T, B, A], alignm
 
 budget() compares a candidate with this truth, in multiples of the error that a plain float32
 evaluation of the same stage on the same inputs (the numpy oracle) makes against it.
+log_mel_budget() does so on two figures of the front end's output: as it is, and in the linear
+domain relative to each frame's scale (mel_linear), where the float32 reference is the torch port.
 """
 import numpy as np
 
@@ -20,6 +22,42 @@ F64 = np.float64
 
 def _f64(x):
     return np.asarray(x, dtype=F64)
+
+
+# --------------------------------------------------------------------------------------
+# front end
+# --------------------------------------------------------------------------------------
+FLT_EPSILON = F64(np.finfo(np.float32).eps)
+
+
+def log_mel(wav, fb, window, preemphasis=0.97, n_fft=512, hop=160):
+    """wav [n] -> (log-mel [L, n_mels], mel power [L, n_mels]), L = 1 + (n - 1 - n_fft) // hop
+    (get_log_mel, data.py:167-224, inference: no dither, no augmentation).  Three float32 constants
+    are data of the operation and are only widened: the pre-emphasis coefficient as numpy's
+    float32 product rounds it (data.py:201-202), the window (torch.hann_window(400), periodic,
+    data.py:381-382; torch.stft centres it in the n_fft points) and the filterbank fb [n_fft // 2 + 1,
+    n_mels] (create_fb_matrix, data.py:21-57).  Then, in float64: y[m] = x[m+1] - pre x[m]; frames
+    y[hop f + j] w[j], j < n_fft, no centring (data.py:205-209); |rfft|^2 (data.py:220-221); the
+    product with fb (data.py:222); mel == 0 -> FLT_EPSILON and log (data.py:223-224).  The mel
+    power is returned as computed, before the floor."""
+    x = _f64(np.asarray(wav, np.float32))
+    y = x[1:] - F64(np.float32(preemphasis)) * x[:-1]
+    win = _f64(np.asarray(window, np.float32))
+    lpad = (n_fft - win.shape[0]) // 2
+    w = np.zeros(n_fft)
+    w[lpad:lpad + win.shape[0]] = win
+    assert y.shape[0] >= n_fft, "shorter than one frame (torch.stft raises, data.py:204)"
+    L = 1 + (y.shape[0] - n_fft) // hop
+    frames = y[np.arange(L)[:, None] * hop + np.arange(n_fft)[None, :]] * w[None, :]
+    spec = np.fft.rfft(frames, axis=1)
+    assert spec.dtype == np.complex128
+    mel = (spec.real ** 2 + spec.imag ** 2) @ _f64(np.asarray(fb, np.float32))
+    return np.log(np.where(mel == 0, FLT_EPSILON, mel)), mel
+
+
+def log_mel_frames(n, n_fft=512, hop=160):
+    """frames of n samples: the pre-emphasised signal has n - 1"""
+    return 1 + (n - 1 - n_fft) // hop if n - 1 >= n_fft else 0
 
 
 # --------------------------------------------------------------------------------------
@@ -259,3 +297,26 @@ def budget(candidate, truth64, ref32, M=M_DEFAULT, valid=None, pad=0.0, tag=None
     assert fig["e_max"] <= M * fig["e_ref_max"] + extra, (tag, "max", fig)
     assert fig["e_rms"] <= M * fig["e_ref_rms"] + extra, (tag, "rms", fig)
     return fig
+
+
+def mel_linear(out, mel64, valid=None):
+    """A log-mel output in the linear domain: exp(out) divided, frame by frame, by that frame's
+    largest float64 mel power (after the floor).  mel64: the float64 mel power of the same shape;
+    with out = None, the float64 truth itself.  Elements outside ``valid`` are 0.  An error of this
+    figure is relative to the frame's scale, so a bin that holds only another bin's leakage (where a
+    float32 transform is off by 0.2 in the log domain) cannot set it."""
+    floored = np.where(_f64(mel64) == 0, FLT_EPSILON, _f64(mel64))
+    v = np.ones(floored.shape, bool) if valid is None else np.broadcast_to(np.asarray(valid, bool), floored.shape)
+    scale = np.where(v, floored, 0).max(axis=-1, keepdims=True)
+    lin = floored if out is None else np.exp(np.where(v, _f64(out), 0))
+    return np.where(v, lin / np.where(scale > 0, scale, 1), 0)
+
+
+def log_mel_budget(candidate, truth_log, truth_mel, ref32, M=M_DEFAULT, valid=None, tag=None):
+    """budget() on two figures of a log-mel output, both at the same M: ``log``, the output as it
+    is (padding rows exactly 0), and ``lin``, mel_linear() of candidate and ref32 against the
+    float64 mel power.  Returns (figures of log, figures of lin)."""
+    log = budget(candidate, truth_log, ref32, M, valid=valid, tag=None if tag is None else tag + " log")
+    lin = budget(mel_linear(candidate, truth_mel, valid), mel_linear(None, truth_mel, valid),
+                 mel_linear(ref32, truth_mel, valid), M, valid=valid, tag=None if tag is None else tag + " lin")
+    return log, lin

@@ -20,6 +20,41 @@ def fbank_for(b, T, n_mels=80):
     return np.random.RandomState(1234 + b).standard_normal((T, n_mels)).astype(np.float32)
 
 
+def synth_wav(n, seed):
+    """a speech-like signal: an amplitude-modulated tone of 100 to 400 Hz in noise"""
+    rs = np.random.RandomState(seed)
+    t = np.arange(n) / 16000.0
+    f0 = rs.uniform(100, 400)
+    w = 0.4 * np.sin(2 * np.pi * f0 * t) * (1 + 0.5 * np.sin(2 * np.pi * 3 * t)) + 0.05 * rs.standard_normal(n)
+    return w.astype(np.float32)
+
+
+WAV_FAMILIES = ("noise", "speech", "quiet", "pcm", "dc")
+
+
+def wav_family(kind, n, seed):
+    """n float32 samples of one signal family of the log-mel accuracy budgets: white noise at 0.1,
+    synth_wav, noise at 1e-4, synth_wav quantised to int16 (what a 16-bit WAV file holds), a DC
+    offset of 0.3 plus noise; "tone": 1 kHz at 0.5, whose leakage bins are ill-conditioned in the
+    log domain."""
+    rs = np.random.RandomState(seed)
+    if kind == "noise":
+        x = 0.1 * rs.standard_normal(n)
+    elif kind == "speech":
+        x = synth_wav(n, seed)
+    elif kind == "quiet":
+        x = 1e-4 * rs.standard_normal(n)
+    elif kind == "pcm":
+        x = np.clip(np.round(synth_wav(n, seed) * 32768.0), -32768, 32767) / 32768.0
+    elif kind == "dc":
+        x = 0.3 + 0.05 * rs.standard_normal(n)
+    elif kind == "tone":
+        x = 0.5 * np.sin(2 * np.pi * 1000.0 * np.arange(n) / 16000.0)
+    else:
+        raise ValueError(kind)
+    return np.asarray(x, np.float32)
+
+
 def golden_frames(meta):
     return [int(x) for x in meta["frames"]]
 

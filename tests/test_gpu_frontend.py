@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from golden_util import load_golden
+from golden_util import load_golden, synth_wav
 from oracle import casr_oracle as O
 from casr.config import CasrConfig
 from casr.weights import synthetic_state_dicts
@@ -25,14 +25,6 @@ def eng():
     e = Engine(CFG, *synthetic_state_dicts(CFG, peaked=True))
     yield e
     e.close()
-
-
-def synth_wav(n, seed):
-    rs = np.random.RandomState(seed)
-    t = np.arange(n) / 16000.0
-    f0 = rs.uniform(100, 400)
-    w = 0.4 * np.sin(2 * np.pi * f0 * t) * (1 + 0.5 * np.sin(2 * np.pi * 3 * t)) + 0.05 * rs.standard_normal(n)
-    return w.astype(np.float32)
 
 
 def test_log_mel_matches_reference_golden(eng):
@@ -99,6 +91,33 @@ def test_log_mel_short_audio_flag(eng):
     fb, frames = eng.log_mel(wav, torch.tensor([2000, 400], dtype=torch.int32))
     assert int(frames[1]) == 0 and int(frames[0]) == 1 + (2000 - 1 - 512) // 160
     assert eng.device_flags() & 64
+
+
+@pytest.mark.parametrize("pre", [0.0, -0.97, float("nan")])
+def test_log_mel_refuses_preemphasis_le_0(eng, pre):
+    """At preemphasis <= 0 the reference skips the filter and keeps all n samples
+    (data.py:201-202): no one-sample shift, another frame count.  casr_log_mel does not implement
+    that form and refuses it before anything is launched: CASR_ERR_ARG, a message naming the
+    reference lines, outputs and flags untouched."""
+    import ctypes
+    from casr.engine import _ptr, _stream
+    wav = torch.from_numpy(synth_wav(2000, 5)[None]).cuda()
+    ns = torch.tensor([2000], dtype=torch.int32, device="cuda")
+    fb = torch.full((1, 10, 80), 7.0, device="cuda")
+    frames = torch.full((1,), -5, dtype=torch.int32, device="cuda")
+    rc = eng.lib.casr_log_mel(eng.handle, _ptr(wav), _ptr(ns), 1, 2000, 10, ctypes.c_float(pre), _ptr(fb),
+                              _ptr(frames), _stream())
+    assert rc == 1  # CASR_ERR_ARG
+    msg = eng.lib.casr_last_error(eng.handle).decode()
+    assert "preemphasis" in msg and "data.py:201-202" in msg
+    torch.cuda.synchronize()
+    assert (fb == 7.0).all() and int(frames[0]) == -5
+    assert eng.device_flags() == 0
+    with pytest.raises(Exception, match="data.py:201-202"):
+        eng.log_mel(wav, [2000], preemphasis=pre)
+    # the reference's value still runs
+    out, fr = eng.log_mel(wav, [2000])
+    assert int(fr[0]) == 10 and eng.device_flags() == 0
 
 
 def test_wav_to_greedy_matches_oracle(eng):

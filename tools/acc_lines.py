@@ -4,7 +4,10 @@ and the per-stage table of that test's docstring.
   python tools/acc_lines.py pytest.log [out.json]
 
 Each line reads "[acc] stage shape arithmetic what max_ratio=.. rms_ratio=.. e_ref_max=.. e_max=..": the
-ratio of the device's error to the float32 reference's, both against float64 (tests/f64_ref.py)."""
+ratio of the device's error to the float32 reference's, both against float64 (tests/f64_ref.py).
+The log-mel front end has two lines per case, "log" and "lin" (the log output, and exp(out) over the
+frame's largest float64 mel power); its shape is case-form (form q16 or wave), and the arithmetic
+column only names the engine that ran it.  The beam lines are one per case (B, k, weights)."""
 import json
 import re
 import sys
