@@ -241,9 +241,22 @@ int casr_set_persistent(casr_handle* h, int enable);
  *                    greedy accum (1.42 against 1.26 times) and the beam score (3.05 against 2.50).
  *   CASR_PREC_S16X1  (round 6, an opt-in perf arithmetic, never the headline: BASELINE config 2's
  *                    "bf16 perf mode") the hi.hi MFMA of every split product only:
- *                    one f16 MFMA instead of three, 11 significant operand bits (bf16 keeps 8),
- *                    f32 accumulators.  Token ids are NOT identical to the reference's; bench.py
- *                    reports its token agreement.  It is a separate build of this library,
+ *                    one f16 MFMA instead of three, f32 accumulators: a site computes exactly
+ *                    sum_k f16(a_k) f16(b_k), operands rounded to nearest even.  Against the float64
+ *                    evaluation of that model the device sits where a float32 evaluation of it
+ *                    sits, at every stage (at most 2.2 times its error; tests/test_gpu_accuracy_s16x1.py,
+ *                    profiles/accuracy/accuracy_budget_s16x1.json).  What the rounding costs,
+ *                    measured per stage on its own inputs as the largest distance from the
+ *                    unrounded float64 stage: encoder output 1.7e-3 (rms 2e-4), keys 4.8e-4, a
+ *                    token's log-probability 6e-5 with flat and up to 1e-2 with peaked output
+ *                    distributions, attention weights 3e-6, a 40-step score 3e-3 and up to 1e-1.
+ *                    The sites differ by decode path: the three-launch step (casr_score, beam
+ *                    below 1,024 rows, every decode's step 0) rounds the embedding and [ctx | h]
+ *                    of the LSTMCell and keeps its query h . W_hidden an exact-f32 MFMA; the folded
+ *                    step rounds [ctx | h] only and takes the embedding's gate part from an f32
+ *                    table, and its query is an f32 fma chain under greedy and an s16 MFMA (h and
+ *                    W_hidden rounded) under beam.  Token ids are NOT identical to the
+ *                    reference's; bench.py reports its token agreement.  It is a separate build of this library,
  *                    libcasr_hip_s16x1.so (casr/build.py variant "s16x1", -DCASR_S16_ONE=1), whose
  *                    s16 mode is S16X1: each build accepts F32 and its own s16 mode, and answers
  *                    the other s16 mode with CASR_ERR_UNSUPPORTED.

@@ -1,5 +1,5 @@
 """Float64 reference of every stage, and the accuracy budget built on it (test helper, not a
-conftest; used by test_accuracy_budget_host.py and test_gpu_accuracy.py).
+conftest; used by test_accuracy_budget_host.py, test_gpu_accuracy.py and test_gpu_accuracy_s16x1.py).
 
 A plain numpy float64 restatement of the reference's inference path, written from the reference
 lines each function cites, independently of oracle/casr_oracle.py (it imports nothing from it, so
@@ -9,6 +9,10 @@ stage before it, and then answers "what is this stage, evaluated exactly, on the
 float32 weights are inputs like any other.
 
 Layouts are the reference's (time-major): enc [T, B, 2H], keys [T, B, A], alignment [L, T, B].
+
+With ``sites`` the encoder, the keys and the decoder functions evaluate the exact model of the s16x1
+arithmetic instead (SITES below): both operands of each named product rounded to f16, everything
+else as before; with ``dtype=np.float32`` the float32 evaluation of the same model.
 
 budget() compares a candidate with this truth, in multiples of the error that a plain float32
 evaluation of the same stage on the same inputs (the numpy oracle) makes against it.
@@ -112,16 +116,90 @@ def _sigm(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-def _lstm_scan(gx, w_hh, b_hh, reverse):
+# The s16x1 arithmetic (the build with CASR_S16_ONE, csrc/casr_common.h:68-85) has an exact model: an
+# MFMA site keeps the hi.hi product of its split operands only, hi = (_Float16)x rounded to nearest
+# even (split16_word, casr_common.h:38-43), every f16 x f16 product is exact in f32 and the
+# accumulators are f32.  So a site computes sum_k f16(a_k) f16(b_k), and the model of a stage is the
+# stage with both operands of each such product rounded to f16.  The sites, each read from the kernel:
+#   enc_ih    encoder input projection, every layer (gemm16.hip:119, :279, :579, :798, :951; the cross
+#             MFMAs behind kS16Cross are compiled out): A is the row image of the layer input, written
+#             by features.hip:333 (layer 0) and by the recurrence from the residual sum y = h + x
+#             (recurrence.hip:354-361) for the layers after it; W_ih's image is the host's
+#             (casr_capi.hip:81-118).  The residual itself adds the unrounded f32 input.
+#   enc_hh    the recurrent product, persistent and per-step kernels alike: the hand-off granule of h
+#             is its split word (recurrence.hip:53-61), W_hh the host image.
+#   keys      enc (encoder.hip:371, :639) and W_enc.
+#   cell_emb  the embedding columns of the LSTMCell GEMM of the three-launch step: the A row is
+#             [emb16 | ctx16 | h16] (decoder.hip:131, :649 emb16, :680) against dec_w16.
+#   cell_ch   its [ctx | h] columns (the state row's split words: attention.hip:850-867 ctx,
+#             decoder.hip:773 / attention.hip:311, :417 h, decoder.hip:1173 at step 0).  The folded
+#             step's GEMM contracts the same [ctx16 | h16] with the same dec_w16 k blocks
+#             (fold_image_kernel, decoder.hip:1074-1083); its embedding part is the f32 table
+#             emb_gates (fold_emb_gates_kernel, decoder.hip:1089-1115: an fmaf chain on the f32
+#             images), which is not rounded.
+#   proj      [h | ctx] and W_p (ProjA, decoder.hip:800-808, proj_w16).  The one-accumulator form
+#             multiplies a_hi by w_hi 2^11 (decoder.hip:338-341), exact in f16 while |w| < 16: the same
+#             values.
+#   query     q = h W_hidden as an s16 MFMA: the folded beam step only (attention.hip:422-434, B
+#             operand fold_wq16_kernel, decoder.hip:1120-1130).  The three-launch step forms q from the
+#             f32 h tile and f32 W_hidden with the exact-f32 MFMA (DecLstmEpi::run, decoder.hip:781-790)
+#             and the folded greedy step with an fmaf chain (attention.hip:316-331): neither is rounded.
+# Never rounded: biases, the cell nonlinearities, scores / softmax / context (VALU f32), log-softmax,
+# the sums over steps.  A decode's step 0 is the three-launch LSTMCell and attention on every path
+# (run_greedy_fold, decoder.hip:1781: decode_step(.., proj = false)); the folded forms start at
+# step 1.  A name with "@0" holds at step 0 only, with "@1+" from step 1 on (teacher_forced).
+SITES_X1_ENCODER = frozenset({"enc_ih", "enc_hh", "keys"})
+SITES_X1_THREE_LAUNCH = frozenset({"cell_emb", "cell_ch", "proj"})
+SITES_X1_FOLD_GREEDY = frozenset({"cell_emb@0", "cell_ch", "proj"})
+SITES_X1_FOLD_BEAM = frozenset({"cell_emb@0", "cell_ch", "proj", "query@1+"})
+SITE_NAMES = frozenset({"enc_ih", "enc_hh", "keys", "cell_emb", "cell_ch", "proj", "query"})
+
+
+def round_f16(x):
+    """the s16x1 operand rounding: to f16, nearest even (split16_word's hi half)"""
+    return np.asarray(x).astype(np.float16)
+
+
+def _op(x, site, sites, dtype, weight=False):
+    """x as an operand of the product ``site``: through f16 if the site is named, widened to dtype.
+    The contracted index is x's last axis for an activation.  ``sites`` is a set of names, or (the
+    host tests' seeded defects) a dict name -> fn(x, weight) that stands in for the rounding."""
+    if sites is not None and site in sites:
+        x = sites[site](x, weight) if isinstance(sites, dict) else round_f16(x)
+    return np.asarray(x, dtype=dtype)
+
+
+def _mm(a, b):
+    """every product that is an MFMA site on the device (the host tests swap in another k order)"""
+    return a @ b
+
+
+def step_sites(sites, l):
+    """The plain site names that hold at decode step l ("@0": step 0 only, "@1+": from step 1 on);
+    a dict keeps its values"""
+    if sites is None:
+        return None
+    out = {}
+    for s in sites:
+        name, _, when = s.partition("@")
+        assert name in SITE_NAMES and when in ("", "0", "1+"), s
+        if when == "" or (when == "0") == (l == 0):
+            out[name] = sites[s] if isinstance(sites, dict) else None
+    return out if isinstance(sites, dict) else frozenset(out)
+
+
+def _lstm_scan(gx, w_hh, b_hh, reverse, sites=None, dtype=F64):
     """One direction of an nn.LSTM layer over one sequence.  gx [T, 4H] = x W_ih^T + b_ih; gate
-    order i, f, g, o; c' = f c + i g, h' = o tanh(c').  Returns (y [T, H] in time order, h, c)."""
+    order i, f, g, o; c' = f c + i g, h' = o tanh(c').  Returns (y [T, H] in time order, h, c).
+    Site enc_hh: h and W_hh of the recurrent product (the state h itself stays unrounded)."""
     T = gx.shape[0]
     H = w_hh.shape[1]
-    h = np.zeros(H)
-    c = np.zeros(H)
-    y = np.zeros((T, H))
+    w_hh = _op(w_hh, "enc_hh", sites, dtype, True)
+    h = np.zeros(H, dtype)
+    c = np.zeros(H, dtype)
+    y = np.zeros((T, H), dtype)
     for t in (range(T - 1, -1, -1) if reverse else range(T)):
-        g = gx[t] + (w_hh @ h + b_hh)
+        g = gx[t] + (_mm(w_hh, _op(h, "enc_hh", sites, dtype)) + b_hh)
         i, f, o = _sigm(g[:H]), _sigm(g[H:2 * H]), _sigm(g[3 * H:])
         c = f * c + i * np.tanh(g[2 * H:3 * H])
         h = o * np.tanh(c)
@@ -129,29 +207,34 @@ def _lstm_scan(gx, w_hh, b_hh, reverse):
     return y, h, c
 
 
-def encoder(feats, lens, enc_sd, num_layers=4, residual=True):
+def encoder(feats, lens, enc_sd, num_layers=4, residual=True, sites=None, dtype=F64):
     """RNNEncoder.forward (encoder.py:36-81) over RNN_RES.forward (util.py:1223-1324): packed
     bidirectional single-layer LSTMs (each utterance runs over exactly its own length, the
     backward direction from its own last frame), the layer input added to the layer output from
     the second layer on (util.py:1284-1291), final state = the last layer's [fw || bw]
     (encoder.py:67-72).  feats: B arrays [>= lens[b], D].  One utterance at a time, which is what
-    packing means.  Returns (enc [Tmax, B, 2H] zero past each length, h [B, 2H], c [B, 2H])."""
+    packing means.  Returns (enc [Tmax, B, 2H] zero past each length, h [B, 2H], c [B, 2H]).
+    Sites enc_ih (the layer input, for layers >= 1 the residual sum, and W_ih) and enc_hh; the
+    residual adds the unrounded input."""
     lens = [int(n) for n in lens]
     B = len(feats)
-    w = {k: _f64(v) for k, v in enc_sd.items()}
+    w = {k: np.asarray(v, dtype=dtype) for k, v in enc_sd.items()}
     H = w["rnn.rnn.0.weight_hh_l0"].shape[1]
-    enc = np.zeros((max(lens), B, 2 * H))
-    hN = np.zeros((B, 2 * H))
-    cN = np.zeros((B, 2 * H))
+    enc = np.zeros((max(lens), B, 2 * H), dtype)
+    hN = np.zeros((B, 2 * H), dtype)
+    cN = np.zeros((B, 2 * H), dtype)
+    w_ih = {k: _op(v, "enc_ih", sites, dtype, True) for k, v in w.items() if "weight_ih" in k}
     for b in range(B):
-        x = _f64(feats[b])[:lens[b]]
+        x = np.asarray(feats[b], dtype=dtype)[:lens[b]]
         for i in range(num_layers):
-            y = np.zeros((lens[b], 2 * H))
+            y = np.zeros((lens[b], 2 * H), dtype)
+            xin = _op(x, "enc_ih", sites, dtype)
             for d, suf in enumerate(("", "_reverse")):
                 p = f"rnn.rnn.{i}."
-                gx = x @ w[p + "weight_ih_l0" + suf].T + w[p + "bias_ih_l0" + suf]
+                gx = _mm(xin, w_ih[p + "weight_ih_l0" + suf].T) + w[p + "bias_ih_l0" + suf]
                 y[:, d * H:(d + 1) * H], hN[b, d * H:(d + 1) * H], cN[b, d * H:(d + 1) * H] = _lstm_scan(
-                    gx, w[p + "weight_hh_l0" + suf], w[p + "bias_hh_l0" + suf], reverse=(d == 1))
+                    gx, w[p + "weight_hh_l0" + suf], w[p + "bias_hh_l0" + suf], reverse=(d == 1), sites=sites,
+                    dtype=dtype)
             x = x + y if (residual and i > 0) else y
         enc[:lens[b], b] = x
     return enc, hN, cN
@@ -160,42 +243,71 @@ def encoder(feats, lens, enc_sd, num_layers=4, residual=True):
 # --------------------------------------------------------------------------------------
 # decoder
 # --------------------------------------------------------------------------------------
-def compute_keys(enc, dec_sd):
+def compute_keys(enc, dec_sd, sites=None, dtype=F64):
     """BauAttn.compute_key_value (attention.py:67-78): keys = enc W_enc + b_attn at every time slot
-    (a zero padding row gives exactly b_attn); the values are enc itself (map_enc False)."""
-    return _f64(enc) @ _f64(dec_sd["attn_mechanism.W_enc"]) + _f64(dec_sd["attn_mechanism.b_attn"])
+    (a zero padding row gives exactly b_attn); the values are enc itself (map_enc False).
+    Site keys: enc and W_enc."""
+    return (_mm(_op(enc, "keys", sites, dtype), _op(dec_sd["attn_mechanism.W_enc"], "keys", sites, dtype, True))
+            + np.asarray(dec_sd["attn_mechanism.b_attn"], dtype=dtype))
 
 
-def log_softmax(logit):
-    logit = _f64(logit)
+def log_softmax(logit, dtype=F64):
+    logit = np.asarray(logit, dtype=dtype)
     m = logit.max(axis=-1, keepdims=True)
     return logit - (m + np.log(np.exp(logit - m).sum(axis=-1, keepdims=True)))
 
 
-def decoder_step(enc, lens, keys, token, h, c, ctx_prev, dec_sd):
+class _Prepared(dict):
+    """the decoder's weights as decoder_step contracts them under one set of sites and one dtype"""
+
+
+def prepare_decoder(dec_sd, sites=None, dtype=F64):
+    """The weight operands of decoder_step, rounded once where their site is named (the same values
+    decoder_step forms from the plain state dict)."""
+    if isinstance(dec_sd, _Prepared):
+        return dec_sd
+    E = dec_sd["embedding.weight"].shape[1]
+    w_ih = np.asarray(dec_sd["cell.cell.0.weight_ih"], dtype=dtype)
+    if sites is not None and ("cell_emb" in sites or "cell_ch" in sites):
+        w_ih = np.concatenate([_op(w_ih[:, :E], "cell_emb", sites, dtype, True),
+                               _op(w_ih[:, E:], "cell_ch", sites, dtype, True)], axis=1)
+    f = lambda name: np.asarray(dec_sd[name], dtype=dtype)
+    return _Prepared(
+        sites=sites, dtype=dtype, emb=f("embedding.weight"), w_ih=w_ih, b_ih=f("cell.cell.0.bias_ih"),
+        w_hh=_op(dec_sd["cell.cell.0.weight_hh"], "cell_ch", sites, dtype, True), b_hh=f("cell.cell.0.bias_hh"),
+        w_hidden=_op(dec_sd["attn_mechanism.W_hidden"], "query", sites, dtype, True), v=f("attn_mechanism.v"),
+        w_p=_op(dec_sd["proj_linear.weight"], "proj", sites, dtype, True), b_p=f("proj_linear.bias"))
+
+
+def decoder_step(enc, lens, keys, token, h, c, ctx_prev, dec_sd, sites=None, dtype=F64):
     """RNNDecoder.forward (decoder.py:94-137), one step for R rows: input feeding x = [embed(token)
     || previous context], the LSTMCell (util.py:1650-1661), Bahdanau attention e_t = v . tanh(key_t
     + h W_hidden) with -inf added past each length before the softmax over time (attention.py:91-95,
     util.py:131-142), context = sum_t alpha_t enc_t, logit = proj([h || context]).
-    enc [T, R, C], keys [T, R, A], lens [R].  Returns (logit [R, V], h, c, ctx, alpha [T, R])."""
-    w = dec_sd
-    enc, keys, h, c, ctx_prev = _f64(enc), _f64(keys), _f64(h), _f64(c), _f64(ctx_prev)
+    enc [T, R, C], keys [T, R, A], lens [R].  Returns (logit [R, V], h, c, ctx, alpha [T, R]).
+    Sites (plain names, see SITES above): cell_emb, cell_ch, query, proj.  dec_sd may be the result
+    of prepare_decoder (its sites and dtype then hold)."""
+    w = prepare_decoder(dec_sd, sites, dtype)
+    sites, dtype = w["sites"], w["dtype"]
+    cast = lambda a: np.asarray(a, dtype=dtype)
+    enc, keys, h, c, ctx_prev = cast(enc), cast(keys), cast(h), cast(c), cast(ctx_prev)
     T, R, _ = enc.shape
     Hd = h.shape[1]
-    x = np.concatenate([_f64(w["embedding.weight"])[np.asarray(token)], ctx_prev], axis=1)
-    g = (x @ _f64(w["cell.cell.0.weight_ih"]).T + _f64(w["cell.cell.0.bias_ih"])
-         + h @ _f64(w["cell.cell.0.weight_hh"]).T + _f64(w["cell.cell.0.bias_hh"]))
+    x = np.concatenate([_op(w["emb"][np.asarray(token)], "cell_emb", sites, dtype),
+                        _op(ctx_prev, "cell_ch", sites, dtype)], axis=1)
+    g = (_mm(x, w["w_ih"].T) + w["b_ih"]
+         + _mm(_op(h, "cell_ch", sites, dtype), w["w_hh"].T) + w["b_hh"])
     i, f, o = _sigm(g[:, :Hd]), _sigm(g[:, Hd:2 * Hd]), _sigm(g[:, 3 * Hd:])
     c2 = f * c + i * np.tanh(g[:, 2 * Hd:3 * Hd])
     h2 = o * np.tanh(c2)
-    q = h2 @ _f64(w["attn_mechanism.W_hidden"])
-    e = np.tanh(keys + q[None]) @ _f64(w["attn_mechanism.v"])             # [T, R]
+    q = _mm(_op(h2, "query", sites, dtype), w["w_hidden"])
+    e = np.tanh(keys + q[None]) @ w["v"]                                  # [T, R]
     live = np.arange(T)[:, None] < np.asarray(lens)[None, :]
     e = np.where(live, e, -np.inf)
     p = np.exp(e - e.max(axis=0, keepdims=True))
     alpha = p / p.sum(axis=0, keepdims=True)
     ctx = np.einsum("tr,trc->rc", alpha, enc)
-    logit = np.concatenate([h2, ctx], axis=1) @ _f64(w["proj_linear.weight"]).T + _f64(w["proj_linear.bias"])
+    logit = _mm(_op(np.concatenate([h2, ctx], axis=1), "proj", sites, dtype), w["w_p"].T) + w["b_p"]
     return logit, h2, c2, ctx, alpha
 
 
@@ -222,14 +334,23 @@ def _teacher_forced(step, lsm, dtype, enc, keys, h, c, lens, targets, tgt_len, d
     return out
 
 
-def teacher_forced(enc, keys, h, c, lens, targets, tgt_len, dec_sd, sos=1, eos=2, feed_len=None):
+def teacher_forced(enc, keys, h, c, lens, targets, tgt_len, dec_sd, sos=1, eos=2, feed_len=None, sites=None,
+                   dtype=F64):
     """The decoder fed a given transcript (model.py:405-469): step l feeds sos (l = 0) or
     targets[b, l - 1], and scores targets[b, l].  Positions l >= tgt_len[b] are not scored (their
     token_logp / mean_logp / best_logp are 0); steps past feed_len[b] (default tgt_len) feed eos.
-    Returns dict(token_logp, mean_logp, best_logp [B, L], alignment [L, T, B]), float64.
-    mean_logp = (sum_v logit_v) / V - logsumexp, the label-smoothing term (util.py:265-279)."""
-    return _teacher_forced(decoder_step, log_softmax, F64, _f64(enc), _f64(keys), _f64(h), _f64(c), lens,
-                           targets, tgt_len, dec_sd, sos, eos, feed_len)
+    Returns dict(token_logp, mean_logp, best_logp [B, L], alignment [L, T, B]), of dtype.
+    mean_logp = (sum_v logit_v) / V - logsumexp, the label-smoothing term (util.py:265-279).
+    sites: one of the SITES_X1_* decode paths (names with "@0" / "@1+" hold at those steps only)."""
+    prepared = [prepare_decoder(dec_sd, step_sites(sites, l), dtype) for l in (0, 1)]
+    at = iter(range(np.asarray(targets).shape[1]))
+
+    def step(enc, lens, keys, tok, h, c, ctx, sd):
+        return decoder_step(enc, lens, keys, tok, h, c, ctx, prepared[min(next(at), 1)])
+
+    cast = lambda a: np.asarray(a, dtype=dtype)
+    return _teacher_forced(step, lambda x: log_softmax(x, dtype), dtype, cast(enc), cast(keys), cast(h), cast(c),
+                           lens, targets, tgt_len, dec_sd, sos, eos, feed_len)
 
 
 def oracle32_teacher_forced(O, enc, keys, h, c, lens, targets, tgt_len, dec_sd, sos=1, eos=2, feed_len=None):
