@@ -104,6 +104,34 @@ class Engine:
             pass
 
     # ------------------------------------------------------------------ features
+    def convert_audio(self, pcm, n_in, rate, channels=None, quantize=True, norm_db=-1.0, m_max=None):
+        """pcm [B, n_max_in, channels] (or [B, n_max_in] mono) float32, n_in [B] frames per utterance,
+        one integer rate -> (wav [B, m_max] 16 kHz mono float32, zero past n_out; n_out [B] int32;
+        gain [B]).  casr_convert_audio (include/casr.h): downmix, polyphase Kaiser-sinc resampling,
+        s16 quantisation (quantize) and peak normalisation to norm_db dBFS (>= 0: off); the
+        reference's convert_audio (main.py:19-24) without ffmpeg or sox.  Returns after enqueueing:
+        wav and n_out feed log_mel directly."""
+        pcm = torch.as_tensor(pcm).to(self.device, torch.float32)
+        if pcm.dim() == 2:
+            pcm = pcm.unsqueeze(-1)
+        if pcm.dim() != 3 or (channels is not None and pcm.shape[2] != int(channels)):
+            raise ValueError(f"convert_audio: pcm must be [B, n_max_in, channels={channels}], got {tuple(pcm.shape)}")
+        pcm = pcm.contiguous()
+        B, n_max_in, ch = pcm.shape
+        ns = torch.as_tensor(n_in).to(self.device, torch.int32).contiguous()
+        if ns.shape != (B,):
+            raise ValueError(f"convert_audio: n_in must be [B={B}]")
+        need = int(self.lib.casr_resample_frames(int(n_max_in), int(rate)))  # -1: the call below says why
+        m_max = max(need, 1) if m_max is None else int(m_max)
+        wav = torch.empty(B, m_max, device=self.device, dtype=torch.float32)
+        n_out = torch.empty(B, device=self.device, dtype=torch.int32)
+        gain = torch.empty(B, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.casr_convert_audio(self.handle, _ptr(pcm), _ptr(ns), B, n_max_in, ch, int(rate), m_max,
+                                               int(bool(quantize)), ctypes.c_float(norm_db), _ptr(wav), _ptr(n_out),
+                                               _ptr(gain), _stream()), self.handle)
+        self._keep_convert = (pcm, ns)  # read by the enqueued kernels
+        return wav, n_out, gain
+
     def log_mel(self, wav, n_samples, t_max=None, preemphasis=0.97):
         """wav [B, n_max] float32 (device), n_samples [B] int (device or host) ->
         (fbank [B, t_max, 80] log-mel, frames [B] int32).  get_log_mel data.py:167-224."""

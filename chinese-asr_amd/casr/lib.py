@@ -23,6 +23,7 @@ EXPORTS = [
     "casr_device_flags", "casr_set_persistent", "casr_recurrence_mode", "casr_log_mel",
     "casr_log_mel_frames", "casr_mel_filterbank", "casr_set_precision", "casr_get_precision",
     "casr_set_option", "casr_get_option", "casr_score",
+    "casr_convert_audio", "casr_resample_plan", "casr_resample_filter", "casr_resample_frames",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -119,6 +120,10 @@ def load(path=None, variant=None):
         "casr_profile_read": (i32, [vp, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]),
         "casr_set_option": (i32, [vp, i32, i32]),
         "casr_get_option": (i32, [vp, i32, ctypes.POINTER(ctypes.c_int32)]),
+        "casr_convert_audio": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+        "casr_resample_plan": (i32, [i32] + [ctypes.POINTER(ctypes.c_int32)] * 3),
+        "casr_resample_filter": (i32, [i32, vp]),
+        "casr_resample_frames": (i32, [i32, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -158,6 +163,32 @@ def mel_filterbank(n_stft=257, f_min=80.0, f_max=7600.0, n_mels=80):
 def log_mel_frames(n_samples):
     """Frames of log-mel an utterance of n_samples produces (0 below 513 samples)."""
     return int(load().casr_log_mel_frames(int(n_samples)))
+
+
+def resample_plan(rate):
+    """(L, M, taps) of casr_convert_audio's resampler for an input rate (include/casr.h): 16000 / g,
+    rate / g and the 2K taps of every phase.  Raises CasrError on a rate the library refuses."""
+    lib = load()
+    L, M, taps = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    check(lib.casr_resample_plan(int(rate), ctypes.byref(L), ctypes.byref(M), ctypes.byref(taps)), lib=lib)
+    return L.value, M.value, taps.value
+
+
+def resample_filter(rate):
+    """The f32 polyphase table [L, taps] casr_convert_audio applies at an input rate."""
+    lib = load()
+    L, _, taps = resample_plan(rate)
+    out = np.empty((L, taps), np.float32)
+    check(lib.casr_resample_filter(int(rate), out.ctypes.data_as(ctypes.c_void_p)), lib=lib)
+    return out
+
+
+def resample_frames(n_in, rate):
+    """16 kHz samples casr_convert_audio produces from n_in frames at a rate: ceil(n_in L / M)."""
+    n = int(load().casr_resample_frames(int(n_in), int(rate)))
+    if n < 0:
+        raise CasrError(f"casr_resample_frames({n_in}, {rate}): unsupported rate, or the count does not fit an int")
+    return n
 
 
 def config_struct(cfg):

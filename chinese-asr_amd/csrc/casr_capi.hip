@@ -169,6 +169,16 @@ struct casr_handle {
   // they cover every call since the previous read (never reset inside a captured graph)
   DevBuf gflags;
   DevBuf fe_const; // FrontendConst (filterbank, window, twiddles), built on first casr_log_mel
+  // casr_convert_audio: the f32 table of each rate seen, on host and device, built at the first call
+  // at that rate (oldest first; RS_CACHE kept), and the per-utterance peak words
+  struct ResampleTable {
+    ResamplePlan plan;
+    std::vector<float> host;  // the source of the stream-ordered upload: lives as long as the entry
+    DevBuf dev;
+  };
+  static constexpr size_t RS_CACHE = 6;
+  std::vector<ResampleTable*> rs_tables;
+  DevBuf cvt_peak;
   bool use_persistent = true;
   int precision = CASR_PREC_S16;  // requested (casr_set_precision)
   bool s16_valid = false;           // the bound blob's s16 images are usable (Layout::info)
@@ -545,8 +555,12 @@ void casr_destroy(casr_handle* h) {
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
-                    &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf})
+                    &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak})
     b->release();
+  for (casr_handle::ResampleTable* t : h->rs_tables) {
+    t->dev.release();
+    delete t;
+  }
   delete h;
 }
 
@@ -652,6 +666,128 @@ int casr_log_mel(casr_handle* h, const float* wav, const int32_t* n_samples, int
   ProfScope ps(&h->prof, CASR_K_FEATURES, s);
   HIP_OK(h, launch_log_mel(wav, n_samples, B, n_max, t_max, preemphasis, h->fe_const.as<FrontendConst>(), fbank,
                            frames, GUARD(h, 2), s, h->tune[CASR_OPT_LOGMEL_Q16]));
+  return CASR_OK;
+}
+
+// the plan of a rate, or the error casr_convert_audio and the host-only entry points report for it
+static int resample_plan_checked(casr_handle* h, const char* who, int rate_in, ResamplePlan* p) {
+  switch (resample_plan(rate_in, p)) {
+    case RS_OK: return CASR_OK;
+    case RS_BAD_RATE:
+      return fail(h, CASR_ERR_UNSUPPORTED, "%s: rate %d Hz outside [%d, %d]", who, rate_in, RS_RATE_MIN, RS_RATE_MAX);
+    default:
+      return fail(h, CASR_ERR_UNSUPPORTED,
+                  "%s: rate %d Hz needs L = %d phases x %d taps = %zu table floats > %d (M = %d)", who, rate_in, p->L,
+                  p->taps, p->table_floats(), RS_TABLE_MAX, p->M);
+  }
+}
+
+int casr_resample_plan(int rate_in, int32_t* L, int32_t* M, int32_t* taps) {
+  if (!L || !M || !taps) return fail(nullptr, CASR_ERR_ARG, "casr_resample_plan: NULL output");
+  ResamplePlan p;
+  const int rc = resample_plan_checked(nullptr, "casr_resample_plan", rate_in, &p);
+  if (rc != CASR_OK) return rc;
+  *L = p.L;
+  *M = p.M;
+  *taps = p.taps;
+  return CASR_OK;
+}
+
+int casr_resample_filter(int rate_in, float* table_host) {
+  if (!table_host) return fail(nullptr, CASR_ERR_ARG, "casr_resample_filter: NULL output");
+  ResamplePlan p;
+  const int rc = resample_plan_checked(nullptr, "casr_resample_filter", rate_in, &p);
+  if (rc != CASR_OK) return rc;
+  resample_filter(p, table_host);
+  return CASR_OK;
+}
+
+int casr_resample_frames(int n_in, int rate_in) {
+  ResamplePlan p;
+  if (resample_plan(rate_in, &p) != RS_OK) return -1;
+  const int64_t n = resample_frames(n_in, p);
+  return n > INT32_MAX ? -1 : (int)n;
+}
+
+// the handle's table of a rate: cached, or built now (host, double -> f32) and uploaded on `s`
+static int resample_table(casr_handle* h, const ResamplePlan& p, hipStream_t s, const float** tab) {
+  for (casr_handle::ResampleTable* t : h->rs_tables)
+    if (t->plan.rate == p.rate) {
+      *tab = t->dev.as<float>();
+      return CASR_OK;
+    }
+  if (h->rs_tables.size() >= casr_handle::RS_CACHE) {
+    // the oldest goes: hipFree waits for the device, so no enqueued kernel or upload still reads it
+    casr_handle::ResampleTable* old = h->rs_tables.front();
+    old->dev.release();
+    delete old;
+    h->rs_tables.erase(h->rs_tables.begin());
+  }
+  casr_handle::ResampleTable* t = new casr_handle::ResampleTable;
+  t->plan = p;
+  t->host.resize(p.table_floats());
+  resample_filter(p, t->host.data());
+  hipError_t e = t->dev.ensure(t->host.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(float), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) {
+    t->dev.release();
+    delete t;
+    return fail(h, CASR_ERR_HIP, "casr_convert_audio: table of %d Hz: %s", p.rate, hipGetErrorString(e));
+  }
+  h->rs_tables.push_back(t);
+  *tab = t->dev.as<float>();
+  return CASR_OK;
+}
+
+int casr_convert_audio(casr_handle* h, const float* pcm, const int32_t* n_in, int B, int n_max_in, int channels,
+                       int rate_in, int m_max, int quantize, float norm_db, float* wav, int32_t* n_out, float* gain,
+                       void* stream) {
+  if (!h || !pcm || !n_in || !wav || !n_out)
+    return fail(h, CASR_ERR_ARG, "casr_convert_audio: NULL handle, pcm, n_in, wav or n_out");
+  if (B <= 0 || B > 65535 || n_max_in <= 0 || m_max <= 0 || m_max > INT32_MAX - RS_TILE)
+    return fail(h, CASR_ERR_ARG, "casr_convert_audio: bad shape (B=%d n_max_in=%d m_max=%d)", B, n_max_in, m_max);
+  if (channels < 1 || channels > RS_CH_MAX)
+    return fail(h, CASR_ERR_ARG, "casr_convert_audio: %d channels not in [1, %d]", channels, RS_CH_MAX);
+  ResamplePlan p;
+  const int rc = resample_plan_checked(h, "casr_convert_audio", rate_in, &p);
+  if (rc != CASR_OK) return rc;
+  if ((int64_t)m_max < resample_frames(n_max_in, p))
+    return fail(h, CASR_ERR_ARG, "casr_convert_audio: m_max %d < %lld outputs of n_max_in %d frames at %d Hz", m_max,
+                (long long)resample_frames(n_max_in, p), n_max_in, rate_in);
+  if (resample_lds_bytes(p) > 64 * 1024 - 256)  // (the kernel's few static words on top)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_convert_audio: rate %d Hz needs %zu B of LDS per tile > 64 KiB", rate_in,
+                resample_lds_bytes(p));
+  HIP_OK(h, hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_convert_audio: guard words not allocated");
+  const bool norm = norm_db < 0.f;  // >= 0 (or NaN) switches stage (d) off
+  ConvertArgs a{};
+  a.tab = nullptr;
+  if (p.L != p.M) {
+    const int rt = resample_table(h, p, s, &a.tab);
+    if (rt != CASR_OK) return rt;
+  }
+  if (norm) HIP_OK(h, h->cvt_peak.ensure((size_t)B * RS_PEAK_STRIDE * sizeof(uint32_t)));
+  a.pcm = pcm;
+  a.n_in = n_in;
+  a.n_max_in = n_max_in;
+  a.ch = channels;
+  a.m_max = m_max;
+  a.inv_ch = 1.0f / (float)channels;
+  a.L = p.L;
+  a.M = p.M;
+  a.K = p.K;
+  a.taps = p.taps;
+  a.quantize = quantize != 0;
+  a.norm = norm;
+  a.wav = wav;
+  a.n_out = n_out;
+  a.gain = gain;
+  a.peak = h->cvt_peak.as<uint32_t>();
+  a.err = GUARD(h, 2);
+  const double lin = std::pow(10.0, (double)norm_db / 20.0);
+  const float target = norm ? (float)(a.quantize ? 32768.0 * lin : lin) : 1.f;
+  HIP_OK(h, launch_convert(a, B, p, target, s));
   return CASR_OK;
 }
 

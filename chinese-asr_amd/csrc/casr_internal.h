@@ -8,6 +8,7 @@
 
 #include "casr.h"
 #include "decode_plan.h"
+#include "resample_design.h"
 
 // the s16 arithmetic of this build (casr_common.h CASR_S16_ONE: the s16x1 build)
 #ifndef CASR_S16_ONE
@@ -27,7 +28,7 @@ constexpr int CASR_DEV_NAN_LOGITS = 4;   // no finite maximum in a logit row (gr
 constexpr int CASR_DEV_BAD_CAND = 8;     // beam candidate index not in [0, k*V)
 constexpr int CASR_DEV_BAD_BACKPTR = 16; // back-pointer walk left [0, k)
 constexpr int CASR_DEV_REC_TIMEOUT = 32; // persistent recurrence: a bounded hand-off wait expired
-constexpr int CASR_DEV_BAD_AUDIO = 64;   // front-end: n_samples < 513 (torch.stft raises) or > n_max
+constexpr int CASR_DEV_BAD_AUDIO = 64;   // front-end: n_samples < 513 (torch.stft raises) or > n_max; convert: n_in outside [0, n_max_in]
 constexpr int CASR_DEV_F16_RANGE = 128;  // s16x3 path: a finite operand beyond the f16 range (>= 65520)
 
 // MFMA-fragment-major weight block: a 16-row x 64-k tile stored as [q=0..3][lane][4] so
@@ -204,6 +205,25 @@ int frontend_frames(int n_samples);
 hipError_t launch_log_mel(const float* wav, const int32_t* nsamp, int B, int Nmax, int Tmax, float pre,
                           const FrontendConst* k, float* out, int32_t* frames, int32_t* err, hipStream_t s,
                           int form = 1);
+
+// convert.hip: casr_convert_audio's stages (a) to (d) for one batch of one format; the plan, the
+// tiling and the LDS need are resample_design.h's
+struct ConvertArgs {
+  const float* pcm;      // [B][n_max_in][ch]
+  const int32_t* n_in;   // [B]
+  int n_max_in, ch, m_max;
+  float inv_ch;          // 1 / ch rounded to f32
+  int L, M, K, taps;     // the plan (L == M: pass-through of the downmix)
+  const float* tab;      // device table [L][taps]
+  int quantize, norm;    // norm: stage (d) follows, so the peaks are reduced
+  float* wav;            // [B][m_max]
+  int32_t* n_out;        // [B]
+  float* gain;           // [B] or null
+  uint32_t* peak;        // [B] scratch (norm only): max |q|, or the bits of max |y|
+  int32_t* err;          // guard word
+};
+// target: 32768 10^(norm_db / 20) (quantize) or 10^(norm_db / 20), rounded to f32
+hipError_t launch_convert(const ConvertArgs& a, int B, const ResamplePlan& p, float target, hipStream_t s);
 
 // features.hip
 // the layer-0 s16 row image straight from fbank (features_rows_kernel<true>, T <= 1024)

@@ -74,9 +74,10 @@ class AudioBase(object):
         self.infer_wav_path_list = list(infer_paths) if infer_paths is not None else None
 
 
-def fast_read(path):
-    """data.py:109-121 (soundfile ``read(path, dtype='float32')``): mono RIFF/WAVE, integer PCM
-    scaled to [-1, 1) like libsndfile (x / 2^(bits-1); 8-bit unsigned centred) or IEEE float32."""
+def _decode_wav(path):
+    """RIFF/WAVE -> (samples as they lie in the data chunk, float32; channels; rate).  Integer PCM
+    is scaled to [-1, 1) like libsndfile (x / 2^(bits-1); 8-bit unsigned centred); IEEE float32 is
+    taken as it is."""
     with open(path, "rb") as f:
         riff = f.read()
     if riff[:4] != b"RIFF" or riff[8:12] != b"WAVE":
@@ -110,11 +111,55 @@ def fast_read(path):
         x = (np.frombuffer(data, np.uint8).astype(np.float32) - 128.0) / 128.0
     else:
         raise ValueError(f"{path}: unsupported WAVE format tag {tag}, {bits} bits")
+    return x, ch, rate
+
+
+def fast_read(path):
+    """data.py:109-121 (soundfile ``read(path, dtype='float32')``): mono RIFF/WAVE, integer PCM
+    scaled to [-1, 1) like libsndfile (x / 2^(bits-1); 8-bit unsigned centred) or IEEE float32."""
+    x, ch, rate = _decode_wav(path)
     if ch != 1:
         raise ValueError(f"{path}: {ch} channels; the path expects mono 16 kHz (main.py:22)")
     if rate != gpd['sample_rate'] and gpd['verbose']:
         print(f'[WARN] rate={rate}, dtype={x.dtype}, path={path}')  # data.py:118-119
     return x
+
+
+def read_wav(path):
+    """Any RIFF/WAVE fast_read can decode, at any rate and channel count: (frames [n, ch] float32,
+    rate).  A trailing partial frame is dropped."""
+    x, ch, rate = _decode_wav(path)
+    if ch < 1:
+        raise ValueError(f"{path}: {ch} channels")
+    n = len(x) // ch
+    return x[:n * ch].reshape(n, ch), int(rate)
+
+
+def load_audio(paths):
+    """WAV files of any rate and channel count -> list of 16 kHz mono float32 sample arrays, in the
+    order given: what ``fast_read(convert_audio(path))`` yields where ffmpeg and sox exist
+    (main.py:19-24), without them.  A 16 kHz mono file is read as fast_read reads it; every other
+    file goes through the device converter (casr_convert_audio, include/casr.h: downmix, resample,
+    s16 quantisation, -1 dB peak normalisation), one call per (rate, channels) group."""
+    out = [None] * len(paths)
+    groups = {}
+    for i, path in enumerate(paths):
+        frames, rate = read_wav(path)
+        if rate == gpd['sample_rate'] and frames.shape[1] == 1:
+            out[i] = frames[:, 0]
+        else:
+            groups.setdefault((rate, frames.shape[1]), []).append((i, frames))
+    for (rate, ch), items in groups.items():
+        n = [int(f.shape[0]) for _, f in items]
+        pcm = np.zeros((len(items), max(max(n), 1), ch), np.float32)
+        for b, (_, f) in enumerate(items):
+            pcm[b, :n[b]] = f
+        wav, n_out, _ = _engine().convert_audio(torch.from_numpy(pcm), torch.tensor(n, dtype=torch.int32), rate, ch,
+                                                quantize=True, norm_db=-1.0)
+        wav, n_out = wav.cpu().numpy(), n_out.cpu().numpy()
+        for b, (i, _) in enumerate(items):
+            out[i] = wav[b, :int(n_out[b])].copy()
+    return out
 
 
 def log_mel_batch(wavs, cmvn_eps=None):

@@ -6,8 +6,9 @@ the reference signatures and results; ``align(path, text, model, audio_base)`` i
 addition (forced alignment of a given transcript).  The chain wav -> log-mel -> delta/stack -> CMVN
 (eps 1e-6, main.py:37) -> encoder -> greedy / beam (+ second pass with a KenLM-like
 ``lm_model.score(s, bos=True)``) runs on the GPU through the casr C ABI.  Format conversion
-(``convert_audio``: ffmpeg + sox, main.py:19-24) stays an external tool: it is used when present,
-otherwise the input must already be 16 kHz mono WAV.
+(``convert_audio``: ffmpeg + sox, main.py:19-24) uses the external tools where both are present;
+without them a WAV input of any rate and channel count is converted on the device
+(``data.load_audio``: casr_convert_audio), and only a non-WAV container is refused.
 """
 import os
 import shutil
@@ -21,13 +22,13 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 from gpd import gpd  # noqa: E402
-from data import AudioBase, fast_read, log_mel_batch  # noqa: E402
+from data import AudioBase, fast_read, load_audio, log_mel_batch  # noqa: E402
 from model import Model  # noqa: E402
 
 
 def convert_audio(path):
     """main.py:19-24: ffmpeg -> 16 kHz mono s16, sox --norm=-1.  Without the tools, a WAV input is
-    used as is."""
+    returned as it is (read_audio then converts it on the device)."""
     if shutil.which("ffmpeg") and shutil.which("sox"):
         td = tempfile.mkdtemp()
         tmp, norm = os.path.join(td, "tmp.wav"), os.path.join(td, "a.wav")
@@ -40,6 +41,25 @@ def convert_audio(path):
     return path
 
 
+def have_tools():
+    return bool(shutil.which("ffmpeg") and shutil.which("sox"))
+
+
+def read_audio(paths):
+    """Paths (or sample arrays, passed through) -> 16 kHz mono float32 sample arrays.  With ffmpeg and
+    sox present: the reference's chain, file by file.  Without them: WAV files of any rate and
+    channel count through data.load_audio as one batch (a non-WAV path raises, as convert_audio does)."""
+    out = list(paths)
+    files = [i for i, p in enumerate(out) if isinstance(p, (str, os.PathLike))]
+    if have_tools():
+        for i in files:
+            out[i] = fast_read(convert_audio(out[i]))
+    elif files:
+        for i, a in zip(files, load_audio([convert_audio(os.fspath(out[i])) for i in files])):
+            out[i] = a
+    return out
+
+
 def features_for(audios):
     """Samples -> CMVN'd encoder inputs (data.py:167-253 + main.py:37), batched on the GPU.
     Returns the list-of-tensors form Model.eval_one_batch_* takes, plus lengths."""
@@ -50,8 +70,7 @@ def features_for(audios):
 
 def parse(path, model, audio_base, lm_model, bw):
     """main.py:27-65: one file -> predicted text."""
-    audio = path if not isinstance(path, (str, os.PathLike)) else fast_read(convert_audio(path))
-    data, lens = features_for([audio])
+    data, lens = features_for(read_audio([path]))
     text = None
     if bw is not None:
         if gpd['verbose']:
@@ -68,8 +87,7 @@ def align(path, text, model, audio_base):
     """Forced alignment of a known transcript: one file and its text -> [(char, start_s, logp)],
     the attention's argmax frame of each character in seconds and its teacher-forced
     log-probability (Model.score_one_batch; the closing eos is scored but not listed)."""
-    audio = path if not isinstance(path, (str, os.PathLike)) else fast_read(convert_audio(path))
-    data, lens = features_for([audio])
+    data, lens = features_for(read_audio([path]))
     res = model.score_one_batch(model.device, data, lens, [text], audio_base.word2int, audio_base.int2word)
     start = res.times['frame_s'][0]
     return [(ch, float(start[i]), float(res.token_logp[0][i])) for i, ch in enumerate(text)]
@@ -78,8 +96,7 @@ def align(path, text, model, audio_base):
 def parse_batch(paths, model, audio_base, lm_model=None, bw=None):
     """Batched form of parse (the reference's __init__.py names it but never defines it): all
     files go through the GPU path as one batch."""
-    audios = [p if not isinstance(p, (str, os.PathLike)) else fast_read(convert_audio(p)) for p in paths]
-    data, lens = features_for(audios)
+    data, lens = features_for(read_audio(paths))
     if bw is not None:
         res = model.eval_one_batch_with_beam(model.device, bw, data, lens, None, audio_base.int2word,
                                              second_pass=lm_model is not None, lm_model=lm_model,

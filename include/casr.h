@@ -132,6 +132,64 @@ int casr_log_mel_frames(int n_samples);
  * (a weight follows the last bit of the mel points).  Host only, no device needed. */
 int casr_mel_filterbank(int n_stft, float f_min, float f_max, int n_mels, float* fb_host);
 
+/* Any-rate, any-channel-count PCM -> the 16 kHz mono samples casr_log_mel takes: the reference's
+ * convert_audio (main.py:19-24: ffmpeg -sample_fmt s16 -ar 16000 -ac 1, then sox --norm=-1) on the
+ * device.  The operation is DEFINED BY THE FORMULAS BELOW, not by those tools' output: parity with
+ * swresample or sox bit for bit is not claimed (their filters differ, and sox dithers at random by
+ * default).  Per utterance, n frames of ch interleaved float32 channels at the integer rate
+ * `rate_in` go through four stages in order:
+ *  (a) downmix   x[i] = (sum_c pcm[i][c]) (1/ch): an f32 sum in ascending channel order, times 1/ch
+ *                rounded to f32 (stereo: ffmpeg's 0.5 / 0.5).  ch in 1..8.
+ *  (b) resample  polyphase windowed sinc.  g = gcd(16000, rate), L = 16000/g, M = rate/g;
+ *                c = 0.94 min(1, L/M), hw = 32/c, K = ceil(hw): 2K taps per phase.  Output m:
+ *                pos = m M (64-bit), base = pos div L, p = pos mod L,
+ *                  y[m] = sum_{j=-K+1..K} tab[p][j] x[base + j],  x = 0 outside [0, n),
+ *                one f32 fma chain in ascending j.  tab[p][j] = h_j / sum_j h_j (unit DC gain in
+ *                every phase) with u = p/L - j, sinc(t) = sin(pi t)/(pi t) and
+ *                  h(u) = c sinc(c u) I0(9 sqrt(1 - (u/hw)^2)) / I0(9) for |u| < hw, else 0,
+ *                computed in float64 on the host and rounded to f32 once.  n_out = ceil(n L / M).
+ *                rate_in = 16000 is an exact pass-through of (a): no filter, equal bit for bit.
+ *                Measured in float64 on 0.5 s tones: error against the analytic 16 kHz
+ *                tone <= -95 dB at 1, 3 and 6 kHz (-45 dB at 7 kHz, inside the 0.94 roll-off),
+ *                aliases and images <= -90 dB.
+ *  (c) quantise  (quantize != 0)  q = clamp(rint(y 32768), -32768, 32767), ties to even, NaN -> 0:
+ *                ffmpeg's -sample_fmt s16 without dither; the value passed on is q (wav = q/32768).
+ *                quantize = 0 skips the stage and y passes on.
+ *  (d) normalise (norm_db < 0; a value >= 0 switches the stage off)  peak = max_m |v_m| over the
+ *                utterance's n_out values.  quantize: g = float32(32768 10^(norm_db/20)) /
+ *                float32(peak_int), ONE correctly rounded f32 division; out_int =
+ *                clamp(rintf(float32(q) g)) (the product rounded to f32 on its own) and wav =
+ *                out_int/32768.  quantize = 0: wav = y g with g = float32(10^(norm_db/20)) / peak
+ *                (a NaN sample takes no part in the peak).  peak = 0 (silence, n = 0): g = 1.
+ *                The peak is an integer maximum (of |q|, or of the bit pattern of |y|): no float
+ *                atomics, results do not depend on scheduling.
+ *   pcm   [B][n_max_in][channels] float32, n_in [B] int32 (frames per utterance)
+ *   wav   [B][m_max] float32: exactly zero past n_out[b];  n_out [B] int32;  gain [B] g (1 with
+ *         stage (d) off), or NULL
+ * All five are device pointers; one rate_in and one channel count per call.  m_max must be >=
+ * casr_resample_frames(n_max_in, rate_in).  Returns after enqueueing, no host synchronisation: wav
+ * and n_out feed casr_log_mel directly.  Rows of pcm past n_in[b] are never read as data; an n_in[b]
+ * outside [0, n_max_in] is clamped and raises guard bit 64.  An utterance's output depends only on
+ * its own samples, n_in[b], the rate and the flags: not on B, n_max_in, m_max or its neighbours.
+ * The handle keeps the table of each rate it has seen (host and device; built and uploaded,
+ * stream-ordered, at the first call at that rate; six rates, the oldest evicted).  Not among the
+ * timed kernel classes.
+ * CASR_ERR_ARG: a NULL handle, pcm, n_in, wav or n_out, B (at most 65,535), n_max_in or m_max <= 0,
+ * channels outside 1..8, or m_max too short; CASR_ERR_UNSUPPORTED: rate_in outside [4000, 384000] or
+ * a table L x 2K of more than 65,536 floats (e.g. 44,101 Hz; casr_last_error has the numbers).
+ * Nothing is launched or written on an error. */
+int casr_convert_audio(casr_handle* h, const float* pcm, const int32_t* n_in, int B, int n_max_in,
+                       int channels, int rate_in, int m_max, int quantize, float norm_db,
+                       float* wav, int32_t* n_out, float* gain, void* stream);
+
+/* The resampler's design for a rate, host only, no device needed: L, M and the taps per phase (2K);
+ * the f32 table [L][taps] (tab[p][j] at column j + K - 1); and n_out = ceil(n_in L / M) (-1 on a rate
+ * the other two refuse, or when the count does not fit an int).  CASR_ERR_UNSUPPORTED as above,
+ * CASR_ERR_ARG for a NULL output. */
+int casr_resample_plan(int rate_in, int32_t* L, int32_t* M, int32_t* taps);
+int casr_resample_filter(int rate_in, float* table_host);
+int casr_resample_frames(int n_in, int rate_in);
+
 /* The list-of-tensors boundary of Model.eval_one_batch_* (model.py:514-516): gather B
  * device rows [lens[b]][feat_dim] (utt_ptrs is a DEVICE array of B device pointers) into
  * the padded batch-major [B][Tp][feat_dim] layout. */
@@ -214,7 +272,7 @@ int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, i
  * row, 8 beam candidate, 16 back-pointer) is clamped and reported here instead of faulting
  * the device; 32 = a bounded hand-off wait of the persistent recurrence expired (results of
  * that casr_encode are invalid); 64 = casr_log_mel got an utterance shorter than 513
- * samples or longer than n_max; 128 = s16x3 arithmetic met a finite activation beyond the f16
+ * samples or longer than n_max, or casr_convert_audio one with n_in outside [0, n_max_in]; 128 = s16x3 arithmetic met a finite activation beyond the f16
  * range (|x| >= 65520: a layer input split by the encoder), so the split images and every
  * result after them are wrong: re-run the batch with casr_set_precision(CASR_PREC_F32) (the
  * Python Model does this itself, chinese-asr_amd/casr/engine.py run_checked).

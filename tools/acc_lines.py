@@ -15,7 +15,13 @@ device's and the float64 s16x1 model's distance from the unrounded float64 stage
 float32 evaluation of that model, its table has one column pair and the cost, and it goes to
 profiles/accuracy/accuracy_budget_s16x1.json:
 
-  python tools/acc_lines.py pytest_s16x1.log profiles/accuracy/accuracy_budget_s16x1.json"""
+  python tools/acc_lines.py pytest_s16x1.log profiles/accuracy/accuracy_budget_s16x1.json
+
+A log of tests/test_gpu_convert.py has one line per (rate x channels) case of casr_convert_audio, stage
+"convert" (the arithmetic column reads f32: no MFMA is involved); its ratios are to the float32
+restatement of tests/resample_ref.py, and it goes to profiles/convert/accuracy.json:
+
+  python tools/acc_lines.py pytest_convert.log profiles/convert/accuracy.json"""
 import json
 import re
 import sys
@@ -85,6 +91,16 @@ def table(rows):
 if __name__ == "__main__":
     rows = parse(open(sys.argv[1], encoding="utf-8").read())
     x1 = bool(rows) and all(r["arithmetic"] == "s16x1" for r in rows)
+    if rows and all(r["stage"] == "convert" for r in rows):
+        if len(sys.argv) > 2:
+            with open(sys.argv[2], "w", encoding="utf-8") as f:
+                json.dump(dict(margin=8, reference="float64 (tests/resample_ref.py); ratios are to the float32 "
+                               "restatement's error on the same inputs (quantize = 0, normalisation off)",
+                               device="MI355X (gfx950)", cases=rows), f, indent=1)
+                f.write("\n")
+        for r in rows:
+            print(f"  {r['shape']:10s} max {r['max_ratio']:6.3f} rms {r['rms_ratio']:6.3f}  e_ref_max {r['e_ref_max']:.3e}")
+        sys.exit(0)
     if x1:
         if len(sys.argv) > 2:
             with open(sys.argv[2], "w", encoding="utf-8") as f:
