@@ -167,7 +167,8 @@ class BeamShardDecoder:
     casr_encode_fbank + casr_beam (model.py:604-987) and, with an LM, the finished-hypothesis
     records to the host and the second pass over them (second_pass_arrays, model.py:749-763;
     the rest keep the device's unfinished fallback / first max, :961-972), exactly as the drop-in
-    Model.eval_one_batch_with_beam does.
+    Model.eval_one_batch_with_beam does.  With a casr.ngram.NgramLM as the LM (and no rescorer) the
+    second pass runs on the device instead (casr_beam_rescore): no records leave it.
 
     A shard larger than `max_batch` utterances is decoded as consecutive batches of at most that
     many (256: the largest batch whose encoder recurrence runs persistent, one workgroup per CU;
@@ -192,6 +193,11 @@ class BeamShardDecoder:
         self.max_len = engine.cfg.max_len
         self.max_batch = int(max_batch)
         self.rescorer = rescorer  # casr.rescore.ParallelRescorer: the LM calls on host worker processes
+        # an n-gram LM of the library's own (casr.ngram.NgramLM) is rescored on the device from the beam
+        # tree (casr_beam_rescore): no record copy, no host pass.  A rescorer or keep_records asks for
+        # the host path, and any other lm_model has no other
+        from .ngram import NgramLM
+        self.device_lm = isinstance(lm_model, NgramLM) and rescorer is None and not keep_records
         self._slots = {}
         self._next = 0
         self.stats = {}
@@ -199,8 +205,12 @@ class BeamShardDecoder:
     def _batch(self, e, fbank, frames, key):
         e.encode_fbank(fbank, frames)
         r = e.beam(self.k, self.lm_weight, self.length_weight)
+        if self.device_lm:
+            steps = r["steps"]
+            r = e.beam_rescore(self.lm_model, self.lm_weight, self.length_weight)
+            r["steps"] = steps
         dev_out = [r["tokens"], r["length"], r["score"], r["steps"]]
-        if self.lm_model is not None:
+        if self.lm_model is not None and not self.device_lm:
             dev_out += list(e.beam_records())
         key = key + (tuple(tuple(x.shape) for x in dev_out),)
         bufs = self._slots.get(key)
@@ -229,7 +239,7 @@ class BeamShardDecoder:
         ev.synchronize()  # this batch only (the guard bits are the caller's: reading them syncs the stream)
         toks, blen, score, steps = (b.numpy().copy() for b in bufs[:4])
         recs = None
-        if self.lm_model is not None:
+        if self.lm_model is not None and not self.device_lm:
             rt, rs, rv = (b.numpy() for b in bufs[4:])
             if self.rescorer is not None:  # the same choice, LM calls spread over worker processes
                 best = self.rescorer.select(rt, rs, rv, self.lm_weight, self.length_weight)

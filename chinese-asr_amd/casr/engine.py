@@ -237,6 +237,40 @@ class Engine:
         _lib.check(self.lib.casr_beam_records(self.handle, _ptr(rt), _ptr(rs), _ptr(rv), _stream()), self.handle)
         return rt, rs, rv
 
+    def lm_score(self, lm, tokens, lens, bos=True):
+        """Sentence scores of an n-gram LM on the device (casr_lm_score): lm a casr.ngram.NgramLM,
+        tokens [n, L] LM ids, lens [n] -> q [n] float32, the bits NgramLM.score_ids gives on the host."""
+        dev = self.device
+        tokens = torch.as_tensor(tokens).to(dev, torch.int32).contiguous()
+        lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
+        if tokens.dim() != 2 or lens.shape != (tokens.shape[0],):
+            raise ValueError("lm_score: tokens must be [n, L] and lens [n]")
+        n, L = tokens.shape
+        q = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(self.lib.casr_lm_score(self.handle, lm.on(self), _ptr(tokens), _ptr(lens), n, L, int(bool(bos)),
+                                          _ptr(q), _stream()), self.handle)
+        self._keep_lm = (lm, tokens, lens)  # read by the enqueued kernel
+        return q
+
+    def beam_rescore(self, lm, lm_weight, length_weight, records=False):
+        """The second pass (model.py:749-763) over the last beam()'s finished hypotheses on the device
+        (casr_beam_rescore): lm a casr.ngram.NgramLM.  Returns tokens [B, max_len] (-1 past the
+        length), length [B], score [B] (the chosen record's first-pass score), lm [B] (its LM score;
+        0 where the utterance had no record and keeps beam()'s fallback), and with ``records`` rec_lm
+        [B, max_len, k], the LM score of every valid record."""
+        B, L, k = self._B, self.cfg.max_len, self._k
+        dev = self.device
+        toks = torch.empty(B, L, dtype=torch.int32, device=dev)
+        blen = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        best_lm = torch.empty(B, dtype=torch.float32, device=dev)
+        rec_lm = torch.empty(B, L, k, dtype=torch.float32, device=dev) if records else None
+        _lib.check(self.lib.casr_beam_rescore(self.handle, lm.on(self), ctypes.c_double(lm_weight),
+                                              ctypes.c_double(length_weight), _ptr(toks), _ptr(blen), _ptr(score),
+                                              _ptr(best_lm), _ptr(rec_lm), _stream()), self.handle)
+        self._keep_lm = (lm,)
+        return dict(tokens=toks, length=blen, score=score, lm=best_lm, rec_lm=rec_lm)
+
     def score(self, targets, tgt_len, alignment=False, best=False, mean=False):
         """Teacher-forced pass over the last encode (casr_score): targets [B, L] int (1 <= L <=
         max_len), tgt_len [B] scored positions per utterance.  Returns token_logp [B, L] (0 past

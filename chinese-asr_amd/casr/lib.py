@@ -24,6 +24,7 @@ EXPORTS = [
     "casr_log_mel_frames", "casr_mel_filterbank", "casr_set_precision", "casr_get_precision",
     "casr_set_option", "casr_get_option", "casr_score",
     "casr_convert_audio", "casr_resample_plan", "casr_resample_filter", "casr_resample_frames",
+    "casr_lm_create", "casr_lm_destroy", "casr_lm_score_host", "casr_lm_score", "casr_beam_rescore",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -124,6 +125,11 @@ def load(path=None, variant=None):
         "casr_resample_plan": (i32, [i32] + [ctypes.POINTER(ctypes.c_int32)] * 3),
         "casr_resample_filter": (i32, [i32, vp]),
         "casr_resample_frames": (i32, [i32, i32]),
+        "casr_lm_create": (i32, [i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]),
+        "casr_lm_destroy": (None, [vp]),
+        "casr_lm_score_host": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+        "casr_lm_score": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "casr_beam_rescore": (i32, [vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

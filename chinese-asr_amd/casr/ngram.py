@@ -1,0 +1,203 @@
+"""Backoff n-gram language model (ARPA, the text format KenLM reads) behind the casr C ABI.
+
+``read_arpa`` parses the file; ``NgramLM`` maps its words to LM ids (0 .. V - 1 the ASR token ids,
+V = <s>, V + 1 = </s>, V + 2 = <unk>), builds a host-only ``casr_lm`` and scores sentences through
+``casr_lm_score_host`` (no GPU needed), with the duck-typed ``score(sentence, bos=True)`` the
+second pass calls (casr.results.second_pass_arrays).  ``on(engine)`` gives the device copy that
+``Engine.lm_score`` and ``Engine.beam_rescore`` take.  The query is defined in include/casr.h: the
+textbook ARPA backoff query.  It should agree with KenLM to float rounding; KenLM is not available
+here, so that statement is not pinned by any test.
+"""
+import ctypes
+import os
+import re
+
+import numpy as np
+
+from . import lib as _lib
+
+BOS, EOS, UNK = "<s>", "</s>", "<unk>"
+MAX_ORDER = 4
+
+
+def read_arpa(path):
+    """Sections of an ARPA file: a list over the orders n = 1, 2, .. of (ngrams, prob, backoff) with
+    ngrams a list of n-tuples of words, prob and backoff float32 arrays (np.float32(float(text));
+    backoff 0 where the line gives none).  Fields are separated by tabs or spaces.  A count that
+    disagrees with ``\\data\\``, a malformed line or a non-finite value is a ValueError naming the line."""
+    counts, sections = {}, []
+    state, cur_n, words, prob, back = "head", 0, None, None, None
+
+    def close(no):
+        if cur_n and len(words) != counts[cur_n]:
+            raise ValueError(f"{path}:{no}: \\{cur_n}-grams: has {len(words)} n-grams, \\data\\ says {counts[cur_n]}")
+        if cur_n:
+            sections.append((words, np.array(prob, np.float32), np.array(back, np.float32)))
+
+    no = 0
+    with open(path, "r", encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            line = line.strip()
+            if not line:
+                continue
+            if state == "head":
+                if line == "\\data\\":
+                    state = "data"
+                continue  # (text before \data\ is a comment)
+            if state == "end":
+                raise ValueError(f"{path}:{no}: text after \\end\\")
+            m = re.fullmatch(r"\\(\d+)-grams:", line)
+            if m or line == "\\end\\":
+                close(no)
+                if m:
+                    n = int(m.group(1))
+                    if n != cur_n + 1 or n not in counts:
+                        raise ValueError(f"{path}:{no}: section {line} out of order or not in \\data\\")
+                    state, cur_n, words, prob, back = "grams", n, [], [], []
+                else:
+                    if cur_n != len(counts):
+                        raise ValueError(f"{path}:{no}: \\end\\ after {cur_n} of {len(counts)} sections")
+                    state, cur_n = "end", 0
+                continue
+            if state == "data":
+                m = re.fullmatch(r"ngram\s+(\d+)\s*=\s*(\d+)", line)
+                if not m or int(m.group(1)) != len(counts) + 1:
+                    raise ValueError(f"{path}:{no}: expected 'ngram {len(counts) + 1}=<count>', got {line!r}")
+                counts[len(counts) + 1] = int(m.group(2))
+                continue
+            fields = line.split()
+            if len(fields) not in (cur_n + 1, cur_n + 2):
+                raise ValueError(f"{path}:{no}: a {cur_n}-gram line has {cur_n + 1} or {cur_n + 2} fields, got {line!r}")
+            try:
+                p = np.float32(float(fields[0]))
+                b = np.float32(float(fields[cur_n + 1])) if len(fields) == cur_n + 2 else np.float32(0.0)
+            except ValueError:
+                raise ValueError(f"{path}:{no}: not a number in {line!r}") from None
+            if not (np.isfinite(p) and np.isfinite(b)):
+                raise ValueError(f"{path}:{no}: non-finite value in {line!r}")
+            words.append(tuple(fields[1:cur_n + 1]))
+            prob.append(p)
+            back.append(b)
+    if state != "end":
+        raise ValueError(f"{path}:{no}: no \\end\\ (stopped in state {state!r})")
+    if not sections:
+        raise ValueError(f"{path}: no n-gram sections")
+    return sections
+
+
+def _ptr_array(arrays, ctype):
+    """A C array of pointers to the given numpy arrays (None: NULL)."""
+    out = (ctypes.c_void_p * len(arrays))()
+    for i, a in enumerate(arrays):
+        out[i] = None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return out
+
+
+class NgramLM:
+    """NgramLM(path_or_sections, word2int, vocab): ``path_or_sections`` an ARPA file or read_arpa's
+    result; ``word2int`` the ASR vocabulary (word -> id in [0, vocab)).  <s>, </s> and <unk> map to
+    the ids vocab, vocab + 1 and vocab + 2; an n-gram with any other word outside the ASR vocabulary
+    is dropped (no hypothesis can contain it).  Orders 1..4."""
+
+    def __init__(self, path_or_sections, word2int, vocab):
+        sections = read_arpa(path_or_sections) if isinstance(path_or_sections, (str, os.PathLike)) \
+            else path_or_sections
+        self.vocab = V = int(vocab)
+        self.word2int = word2int
+        special = {BOS: V, EOS: V + 1, UNK: V + 2}
+        ids, prob, back = [], [], []
+        for n, (grams, p, b) in enumerate(sections, 1):
+            rows = np.full((len(grams), n), -1, np.int32)
+            for i, g in enumerate(grams):
+                for e, w in enumerate(g):
+                    t = special.get(w)
+                    if t is None:
+                        t = word2int.get(w, -1)
+                        t = t if 0 <= t < V else -1
+                    rows[i, e] = t
+            keep = (rows >= 0).all(axis=1)
+            ids.append(np.ascontiguousarray(rows[keep]))
+            prob.append(np.ascontiguousarray(np.asarray(p, np.float32)[keep]))
+            back.append(np.ascontiguousarray(np.asarray(b, np.float32)[keep]))
+        self._init_arrays(ids, prob, back)
+
+    @classmethod
+    def from_ids(cls, ids, prob, backoff, word2int, vocab):
+        """From LM-id arrays directly: per order n, ids[n-1] int32 [count, n], prob[n-1] and
+        backoff[n-1] float32 [count] (casr_lm_create's arguments)."""
+        self = cls.__new__(cls)
+        self.vocab, self.word2int = int(vocab), word2int
+        self._init_arrays([np.ascontiguousarray(a, np.int32).reshape(-1, n) for n, a in enumerate(ids, 1)],
+                          [np.ascontiguousarray(a, np.float32) for a in prob],
+                          [np.ascontiguousarray(a, np.float32) for a in backoff])
+        return self
+
+    def _init_arrays(self, ids, prob, back):
+        self.order = len(ids)
+        self._arrays = (ids, prob, back)
+        self._lib = _lib.load()
+        self._host = self._create(self._lib, -1)
+        self._device = {}  # (library, device index) -> casr_lm*
+
+    def _create(self, lib, device):
+        ids, prob, back = self._arrays
+        count = np.array([len(a) for a in ids], np.int64)
+        out = ctypes.c_void_p()
+        rc = lib.casr_lm_create(int(device), self.order, self.vocab, count.ctypes.data_as(ctypes.c_void_p),
+                                _ptr_array(ids, ctypes.c_int32), _ptr_array(prob, ctypes.c_float),
+                                _ptr_array(back, ctypes.c_float), ctypes.byref(out))
+        _lib.check(rc, lib=lib)
+        return out
+
+    def close(self):
+        if getattr(self, "_host", None):
+            self._lib.casr_lm_destroy(self._host)
+            self._host = None
+        for (lib, _), p in list(getattr(self, "_device", {}).items()):
+            lib.casr_lm_destroy(p)
+        self._device = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def on(self, engine):
+        """The device object for an Engine's device (uploaded once per device and library, shared by
+        every Engine there)."""
+        key = (engine.lib, engine.device.index)
+        if key not in self._device:
+            self._device[key] = self._create(engine.lib, engine.device.index)
+        return self._device[key]
+
+    # ------------------------------------------------------------------ host scoring
+    def score_ids(self, tokens, lens, bos=True):
+        """Sentence scores float32 [n] of LM-id rows tokens [n, L] with lens [n], on the host."""
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        lens = np.ascontiguousarray(lens, np.int32)
+        n, L = tokens.shape
+        q = np.empty(n, np.float32)
+        rc = self._lib.casr_lm_score_host(self._host, tokens.ctypes.data_as(ctypes.c_void_p),
+                                          lens.ctypes.data_as(ctypes.c_void_p), n, L, int(bool(bos)),
+                                          q.ctypes.data_as(ctypes.c_void_p))
+        _lib.check(rc, lib=self._lib)
+        return q
+
+    def ids_of(self, sentence):
+        """LM ids of a sentence's whitespace-separated words: the ASR id, or <unk> for a word outside
+        the ASR vocabulary.  (An ASR id the model has no unigram for scores as <unk> too, in the
+        table.)"""
+        V, w2i = self.vocab, self.word2int
+        out = []
+        for w in sentence.split():
+            t = w2i.get(w, -1)
+            out.append(t if 0 <= t < V else V + 2)
+        return out
+
+    def score(self, sentence, bos=True):
+        """log10 probability of the sentence with its closing </s>: the call the host second pass
+        makes (lm_model.score(s, bos=True), model.py:755)."""
+        ids = self.ids_of(sentence)
+        row = np.array([ids + [0] * (1 - min(len(ids), 1))], np.int32)
+        return float(self.score_ids(row, [len(ids)], bos)[0])

@@ -211,6 +211,7 @@ struct casr_handle {
   Profiler prof;
   int dec_k = 0;
   bool beam_done = false;
+  float beam_lm_weight = 0.f, beam_length_weight = 0.f;  // the last casr_beam's (casr_beam_rescore's fallback)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
   // fallback does.  Default 2: the decode loop launches eagerly (measured faster)
@@ -220,6 +221,15 @@ struct casr_handle {
   hipEvent_t ev_in = nullptr, ev_out[2] = {};
   GraphCache graphs;
   Tuning tune;  // casr_set_option
+};
+
+// An immutable backoff n-gram LM (ngram_table.h): the host tables, and for device >= 0 their copy on
+// that device, which any number of handles there may read.
+struct casr_lm {
+  int device = -1;
+  NgramTables host;
+  void* dev[2 + NGRAM_MAX_ORDER - 1] = {};  // uni, redirect, tab[0..2]
+  NgramView dview{};
 };
 
 static int fail(casr_handle* h, int code, const char* fmt, ...);
@@ -1201,6 +1211,8 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
   hipStream_t s = (hipStream_t)stream;
   h->dec_k = k;
   h->beam_done = true;
+  h->beam_lm_weight = lm_weight;
+  h->beam_length_weight = length_weight;
   if (!decode_graph_ok(h)) {
     dg_trace_init();  // CASR_DG_TRACE diagnostics only
     HIP_OK(h, run_beam(a, h->d, lm_weight, length_weight, best_tokens, best_len, best_score, steps, s));
@@ -1254,6 +1266,102 @@ int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, i
   const ScoreBufs sb = score_carve(h->scorebuf.p, h->B, L);
   HIP_OK(h, run_score(c.a, h->d, sb, targets, tgt_len, L, token_logp, total_logp, best_token, best_logp, mean_logp, align,
                       (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_lm_create(int device, int order, int vocab, const int64_t* count, const int32_t* const* ids,
+                   const float* const* prob, const float* const* backoff, casr_lm** out) {
+  if (!out) return fail(nullptr, CASR_ERR_ARG, "casr_lm_create: out is NULL");
+  *out = nullptr;
+  if (device < -1) return fail(nullptr, CASR_ERR_ARG, "casr_lm_create: device %d", device);
+  casr_lm* lm = new casr_lm();
+  std::string why;
+  const int rc = ngram_build(order, vocab, count, ids, prob, backoff, &lm->host, &why);
+  if (rc != NGRAM_OK) {
+    delete lm;
+    return fail(nullptr, rc, "casr_lm_create: %s", why.c_str());
+  }
+  lm->device = device;
+  if (device >= 0) {
+    const NgramTables& t = lm->host;
+    const void* src[5] = {t.uni.data(), t.redirect.data(), t.tab[0].data(), t.tab[1].data(), t.tab[2].data()};
+    const size_t bytes[5] = {t.uni.size() * sizeof(NgramUni), t.redirect.size() * sizeof(int32_t),
+                             t.tab[0].size() * sizeof(NgramEntry), t.tab[1].size() * sizeof(NgramEntry),
+                             t.tab[2].size() * sizeof(NgramEntry)};
+    hipError_t e = hipSetDevice(device);
+    for (int i = 0; i < 5 && e == hipSuccess; ++i) {
+      e = hipMalloc(&lm->dev[i], bytes[i]);
+      if (e == hipSuccess) e = hipMemcpy(lm->dev[i], src[i], bytes[i], hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+      casr_lm_destroy(lm);
+      return fail(nullptr, CASR_ERR_HIP, "casr_lm_create: %s", hipGetErrorString(e));
+    }
+    lm->dview = t.view();
+    lm->dview.uni = static_cast<const NgramUni*>(lm->dev[0]);
+    lm->dview.redirect = static_cast<const int32_t*>(lm->dev[1]);
+    for (int i = 0; i < NGRAM_MAX_ORDER - 1; ++i) lm->dview.tab[i] = static_cast<const NgramEntry*>(lm->dev[2 + i]);
+  }
+  *out = lm;
+  return CASR_OK;
+}
+
+void casr_lm_destroy(casr_lm* lm) {
+  if (!lm) return;
+  if (lm->device >= 0 && hipSetDevice(lm->device) == hipSuccess)
+    for (void* p : lm->dev)
+      if (p) (void)hipFree(p);
+  delete lm;
+}
+
+int casr_lm_score_host(const casr_lm* lm, const int32_t* tokens, const int32_t* lens, int n, int L, int bos,
+                       float* q) {
+  if (!lm || !lens || !q || (!tokens && L > 0) || n < 0 || L < 0)
+    return fail(nullptr, CASR_ERR_ARG, "casr_lm_score_host: NULL argument, n < 0 or L < 0");
+  for (int i = 0; i < n; ++i)
+    if (lens[i] < 0 || lens[i] > L)
+      return fail(nullptr, CASR_ERR_ARG, "casr_lm_score_host: lens[%d] = %d not in [0, %d]", i, lens[i], L);
+  const NgramView m = lm->host.view();
+  for (int i = 0; i < n; ++i) q[i] = ngram_sentence(m, tokens + (size_t)i * L, lens[i], bos != 0);
+  return CASR_OK;
+}
+
+int casr_lm_score(casr_handle* h, const casr_lm* lm, const int32_t* tokens, const int32_t* lens, int n, int L,
+                  int bos, float* q, void* stream) {
+  if (!h || !lm || !tokens || !lens || !q || n < 0 || L < 1)
+    return fail(h, CASR_ERR_ARG, "casr_lm_score: NULL argument, n < 0 or L < 1");
+  if (lm->device != h->device)
+    return fail(h, CASR_ERR_ARG, "casr_lm_score: the LM is %s, the handle on device %d",
+                lm->device < 0 ? "host-only" : "on another device", h->device);
+  if (lm->host.V != h->cfg.vocab)
+    return fail(h, CASR_ERR_ARG, "casr_lm_score: the LM's vocab %d is not the handle's %d", lm->host.V, h->cfg.vocab);
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_lm_score: no guard words");
+  int32_t* err = GUARD(h, 0);
+  HIP_OK(h, launch_lm_score(lm->dview, tokens, lens, n, L, bos != 0, q, err, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, double length_weight,
+                      int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm, float* rec_lm,
+                      void* stream) {
+  if (!h || !lm || !best_tokens || !best_len || !best_score)
+    return fail(h, CASR_ERR_ARG, "casr_beam_rescore: NULL handle, LM or output");
+  if (!h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_rescore before casr_beam");
+  if (lm->device != h->device)
+    return fail(h, CASR_ERR_ARG, "casr_beam_rescore: the LM is %s, the handle on device %d",
+                lm->device < 0 ? "host-only" : "on another device", h->device);
+  if (lm->host.V != h->cfg.vocab)
+    return fail(h, CASR_ERR_ARG, "casr_beam_rescore: the LM's vocab %d is not the handle's %d", lm->host.V,
+                h->cfg.vocab);
+  if (!rescore_supported(h->cfg.max_len, h->dec_k))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_rescore: max_len %d x k %d past the LDS", h->cfg.max_len, h->dec_k);
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  if (rc) return rc;
+  HIP_OK(h, run_beam_rescore(c.a, h->d, lm->dview, lm_weight, length_weight, h->beam_lm_weight, h->beam_length_weight,
+                             best_tokens, best_len, best_score, best_lm, rec_lm, (hipStream_t)stream));
   return CASR_OK;
 }
 

@@ -8,6 +8,7 @@
 
 #include "casr.h"
 #include "decode_plan.h"
+#include "ngram_table.h"
 #include "resample_design.h"
 
 // the s16 arithmetic of this build (casr_common.h CASR_S16_ONE: the s16x1 build)
@@ -454,5 +455,17 @@ hipError_t score_project(const DecodeArgs& a, const DecodeBufs& d, const ScoreBu
 hipError_t run_score(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, const int32_t* targets,
                      const int32_t* tgt_len, int L, float* token_logp, float* total_logp, int32_t* best_token,
                      float* best_logp, float* mean_logp, float* align, hipStream_t s);
+
+// ngram.hip: the backoff n-gram LM on the device (ngram_table.h's query).  m holds device pointers.
+// Sentence scores q [n] of tokens [n][L] (LM ids) with lens [n]
+hipError_t launch_lm_score(const NgramView& m, const int32_t* tokens, const int32_t* lens, int n, int L, int bos,
+                           float* q, int32_t* err, hipStream_t s);
+// the second pass over the beam state run_beam left in d (one workgroup per utterance); the beam
+// weights are casr_beam's own, for its unfinished fallback.  rescore_supported: its LDS fits
+bool rescore_supported(int max_len, int k);
+hipError_t run_beam_rescore(const DecodeArgs& a, const DecodeBufs& d, const NgramView& m, double lm_weight,
+                            double length_weight, float beam_lm_weight, float beam_length_weight,
+                            int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
+                            float* rec_lm, hipStream_t s);
 
 }  // namespace casr

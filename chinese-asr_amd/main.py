@@ -109,8 +109,13 @@ def parse_batch(paths, model, audio_base, lm_model=None, bw=None):
 class ASR:
     """main.py:68-102."""
 
-    def __init__(self, lm_path=None, bw=None, ckpt='./pretrain-0.06328.ckpt'):
-        if lm_path is not None and bw is not None and bw > 1:
+    def __init__(self, lm_path=None, bw=None, ckpt='./pretrain-0.06328.ckpt', lm_backend="kenlm"):
+        """lm_backend "kenlm" (default: the reference's import) or "casr": the library's own ARPA
+        n-gram LM (casr.ngram.NgramLM), rescored on the device."""
+        if lm_backend not in ("kenlm", "casr"):
+            raise ValueError(f"lm_backend must be 'kenlm' or 'casr', got {lm_backend!r}")
+        want_lm = lm_path is not None and bw is not None and bw > 1
+        if want_lm and lm_backend == "kenlm":
             import kenlm  # third-party (model.py:13); absent here -> ImportError like the reference
             print('loading language model...')
             ts = time()
@@ -122,6 +127,12 @@ class ASR:
         model.load(ckpt)
         model.model.eval()
         self.audio_base = AudioBase()
+        if want_lm and lm_backend == "casr":
+            from casr.ngram import NgramLM
+            print('loading language model...')
+            ts = time()
+            lm_model = NgramLM(lm_path, self.audio_base.word2int, model.cfg.vocab)
+            print('loading cost %.3fs' % (time() - ts))
         self.lm_model = lm_model
         self.model = model
         self.bw = bw

@@ -13,6 +13,7 @@ from gpd import gpd
 from casr.config import config_from_gpd
 from casr.engine import Engine
 from casr.lib import pack_weights
+from casr.ngram import NgramLM
 from casr.results import (EvalOutput, ScoreOutput, encode_targets, get_wer, greedy_outputs, greedy_steps,
                           label_smoothed_loss, score_outputs, second_pass_arrays, token_times)
 from casr.vocab import load_vocab
@@ -132,7 +133,16 @@ class Model(object):
                                  lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight']):
         """model.py:604-987."""
         self.model.eval()
-        bsz, _, r = self._run(data, lens, lambda: self.engine.beam(bmsz, lm_weight, length_weight))
+        # an NgramLM (casr/ngram.py) is rescored on the device from the beam tree: no record copy and
+        # no host pass; any other lm_model keeps the host second pass below
+        on_device = bool(second_pass) and isinstance(lm_model, NgramLM)
+
+        def decode():
+            r = self.engine.beam(bmsz, lm_weight, length_weight)
+            return self.engine.beam_rescore(lm_model, lm_weight, length_weight) if on_device else r
+
+        bsz, _, r = self._run(data, lens, decode)
+        second_pass = second_pass and not on_device
         toks = r['tokens'].cpu().numpy()
         blen = r['length'].cpu().numpy()
         bscore = r['score'].cpu().numpy()

@@ -266,6 +266,81 @@ int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, i
                float* token_logp, float* total_logp, int32_t* best_token, float* best_logp,
                float* mean_logp, float* align, void* stream);
 
+/* A backoff n-gram language model (ARPA, the text format KenLM reads) for sentence scoring and for the
+ * second pass of Model.eval_one_batch_with_beam (parse_finished_tensors, model.py:749-763; main.py:79-85)
+ * on the device.  The operation is DEFINED BY THE FORMULAS BELOW: the textbook ARPA backoff query, which
+ * is what KenLM evaluates.  Agreement with KenLM to float rounding is expected but NOT PINNED (KenLM is
+ * not available to test against); parity bit for bit is not claimed.
+ *   Model     order N in 1..4.  LM ids: 0 .. V - 1 the ASR token ids (V = cfg.vocab), V = <s>,
+ *             V + 1 = </s>, V + 2 = <unk>.  Each n-gram of each order has prob (log10, f32) and backoff
+ *             (f32; 0 where none is given; the top order has none).  An id with no unigram scores and
+ *             matches as <unk>: it is redirected to V + 2 in every lookup, context positions included
+ *             (the n-grams themselves are stored as given).  Without a <unk> unigram, <unk> is
+ *             (prob -100, backoff 0), KenLM's default.
+ *   Word      ctx = the up to N - 1 LM ids before w (starting with <s> under bos).  m = the largest
+ *             order whose n-gram (ctx[-(m-1):], w) is in the model (the unigram always is); p = prob_m;
+ *             then for j = m, m + 1, .., len(ctx) in that order: where ctx[-j:] is in the model as a
+ *             j-gram, p = p + backoff(ctx[-j:]).  Every operation an f32 add, in that order.
+ *   Sentence  q = (..((t_1 + t_2) + t_3).. + t_n) + t_eos: t_i the term of word i, t_eos that of </s>
+ *             after the last words; f32 adds, ascending, t_1 taken as is.  bos = 0 starts from an empty
+ *             context instead of <s>.
+ * casr_lm_create builds the tables from HOST arrays, per order n = 1..order: count[n-1] n-grams,
+ * ids[n-1] [count][n] int32 LM ids, prob[n-1] [count], backoff[n-1] [count] (NULL: zeros; the top
+ * order's is not read).  Unigrams are a direct array [V + 3]; orders 2..4 open-addressing tables with
+ * linear probing of 16-byte entries {uint64 key, f32 prob, f32 backoff}, capacity the power of two
+ * >= 2 count; the key packs id + 1 of each word into a 16-bit field (exact, never 0; 0 = empty) and the
+ * slot is the splitmix64 finaliser of the key, masked (csrc/ngram_table.h).  device >= 0 also uploads
+ * the tables to that device (synchronously); device = -1 makes a host-only object: nothing is uploaded
+ * and no GPU is needed.  The object is immutable: any number of handles on its device may share it,
+ * from any thread.  It must outlive the work enqueued with it.
+ * CASR_ERR_UNSUPPORTED: order > 4, or V + 3 > 65535.  CASR_ERR_ARG: order < 1, a NULL array, a duplicate
+ * n-gram, an id outside [0, V + 3), a non-finite value (casr_last_error(NULL) says which). */
+typedef struct casr_lm casr_lm;
+int casr_lm_create(int device, int order, int vocab, const int64_t* count, const int32_t* const* ids,
+                   const float* const* prob, const float* const* backoff, casr_lm** out);
+void casr_lm_destroy(casr_lm* lm);
+
+/* Sentence scores q [n] of tokens [n][L] (LM ids; lens [n] words each, 0..L).  An id outside
+ * [0, V + 3) scores as <unk>.
+ * casr_lm_score_host: every pointer a HOST pointer, any LM object, no GPU; CASR_ERR_ARG for a NULL
+ * argument or a length outside [0, L].
+ * casr_lm_score: every pointer a DEVICE pointer; one work item per (sentence, position) computes the
+ * terms, then one per sentence adds them in ascending order: the host's bits.  An id outside
+ * [0, V + 3), or a length outside [0, L] (clamped), raises guard bit 1.  L >= 1.  Returns after
+ * enqueueing.  CASR_ERR_ARG: a NULL argument, an LM that is host-only or on another device, or whose
+ * vocab is not the handle's.  Needs no weights and no encode.  Nothing is launched or written on an
+ * error. */
+int casr_lm_score_host(const casr_lm* lm, const int32_t* tokens, const int32_t* lens, int n, int L, int bos,
+                       float* q);
+int casr_lm_score(casr_handle* h, const casr_lm* lm, const int32_t* tokens, const int32_t* lens, int n, int L,
+                  int bos, float* q, void* stream);
+
+/* The second pass (model.py:749-763) over the finished hypotheses of the last casr_beam, on the
+ * device, from the beam tree the handle still holds: no record is expanded and nothing is copied to the
+ * host.  Per utterance, over its valid records in (step, rank) order, with l the record's length, q its
+ * sentence score under bos and rec_score its first-pass score:
+ *     comb = (double(rec_score) + lm_weight double(q)) + length_weight double(l),
+ * each operation one IEEE double operation (never contracted), as the host path evaluates it on Python
+ * floats.  The choice is the first maximum; if a comb is NaN the first NaN (np.argmax's rule).  An
+ * utterance with no record keeps casr_beam's unfinished fallback (its own weights), bit for bit.
+ *   best_tokens [B][max_len] (-1 past the length), best_len [B], best_score [B] = the chosen record's
+ *   rec_score (not comb, as the host path returns)
+ *   best_lm  NULL or [B]: q of the choice, 0 where the utterance has no record
+ *   rec_lm   NULL or [B][max_len][k]: q of every valid record, 0 elsewhere
+ * A word's term depends only on its at most 3 predecessors, so it is computed once per beam-tree node
+ * (at most steps x k per utterance) and summed down the tree in f32, ascending: the sentence sum's
+ * bits.  One workgroup per utterance; no float atomics; the handle's beam state is only read, so a
+ * later casr_beam_records, or a second rescore, gives the same bits.  A token id outside [0, V) scores
+ * as <unk> (guard bit 1); a back-pointer outside [0, k) is clamped (guard bit 16).  Never replayed as a
+ * hipGraph and not among the timed kernel classes.  Returns after enqueueing.
+ * CASR_ERR_STATE before casr_beam; CASR_ERR_ARG: a NULL handle, LM or required output, an LM that is
+ * host-only or on another device, or whose vocab is not the handle's; CASR_ERR_UNSUPPORTED: a max_len x
+ * k whose tree does not fit the LDS (64 KB: 16 max_len k + 3 KB).  Nothing is launched or written on an
+ * error. */
+int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, double length_weight,
+                      int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
+                      float* rec_lm, void* stream);
+
 /* Guard bits raised by the device since the previous casr_device_flags call (read and clear;
  * they accumulate over every encode / decode / log-mel call in between, so one read after a
  * series of calls vouches for all of them; 0 = clean): a data-dependent index out of range (1 token, 2 predecessor row, 4 NaN logit
