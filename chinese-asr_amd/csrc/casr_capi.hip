@@ -157,6 +157,7 @@ struct casr_handle {
   casr_config cfg{};
   Layout L{};
   int device = 0;
+  DeviceFacts dev{};  // of `device`, read at casr_create (plan_encode's input)
   const float* W = nullptr;
   std::string err;
   // encoder workspace
@@ -467,6 +468,18 @@ int casr_create(const casr_config* cfg, int device, casr_handle** out) {
   h->cfg = *cfg;
   h->L = make_layout(*cfg);
   h->device = device;
+  // the device's facts, once per handle; the caller's current device is restored
+  int cur = -1;
+  e = hipGetDevice(&cur);
+  if (e == hipSuccess) e = hipSetDevice(device);
+  if (e == hipSuccess) {
+    h->dev = read_device_facts();
+    if (cur != device) e = hipSetDevice(cur);
+  }
+  if (e != hipSuccess) {
+    delete h;
+    return fail(nullptr, CASR_ERR_HIP, "casr_create: device %d: %s", device, hipGetErrorString(e));
+  }
   *out = h;
   return CASR_OK;
 }
@@ -587,17 +600,10 @@ int casr_set_persistent(casr_handle* h, int enable) {
   return CASR_OK;
 }
 
+// (the persistent recurrence needs every workgroup of its grid resident at once: plan_recurrence)
 int casr_recurrence_mode(const casr_handle* h, int B) {
   if (!h || B <= 0) return -1;
-  if (!h->use_persistent) return 0;
-  // the persistent recurrence needs every workgroup of its grid resident at once; the occupancy
-  // query runs on the handle's device, and the caller's current device is restored
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess) return 0;
-  if (cur != h->device && hipSetDevice(h->device) != hipSuccess) return 0;
-  const int fits = rec_layer_fits(B, rec_layout(B, h->tune)) ? 1 : 0;
-  if (cur != h->device) (void)hipSetDevice(cur);
-  return fits;
+  return plan_recurrence(B, 1, h->tune, h->s16(), false, h->use_persistent, h->dev).persistent;
 }
 
 int casr_set_option(casr_handle* h, int option, int value) {
@@ -636,7 +642,8 @@ int casr_features(casr_handle* h, const float* fbank, const int32_t* frames, int
   HIP_OK(h, hipSetDevice(h->device));
   ProfScope ps(&h->prof, CASR_K_FEATURES, (hipStream_t)stream);
   HIP_OK(h, h->fstat.ensure((size_t)B * 2 * D * sizeof(float)));
-  HIP_OK(h, launch_features(fbank, frames, B, T, eps, feat, feat_len, h->fstat.as<float>(), (hipStream_t)stream));
+  HIP_OK(h, launch_features(feature_path(T, false), fbank, frames, B, T, eps, feat, feat_len, h->fstat.as<float>(),
+                            (hipStream_t)stream));
   return CASR_OK;
 }
 
@@ -811,112 +818,114 @@ int casr_gather_utterances(casr_handle* h, const float* const* utt_ptrs, const i
 }
 
 // The encoder.  fb != nullptr (casr_encode_fbank): the inputs are fbank [B][T][n_mels] + frames
-// and the features are computed here (s16x3: straight into the layer-0 row image); otherwise
-// feat [B][Tp][feat_dim] + lens.
+// and the features are computed here (s16x3: straight into the layer-0 image); otherwise
+// feat [B][Tp][feat_dim] + lens.  Every path decision is the plan's (encode_plan.h plan_encode); the
+// one runtime event is a refused cooperative launch, after which `persistent` is off.
 static int encode_impl(casr_handle* h, const float* feat, const int32_t* lens, int B, int Tp, hipStream_t s,
                        const float* fb = nullptr, const int32_t* frames = nullptr, int T = 0, float eps = 0.f) {
-  const size_t rows = (size_t)B * Tp;
-  HIP_OK(h, h->gin.ensure(rows * 8 * H * sizeof(float)));
-  HIP_OK(h, h->out0.ensure(rows * C * sizeof(float)));
-  HIP_OK(h, h->out1.ensure(rows * C * sizeof(float)));
-  HIP_OK(h, h->hbuf.ensure((size_t)2 * 2 * B * H * sizeof(float)));
-  HIP_OK(h, h->cst.ensure((size_t)2 * B * H * sizeof(float)));
-  HIP_OK(h, h->hfin.ensure((size_t)2 * B * H * sizeof(float)));
-  const int Tq = attn_tq(Tp);  // keysT row stride (16 B aligned rows for the attention)
-  HIP_OK(h, h->keysT.ensure(2 * (size_t)B * A * Tq * sizeof(float)));  // [keys | exp(2 keys)] (KeysEpi)
-  HIP_OK(h, h->lens.ensure((size_t)B * sizeof(int32_t)));
-  if (!fb) HIP_OK(h, hipMemcpyAsync(h->lens.p, lens, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
-  const int layout = rec_layout(B, h->tune);
-  bool persistent = casr_recurrence_mode(h, B) == 1;
-  if (!persistent) {  // the persistent recurrence writes the padded frames itself
-    HIP_OK(h, hipMemsetAsync(h->out0.p, 0, rows * C * sizeof(float), s));
-    HIP_OK(h, hipMemsetAsync(h->out1.p, 0, rows * C * sizeof(float), s));
+  const EncodePlan plan = plan_encode(B, Tp, T, fb != nullptr, h->cfg, h->tune, h->s16(), h->use_persistent, h->dev);
+  switch (plan.status) {
+    case ENC_BAD_SHAPE: return fail(h, CASR_ERR_ARG, "encode: bad shape (B=%d Tp=%d)", B, Tp);
+    case ENC_KEYS_OFFSET:
+      return fail(h, CASR_ERR_UNSUPPORTED, "encode: keys of B=%d Tp=%d are past the row-streaming form's 32-bit offsets", B, Tp);
+    case ENC_KM_FORM: return fail(h, CASR_ERR_UNSUPPORTED, "encode: a 16-k-major image with a row-image kernel form");
+    default: break;
   }
+  const RecPlan& rec = plan.rec;
+  const EncodeSizes size = encode_sizes(plan);
+  HIP_OK(h, h->gin.ensure(size.gin));
+  HIP_OK(h, h->out0.ensure(size.out));
+  HIP_OK(h, h->out1.ensure(size.out));
+  HIP_OK(h, h->hbuf.ensure(size.hbuf));
+  HIP_OK(h, h->cst.ensure(size.cst));
+  HIP_OK(h, h->hfin.ensure(size.hfin));
+  HIP_OK(h, h->keysT.ensure(size.keysT));
+  HIP_OK(h, h->lens.ensure(size.lens));
+  // (the guard words, allocated at their first use, keep their place in the allocation order: the
+  // hand-off buffer's address after them is the one the recurrence was tuned and measured at)
   if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_encode: guard words not allocated");
   int32_t* eflag = GUARD(h, 1);
+  HIP_OK(h, h->x16.ensure(size.x16));
+  HIP_OK(h, h->hx.ensure(size.hx));
+  HIP_OK(h, h->fstat.ensure(size.fstat));
+  HIP_OK(h, h->feat.ensure(size.feat));
+  if (!fb) HIP_OK(h, hipMemcpyAsync(h->lens.p, lens, size.lens, hipMemcpyDeviceToDevice, s));
+  bool persistent = rec.persistent;
+  if (!persistent) {  // the persistent recurrence writes the padded frames itself
+    HIP_OK(h, hipMemsetAsync(h->out0.p, 0, size.out, s));
+    HIP_OK(h, hipMemsetAsync(h->out1.p, 0, size.out, s));
+  }
   {  // final h
     FillList fl;
-    fl.add32(h->hfin.p, 0u, (size_t)2 * B * H);
+    fl.add32(h->hfin.p, 0u, size.hfin / sizeof(float));
     HIP_OK(h, fill_multi(fl, s));
   }
-  const bool s16 = h->s16();
-  // the layer-input images 16-k-block major (CASR_OPT_X16_KM and the GEMM / keys forms that read them)
-  const int km = s16 && x16_km(h->tune) ? 1 : 0;
-  if (s16) HIP_OK(h, h->x16.ensure(rows * s16_kpad(D) * sizeof(float)));
-  if (persistent) HIP_OK(h, h->hx.ensure(rec_layer_granule_bytes(B, layout)));
+  const bool s16 = plan.s16;
   const int32_t* dl = h->lens.as<int32_t>();
   float* outs[2] = {h->out0.as<float>(), h->out1.as<float>()};
-  bool x16_ready = false;
   if (fb) {
     ProfScope ps(&h->prof, CASR_K_FEATURES, s);
-    HIP_OK(h, h->fstat.ensure((size_t)B * 2 * D * sizeof(float)));
-    if (s16 && features_x16_supported(T)) {
-      HIP_OK(h, launch_features_x16(fb, frames, B, T, eps, h->lens.as<int32_t>(), h->fstat.as<float>(),
-                                    h->x16.as<uint16_t>(), s16_kpad(D),
-                                    eflag, s, km));
-      x16_ready = true;  // feat stays NULL: layer 0 reads only the image (no residual input)
+    if (plan.feat == FEAT_IMAGE) {  // feat stays NULL: layer 0 reads only the image (no residual input)
+      HIP_OK(h, launch_features_x16(plan, fb, frames, T, eps, h->lens.as<int32_t>(), h->fstat.as<float>(),
+                                    h->x16.as<uint16_t>(), eflag, s));
     } else {
-      HIP_OK(h, h->feat.ensure(rows * D * sizeof(float)));
-      HIP_OK(h, launch_features(fb, frames, B, T, eps, h->feat.as<float>(), h->lens.as<int32_t>(), h->fstat.as<float>(), s));
+      HIP_OK(h, launch_features(plan.feat, fb, frames, B, T, eps, h->feat.as<float>(), h->lens.as<int32_t>(),
+                                h->fstat.as<float>(), s));
       feat = h->feat.as<float>();
     }
   }
   const float* x = feat;
   float* hb = h->hbuf.as<float>();
-  // s16: a persistent layer writes the next layer's input row image itself (no split pass)
-  bool fell_back = false;  // a cooperative persistent launch was refused: per-step from here on
-  for (int l = 0; l < h->cfg.enc_layers; ++l) {
-    const int din = l == 0 ? D : C;
+  for (int l = 0; l < plan.layers; ++l) {
+    const InputGemmPlan& g = plan.layer_gemm(l);
     float* out = outs[l & 1];
     {
     ProfScope ps(&h->prof, CASR_K_INPUT_PROJ, s);
     if (s16) {
-      const int kp = s16_kpad(din);
-      if (!x16_ready)
-        HIP_OK(h, launch_split_rows(x, din, (int)rows, din, kp, h->x16.as<uint16_t>(), eflag, s, km));
-      HIP_OK(h, launch_input_proj_s16_big(h->x16.as<float>(), (int)rows, kp,
-                                          km ? h->wih16km.as<float>() + h->wih16km_off[l] : h->W + h->L.enc_wih16[l],
-                                          h->W + h->L.enc_bias[l], h->gin.as<float>(), s, din,
-                                          h->tune[CASR_OPT_GEMM16_PERSIST], h->tune[CASR_OPT_GEMM16_TAIL], km,
-                                          h->tune[CASR_OPT_GEMM16_LEAN]));
+      // the layer input's image: layer 0's from the features kernel, a later layer's from the
+      // persistent layer before it (no split pass)
+      const bool have_image = l == 0 ? plan.feat == FEAT_IMAGE : persistent;
+      if (!have_image)
+        HIP_OK(h, launch_split_rows(x, g.K, plan.M, g.K, g.Kp, h->x16.as<uint16_t>(), eflag, s, plan.km));
+      HIP_OK(h, launch_input_proj_s16_big(g, h->x16.as<float>(),
+                                          plan.km ? h->wih16km.as<float>() + h->wih16km_off[l] : h->W + h->L.enc_wih16[l],
+                                          h->W + h->L.enc_bias[l], h->gin.as<float>(), s));
     } else {
-      HIP_OK(h, launch_input_proj(x, (int)rows, din, h->W + h->L.enc_wih[l], h->W + h->L.enc_bias[l],
+      HIP_OK(h, launch_input_proj(x, plan.M, g.K, h->W + h->L.enc_wih[l], h->W + h->L.enc_bias[l],
                                   h->gin.as<float>(), s));
     }
     }
-    const int residual = (h->cfg.residual && l > 0) ? 1 : 0;
+    const int residual = plan.residual && l > 0;
     // layer 0 has no residual input: pass an internal pointer so a graph never bakes in the
     // caller's feature buffer
     const float* xin = residual ? x : out;
     const float* whh = h->W + (s16 ? h->L.enc_whh16[l] : h->L.enc_whh[l]);
+    x = out;
     if (persistent) {
       // one launch runs all Tp steps; h and c start at zero inside (util.py:1236-1247)
-      HIP_OK(h, reset_rec_layer(reinterpret_cast<uint32_t*>(h->hx.p), B, layout, s));
+      HIP_OK(h, reset_rec_layer(rec, h->hx.as<uint32_t>(), s));
       // diagnostics only: CASR_REC_TRACE=<file> dumps per-wave phase timestamps of layer 0
       const char* trace_path = l == 0 ? std::getenv("CASR_REC_TRACE") : nullptr;
       DevBuf tbuf;
-      const size_t tbytes = (size_t)rec_layer_grid_blocks(B, layout) * rec_layer_waves(layout) * Tp * 5 * sizeof(uint32_t);
+      const size_t tbytes = (size_t)rec.grid * rec.waves() * Tp * 5 * sizeof(uint32_t);
       if (trace_path) {
         HIP_OK(h, tbuf.ensure(tbytes));
         HIP_OK(h, hipMemsetAsync(tbuf.p, 0, tbytes, s));
       }
       hipError_t er;
-      if (h->tune[CASR_OPT_REC_COOP_REFUSE] == l + 1) {
+      if (rec.refuse == l + 1) {
         er = hipErrorCooperativeLaunchTooLarge;  // tests only: this layer's launch "refused"
       } else {
         ProfScope ps(&h->prof, CASR_K_REC_STEP, s);
-        // the last layer's image feeds the keys GEMM
-        uint16_t* x16o = s16 ? h->x16.as<uint16_t>() : nullptr;
-        er = launch_rec_layer(whh, h->gin.as<float>(), xin, out, x16o, reinterpret_cast<uint32_t*>(h->hx.p),
-                              h->hfin.as<float>(), h->cst.as<float>(), dl, B, Tp, residual, s16,
-                              eflag, tbuf.as<uint32_t>(), layout, h->tune, s, km);
+        // (s16: the image of the layer's output, the last layer's feeds the keys GEMM)
+        er = launch_rec_layer(rec, whh, h->gin.as<float>(), xin, out, s16 ? h->x16.as<uint16_t>() : nullptr, h->hx.as<uint32_t>(),
+                              h->hfin.as<float>(), h->cst.as<float>(), dl, residual, eflag, tbuf.as<uint32_t>(), s);
       }
       if (er == hipErrorCooperativeLaunchTooLarge) {
         // the device cannot hold the whole grid at once (e.g. CUs taken by other work): this layer
         // and the next ones run the per-step recurrence (same bits) instead of spinning
         (void)hipGetLastError();
         persistent = false;
-        fell_back = true;
       } else {
         HIP_OK(h, er);
       }
@@ -926,25 +935,21 @@ static int encode_impl(casr_handle* h, const float* feat, const int32_t* lens, i
         HIP_OK(h, hipStreamSynchronize(s));
         tbuf.release();
         if (FILE* f = std::fopen(trace_path, "wb")) {
-          const int32_t hdr[5] = {rec_layer_grid_blocks(B, layout), rec_layer_waves(layout), Tp, 5,
-                                  rec_layer_producers(layout)};
+          const int32_t hdr[5] = {rec.grid, rec.waves(), Tp, 5, rec.producers()};
           std::fwrite(hdr, sizeof hdr, 1, f);
           std::fwrite(hostv.data(), 4, hostv.size(), f);
           std::fclose(f);
         }
       }
-      if (persistent) {
-        x = out;
-        x16_ready = s16;
-        continue;
-      }
+      if (persistent) continue;
     }
-    x16_ready = false;
     // the persistent layers write their padded frames themselves; the per-step ones need zeros
-    if (fell_back) HIP_OK(h, hipMemsetAsync(out, 0, rows * C * sizeof(float), s));
+    if (rec.persistent) HIP_OK(h, hipMemsetAsync(out, 0, size.out, s));
     // h (both ping-pong buffers) and c start at zero (RNN_RES state None, util.py:1236-1247)
-    HIP_OK(h, fill_u32(hb, 0, (size_t)2 * 2 * B * H, s));
-    HIP_OK(h, fill_u32(h->cst.p, 0, (size_t)2 * B * H, s));
+    HIP_OK(h, fill_u32(hb, 0, size.hbuf / sizeof(float), s));
+    HIP_OK(h, fill_u32(h->cst.p, 0, size.cst / sizeof(float), s));
+    // every buffer the step loop is handed: the launch arguments and the pointer part of its graphs' key
+    const void* const buf[] = {whh, h->gin.p, xin, out, hb, h->cst.p, h->hfin.p, dl};
     auto rec_loop = [&](hipStream_t st, Profiler* prof, int r0, int r1) -> hipError_t {
       hipError_t e = hipSuccess;
       for (int step = 0; step < Tp && e == hipSuccess; ++step) {
@@ -957,41 +962,30 @@ static int encode_impl(casr_handle* h, const float* feat, const int32_t* lens, i
       return e;
     };
     if (h->graph_mode & CASR_GRAPHS_RECURRENCE) {
-      // rows are independent: two row halves replay as two graphs on two streams, so one
-      // half's load latency hides behind the other's MFMAs
-      const int nsplit = B >= 64 ? 2 : 1;
-      const int half = ((B / 2) + 15) / 16 * 16;
       hipGraphExec_t ex[2] = {};
-      for (int p = 0; p < nsplit; ++p) {
-        const int r0 = (nsplit == 1 || p == 0) ? 0 : half;
-        const int r1 = (nsplit == 1 || p == 1) ? B : half;
-        const std::vector<uint64_t> key = {1, (uint64_t)s16, (uint64_t)l, (uint64_t)B, (uint64_t)Tp, (uint64_t)residual,
-                                           (uint64_t)r0, (uint64_t)r1, (uint64_t)h->W, (uint64_t)h->gin.p,
-                                           (uint64_t)xin, (uint64_t)out, (uint64_t)hb, (uint64_t)h->cst.p,
-                                           (uint64_t)h->hfin.p, (uint64_t)dl};
+      for (int p = 0; p < rec.nsplit; ++p) {
+        const int r0 = rec.row0[p], r1 = rec.row1[p];
+        const int32_t scalars[] = {l, r0, r1};
+        const std::vector<uint64_t> key = plan_graph_key(1, &plan, sizeof plan, scalars, 3, buf, sizeof buf / sizeof buf[0]);
         HIP_OK(h, get_graph(h, key, [&](hipStream_t cs) { return rec_loop(cs, nullptr, r0, r1); }, &ex[p]));
       }
       ProfScope ps(&h->prof, CASR_K_REC_STEP, s, Tp);  // one pair per replay of Tp steps
-      HIP_OK(h, launch_graphs(h, ex, nsplit, s));
+      HIP_OK(h, launch_graphs(h, ex, rec.nsplit, s));
     } else {
       HIP_OK(h, rec_loop(s, &h->prof, 0, B));
     }
-    x = out;
   }
   h->enc_out = const_cast<float*>(x);
   {
   ProfScope ps(&h->prof, CASR_K_KEYS, s);
-  // s16x3 keys on every s16 path (the per-step fallback splits the encoder output first), so both
-  // recurrences give the same keys bits
-  if (s16 && !x16_ready) {
-    HIP_OK(h, launch_split_rows(h->enc_out, C, (int)rows, C, C, h->x16.as<uint16_t>(), eflag, s, km));
-    x16_ready = true;
+  if (s16) {  // from the image the last persistent layer wrote, or of a split pass after a per-step one
+    if (!persistent && plan.keys.split)
+      HIP_OK(h, launch_split_rows(h->enc_out, C, plan.M, C, C, h->x16.as<uint16_t>(), eflag, s, plan.km));
+    HIP_OK(h, launch_keys_s16(plan.keys, h->x16.as<float>(), h->W + h->L.wenc16, h->W + h->L.b_attn,
+                              h->keysT.as<float>(), s));
+  } else {
+    HIP_OK(h, launch_keys(plan.keys, h->enc_out, h->W + h->L.wencT, h->W + h->L.b_attn, h->keysT.as<float>(), s));
   }
-  if (x16_ready)  // s16x3 keys from the image the last persistent layer wrote
-    HIP_OK(h, launch_keys_s16(h->x16.as<float>(), B, Tp, h->W + h->L.wenc16, h->W + h->L.b_attn,
-                              h->keysT.as<float>(), s, h->tune[CASR_OPT_KEYS_ROWS], km));
-  else
-    HIP_OK(h, launch_keys(h->enc_out, B, Tp, h->W + h->L.wencT, h->W + h->L.b_attn, h->keysT.as<float>(), s));
   }
   h->B = B;
   h->Tp = Tp;

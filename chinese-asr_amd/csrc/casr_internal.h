@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "casr.h"
-#include "decode_plan.h"
+#include "encode_plan.h"
 #include "ngram_table.h"
 #include "resample_design.h"
 
@@ -227,13 +227,12 @@ struct ConvertArgs {
 hipError_t launch_convert(const ConvertArgs& a, int B, const ResamplePlan& p, float target, hipStream_t s);
 
 // features.hip
-// the layer-0 s16 row image straight from fbank (features_rows_kernel<true>, T <= 1024)
-bool features_x16_supported(int T);
+// the layer-0 s16 image straight from fbank (features_rows_kernel<true>): the plan's FEAT_IMAGE
 // stats: [B][2][D] floats of scratch (per-utterance mean and std + eps of the 720 dimensions)
-hipError_t launch_features_x16(const float* fbank, const int32_t* frames, int B, int T, float eps,
-                               int32_t* feat_len, float* stats, uint16_t* x16, int Kp, int32_t* err, hipStream_t s,
-                               int km = 0);
-hipError_t launch_features(const float* fbank, const int32_t* frames, int B, int T, float eps,
+hipError_t launch_features_x16(const EncodePlan& p, const float* fbank, const int32_t* frames, int T, float eps,
+                               int32_t* feat_len, float* stats, uint16_t* x16, int32_t* err, hipStream_t s);
+// path: feature_path's FEAT_ROWS (T <= FS_MAX_T) or FEAT_TWO_PASS
+hipError_t launch_features(int path, const float* fbank, const int32_t* frames, int B, int T, float eps,
                            float* feat, int32_t* feat_len, float* stats, hipStream_t s);
 hipError_t launch_gather_utts(const float* const* ptrs, const int32_t* lens, int B, int Tp,
                               float* feat, hipStream_t s);
@@ -245,49 +244,34 @@ hipError_t launch_input_proj(const float* X, int M, int Din, const float* W, con
 // of two layouts (the same words): the row image [R][Kp / 32][32 hi | 32 lo] halves, or (km, round
 // 5, CASR_OPT_X16_KM) 16-k-block major [Kp / 16][R][16 hi | 16 lo], in which 16 consecutive rows of
 // one 16-k block are 1 KB contiguous (whole 128-B lines for the input GEMM's 16-deep stages).
-// x16_km: whether one encode uses the 16-k-major layout (the ping-pong input GEMM, the balanced tail
-// and the row-streaming keys form read it; the other forms take row images)
-inline bool x16_km(const Tuning& t) {
-  return t[CASR_OPT_X16_KM] && t[CASR_OPT_GEMM16_PERSIST] == 2 && t[CASR_OPT_GEMM16_TAIL] != 1 &&
-         t[CASR_OPT_KEYS_ROWS];
-}
-// gemm16.hip: the s16x3 input projection on 256 x 256 tiles; X16 / W16 are s16 images with Kp
-// (multiple of 64) k per row (km: both 16-k-block major, X16 with M rows).  K: the real input width
-// (the images are zero from K to Kp); 0 = Kp.  persist / tail: CASR_OPT_GEMM16_PERSIST / _TAIL
-hipError_t launch_input_proj_s16_big(const float* X16, int M, int Kp, const float* W16, const float* bias,
-                                     float* Gin, hipStream_t s, int K, int persist, int tail, int km = 0,
-                                     int lean = 0);
+// (which layout one encode uses: encode_plan.h encode_km)
+// gemm16.hip: the s16x3 input projection on 256 x 256 tiles in the form g plans; X16 / W16 are s16
+// images with g.Kp k per row (g.km: both 16-k-block major, X16 with g.M rows)
+hipError_t launch_input_proj_s16_big(const InputGemmPlan& g, const float* X16, const float* W16, const float* bias,
+                                     float* Gin, hipStream_t s);
 // a row-image weight matrix [R][Kp] -> its 16-k-block-major image (bind time)
 hipError_t launch_relayout_km16(const float* rowimg, int R, int Kp, float* km, hipStream_t s);
 hipError_t launch_split_rows(const float* X, int ldx, int M, int K, int Kp, uint16_t* out, int32_t* err,
                              hipStream_t s, int km = 0);
-inline int s16_kpad(int K) { return (K + 63) / 64 * 64; }  // even number of 32-k tiles (gemm16.hip)
 hipError_t launch_rec_step(const float* Whh_f, const float* Gin, const float* xin, float* out,
                            const float* hprev, float* hnext, float* cst, float* hfin,
                            const int32_t* lens, int B, int Tp, int step, int residual, int row0,
                            int row1, int s16, hipStream_t s);
-// recurrence.hip: persistent per-layer recurrence (all Tp steps in one launch).  `layout` is the
-// resolved workgroup shape rec_layout(B, opt) returns: 0 = 32 rows x 16 units, 1 = 16 x 32, 2 = 16 x 16
-int rec_layout(int B, const Tuning& t);
-size_t rec_layer_granule_bytes(int B, int layout);
-int rec_layer_grid_blocks(int B, int layout);
-int rec_layer_waves(int layout);      // waves per workgroup (trace layout)
-int rec_layer_producers(int layout);  // workgroups per row group (trace layout)
-bool rec_layer_fits(int B, int layout);  // the persistent grid for batch B is resident at once (one launch)
-hipError_t reset_rec_layer(uint32_t* hx, int B, int layout, hipStream_t s);  // before EVERY launch_rec_layer
-// x16 (s16 only, may be null): also write out's s16 row image [B*Tp][C/32][32 hi | 32 lo] (the
-// next layer's input-GEMM operand, zeros past each length), replacing a split_rows pass.
-// With t[CASR_OPT_REC_COOP] the launch is cooperative: a grid that cannot be co-resident returns
+// recurrence.hip: persistent per-layer recurrence (all Tp steps in one launch) in the shape r plans
+DeviceFacts read_device_facts();  // of the current device (once per handle)
+hipError_t reset_rec_layer(const RecPlan& r, uint32_t* hx, hipStream_t s);  // before EVERY launch_rec_layer
+// x16 (s16 only, may be null): also write out's s16 image (the next layer's input-GEMM operand,
+// zeros past each length), replacing a split_rows pass.
+// With r.coop == 1 the launch is cooperative: a grid that cannot be co-resident returns
 // an error (hipErrorCooperativeLaunchTooLarge) instead of spinning into the hand-off timeout.
-hipError_t launch_rec_layer(const float* Whh_f, const float* Gin, const float* xin, float* out,
-                            uint16_t* x16, uint32_t* hx, float* hfin, float* cst, const int32_t* lens, int B, int Tp,
-                            int residual, int s16, int32_t* err, uint32_t* trace, int layout, const Tuning& t,
-                            hipStream_t s, int km = 0);
-// enc16: the encoder output's s16 image (km: 16-k-block major; rows = 1 only)
-hipError_t launch_keys_s16(const float* enc16, int B, int Tp, const float* wenc16, const float* b_attn,
-                           float* keysT, hipStream_t s, int rows = 1, int km = 0);
-hipError_t launch_keys(const float* enc, int B, int Tp, const float* wencT, const float* b_attn,
-                       float* keysT, hipStream_t s);
+hipError_t launch_rec_layer(const RecPlan& r, const float* Whh_f, const float* Gin, const float* xin, float* out,
+                            uint16_t* x16, uint32_t* hx, float* hfin, float* cst, const int32_t* lens, int residual,
+                            int32_t* err, uint32_t* trace, hipStream_t s);
+// enc16: the encoder output's s16 image (k.km: 16-k-block major); k.form KEYS16_ROWS or KEYS16_TILES
+hipError_t launch_keys_s16(const KeysPlan& k, const float* enc16, const float* wenc16, const float* b_attn,
+                           float* keysT, hipStream_t s);
+hipError_t launch_keys(const KeysPlan& k, const float* enc, const float* wencT, const float* b_attn, float* keysT,
+                       hipStream_t s);
 
 // decoder.hip
 // (GreedyPart, GP_NB, GP_NT and the fused image's tiling, FOLD_*: decode_plan.h)

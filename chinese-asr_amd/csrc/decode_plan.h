@@ -395,26 +395,31 @@ inline size_t carve_beam_out(void* base, int B, int L, BeamOut& o) {
   return c.bytes(64);
 }
 
-// ---------------------------------------------------------------- hipGraph key of a captured decode
-// Everything a captured decode bakes in: the kind of capture, the plan's bytes, the scalar kernel
-// arguments (their bit patterns) and the base pointer of every buffer handed to the launchers.
-inline std::vector<uint64_t> decode_graph_key(int kind, const DecodePlan& plan, const float* scalars, int n_scalars,
-                                              const void* const* bufs, int n_bufs) {
-  static_assert(sizeof(DecodePlan) % sizeof(uint32_t) == 0, "DecodePlan: int32 fields only");
+// ---------------------------------------------------------------- hipGraph key of a captured sequence
+// Everything a captured sequence bakes in: the kind of capture, the plan's bytes (a DecodePlan or an
+// EncodePlan: int32 fields only), the scalar arguments (4-byte words: their bit patterns) and the
+// base pointer of every buffer handed to the launchers.
+inline std::vector<uint64_t> plan_graph_key(int kind, const void* plan, size_t plan_bytes, const void* scalars,
+                                            int n_scalars, const void* const* bufs, int n_bufs) {
   std::vector<uint64_t> key;
-  key.reserve(1 + sizeof(DecodePlan) / 4 + n_scalars + n_bufs);
+  key.reserve(1 + plan_bytes / 4 + n_scalars + n_bufs);
   key.push_back((uint64_t)kind);
   uint32_t w;
-  for (size_t i = 0; i < sizeof(DecodePlan) / 4; ++i) {
-    memcpy(&w, reinterpret_cast<const char*>(&plan) + 4 * i, 4);
+  for (size_t i = 0; i < plan_bytes / 4; ++i) {
+    memcpy(&w, static_cast<const char*>(plan) + 4 * i, 4);
     key.push_back(w);
   }
   for (int i = 0; i < n_scalars; ++i) {
-    memcpy(&w, scalars + i, 4);
+    memcpy(&w, static_cast<const char*>(scalars) + 4 * i, 4);
     key.push_back(w);
   }
   for (int i = 0; i < n_bufs; ++i) key.push_back((uint64_t)(uintptr_t)bufs[i]);
   return key;
+}
+inline std::vector<uint64_t> decode_graph_key(int kind, const DecodePlan& plan, const float* scalars, int n_scalars,
+                                              const void* const* bufs, int n_bufs) {
+  static_assert(sizeof(DecodePlan) % sizeof(uint32_t) == 0, "DecodePlan: int32 fields only");
+  return plan_graph_key(kind, &plan, sizeof plan, scalars, n_scalars, bufs, n_bufs);
 }
 
 }  // namespace casr

@@ -23,7 +23,7 @@ namespace casr {
 // 64x64 (4x4 MFMA tiles).  The k order inside a BK tile is permuted identically for A and
 // W (lane group g takes k = 8g + 4*half + e) so each lane's A/W fragment is a contiguous
 // float4 in LDS (ds_read_b128).  K must be a multiple of 4 (a partial last k tile is zero-filled).
-constexpr int GB_M = 128, GB_N = 128, GB_K = 32;
+// (the GB_M x GB_N tile, GB_K k per stage: encode_plan.h)
 
 struct StoreBiasEpi {  // C[row][col] = acc + bias[col]; N % 4 == 0, rows 16 B aligned
   static constexpr bool kRowTile = true;
@@ -68,7 +68,6 @@ struct KeysEpi {
 // each A row block is fetched by NG XCDs instead of all 8.
 struct TileOrder {
   int NB, NM, NG;
-  __host__ __device__ int blocks() const { return 8 * (NB / NG) * ((NM + 8 / NG - 1) / (8 / NG)); }
   __device__ bool tile(int L, int& n, int& m) const {
     const int x = L & 7, j = L >> 3, nbg = NB / NG;
     n = (x % NG) * nbg + (j % nbg);
@@ -77,13 +76,8 @@ struct TileOrder {
   }
 };
 
-inline TileOrder tile_order(int NB, int NM, int K) {
-  // smallest group count whose W share (NB/NG blocks of 128 rows x K) fits 3/4 of an L2
-  // (input projection: NG = 2, 2.9 MB at K = 720)
-  int NG = 1;
-  while (NG < 8 && NB % (NG * 2) == 0 && (size_t)(NB / NG) * GB_N * K * 4 > (3u << 20)) NG *= 2;
-  return TileOrder{NB, NM, NG};
-}
+// (the group count, input projection: NG = 2, 2.9 MB at K = 720, and the grid: encode_plan.h
+// xcd_groups, xcd_order_blocks)
 
 // S16 = true: A and W are s16 row images (casr_common.h split16): row r holds K/32 k-tiles of
 // 128 B = [32 hi halves | 32 lo halves], so one k-tile of a row is the same 128 B the f32 kernel
@@ -339,9 +333,9 @@ hipError_t launch_input_proj(const float* X, int M, int Din, const float* W, con
   const int N = 8 * H;
   if (Din % 4 != 0 || M <= 0) return hipErrorInvalidValue;  // 16-B rows chunks (K tail: gemm_nt_kernel)
   StoreBiasEpi epi{Gin, bias, N};
-  const TileOrder order = tile_order(N / GB_N, (M + GB_M - 1) / GB_M, Din);
-  hipLaunchKernelGGL(gemm_nt_kernel<StoreBiasEpi>, dim3(order.blocks()), dim3(256), 0, s, X, Din, W,
-                     Din, M, N, Din, order, epi);
+  const TileOrder order{N / GB_N, (M + GB_M - 1) / GB_M, xcd_groups(N / GB_N, GB_N, Din)};
+  const dim3 grid(xcd_order_blocks(order.NB, order.NM, order.NG));
+  hipLaunchKernelGGL(gemm_nt_kernel<StoreBiasEpi>, grid, dim3(256), 0, s, X, Din, W, Din, M, N, Din, order, epi);
   return hipGetLastError();
 }
 
@@ -390,14 +384,12 @@ hipError_t launch_split_rows(const float* X, int ldx, int M, int K, int Kp, uint
   return hipGetLastError();
 }
 
-hipError_t launch_keys(const float* enc, int B, int Tp, const float* wencT, const float* b_attn,
-                       float* keysT, hipStream_t s) {
-  const int M = B * Tp;
-  if (M <= 0) return hipErrorInvalidValue;
-  KeysEpi epi{keysT, b_attn, Tp, attn_tq(Tp), B};
-  const TileOrder order = tile_order(A / GB_N, (M + GB_M - 1) / GB_M, C);
-  hipLaunchKernelGGL(gemm_nt_kernel<KeysEpi>, dim3(order.blocks()), dim3(256), 0, s, enc, C, wencT,
-                     C, M, A, C, order, epi);
+hipError_t launch_keys(const KeysPlan& k, const float* enc, const float* wencT, const float* b_attn, float* keysT,
+                       hipStream_t s) {
+  KeysEpi epi{keysT, b_attn, k.Tp, k.Tq, k.B};
+  const TileOrder order{A / GB_N, k.NM, k.NG};
+  hipLaunchKernelGGL(gemm_nt_kernel<KeysEpi>, dim3(k.grid), dim3(256), 0, s, enc, C, wencT, C, k.B * k.Tp, A, C, order,
+                     epi);
   return hipGetLastError();
 }
 
@@ -426,7 +418,7 @@ CASR_DEV void g16_vm_wait_k() {
 #ifndef CASR_KR_DIAG
 #define CASR_KR_DIAG 0
 #endif
-constexpr int KR_G = 16;                   // A rows per item
+// (KR_G A rows per item: encode_plan.h)
 constexpr int KR_KT = C / 32;              // 32-deep k-tiles
 constexpr int KR_IF = KR_KT * KR_G * 32;   // floats per item (32 KB)
 constexpr int KR_NBUF = 4;                 // ring slots (three items in flight)
@@ -549,29 +541,18 @@ __global__ __launch_bounds__(512, 1) void keys16_kernel(const float* __restrict_
   }
 }
 
-// keys from the s16 row image of the encoder output (written by the last persistent layer) and
-// of wencT: s16x3 products, same KeysEpi store (rows = 1: keys16_kernel, the default)
-hipError_t launch_keys_s16(const float* enc16, int B, int Tp, const float* wenc16, const float* b_attn,
-                           float* keysT, hipStream_t s, int rows, int km) {
-  const int M = B * Tp;
-  if (M <= 0 || C % GB_K != 0 || (km && !rows)) return hipErrorInvalidValue;
-  if (rows) {
-    static int ncu = [] {
-      int dev = 0, v = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-      return v > 0 ? v : 256;
-    }();
-    const int Tq = attn_tq(Tp), NI = B * ((Tp + KR_G - 1) / KR_G);
-    if ((size_t)2 * B * A * Tq * 4 >= 0xFFFFFFF0u) return hipErrorInvalidValue;  // 32-bit buffer offsets
-    hipLaunchKernelGGL(keys16_kernel, dim3(std::min(NI, ncu)), dim3(512), 0, s, enc16, wenc16, b_attn, keysT, B, Tp,
-                       Tq, km);
+// keys from the s16 image of the encoder output (written by the last persistent layer) and of
+// wencT: s16x3 products, same KeysEpi store (KEYS16_ROWS: keys16_kernel, the default)
+hipError_t launch_keys_s16(const KeysPlan& k, const float* enc16, const float* wenc16, const float* b_attn,
+                           float* keysT, hipStream_t s) {
+  if (k.form == KEYS16_ROWS) {
+    hipLaunchKernelGGL(keys16_kernel, dim3(k.grid), dim3(512), 0, s, enc16, wenc16, b_attn, keysT, k.B, k.Tp, k.Tq, k.km);
     return hipGetLastError();
   }
-  KeysEpi epi{keysT, b_attn, Tp, attn_tq(Tp), B};
-  const TileOrder order = tile_order(A / GB_N, (M + GB_M - 1) / GB_M, C);
-  hipLaunchKernelGGL((gemm_nt_kernel<KeysEpi, true>), dim3(order.blocks()), dim3(256), 0, s, enc16, C, wenc16,
-                     C, M, A, C, order, epi);
+  KeysEpi epi{keysT, b_attn, k.Tp, k.Tq, k.B};
+  const TileOrder order{A / GB_N, k.NM, k.NG};
+  hipLaunchKernelGGL((gemm_nt_kernel<KeysEpi, true>), dim3(k.grid), dim3(256), 0, s, enc16, C, wenc16, C, k.B * k.Tp, A,
+                     C, order, epi);
   return hipGetLastError();
 }
 

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void cmvn_kernel(float* __restrict__ feat,
 // [0, nf) (stack_kernel's); mean = the 24 chunk sums (each in row order) added in a fixed tree,
 // / lp; var likewise over (v - mean)^2 / (lp - 1); std = sqrt(var) + eps (main.py:37).
 constexpr int SM = 8, SRM = 3 * SM, SPH = 24, SQ = 9 * SM;  // mels, (frame, mel) pairs, chunks, dims
-constexpr int FS_MAX_T = 1024;  // stats kernel's LDS: (nf + 14) x SM floats (33 KB) + 7 KB
+// FS_MAX_T (encode_plan.h) = 1024 frames: the stats kernel's LDS: (nf + 14) x SM floats (33 KB) + 7 KB
 // zero frames staged before / after the nf frames: windows reach t = -4 and, with the refill after
 // a chunk's last row, t = 3 lp + 6 <= nf + 6; FS_PAD2 = 10 covers it (the refill's values are unused)
 constexpr int FS_PAD = 4, FS_PAD2 = 10;
@@ -372,12 +372,12 @@ __global__ __launch_bounds__(RTH) void features_rows_kernel(const float* __restr
   if (X16 && !range_ok) __hip_atomic_fetch_or(err, CASR_DEV_F16_RANGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-hipError_t launch_features(const float* fbank, const int32_t* frames, int B, int T, float eps,
+hipError_t launch_features(int path, const float* fbank, const int32_t* frames, int B, int T, float eps,
                            float* feat, int32_t* feat_len, float* stats, hipStream_t s) {
   const int Tp = T / 3;
   if (Tp <= 0 || B <= 0) return hipErrorInvalidValue;
   // eps < 0: no CMVN (the stacked features get_log_mel returns, data.py:226-249)
-  if (T <= FS_MAX_T) {
+  if (path == FEAT_ROWS) {
     const size_t shm = (size_t)(T + FS_PAD + FS_PAD2) * SM * sizeof(float);
     hipLaunchKernelGGL(features_stats_kernel, dim3((F / SM) * ((B + 7) / 8 * 8)), dim3(SRM * SPH), shm, s, fbank, frames, B, T, eps, stats,
                        feat_len);
@@ -393,13 +393,11 @@ hipError_t launch_features(const float* fbank, const int32_t* frames, int B, int
   return hipGetLastError();
 }
 
-bool features_x16_supported(int T) { return T / 3 > 0 && T <= FS_MAX_T; }
+static_assert(s16_kpad(D) == 2 * RTH, "features_rows_kernel<true>: one thread per two k of the layer-0 image");
 
-hipError_t launch_features_x16(const float* fbank, const int32_t* frames, int B, int T, float eps,
-                               int32_t* feat_len, float* stats, uint16_t* x16, int Kp, int32_t* err, hipStream_t s,
-                               int km) {
-  const int Tp = T / 3;
-  if (B <= 0 || !features_x16_supported(T) || Kp != 2 * RTH) return hipErrorInvalidValue;
+hipError_t launch_features_x16(const EncodePlan& p, const float* fbank, const int32_t* frames, int T, float eps,
+                               int32_t* feat_len, float* stats, uint16_t* x16, int32_t* err, hipStream_t s) {
+  const int B = p.B, Tp = p.Tp, Kp = s16_kpad(D), km = p.km;
   const size_t shm = (size_t)(T + FS_PAD + FS_PAD2) * SM * sizeof(float);
   hipLaunchKernelGGL(features_stats_kernel, dim3((F / SM) * ((B + 7) / 8 * 8)), dim3(SRM * SPH), shm, s, fbank, frames, B, T, eps, stats,
                      feat_len);

@@ -31,12 +31,11 @@ namespace casr {
 
 namespace {
 
-constexpr int G16_M = 256, G16_N = 256, G16_K = 32;  // tile rows, columns, k per stage
+// (G16_M x G16_N tiles, G16_K k per stage: encode_plan.h)
 constexpr int G16_TILE = G16_M * G16_K;              // 4-B words per operand stage (32 KB)
 
 struct Order16 {
   int NB, NM, NG;
-  __host__ __device__ int blocks() const { return 8 * (NB / NG) * ((NM + 8 / NG - 1) / (8 / NG)); }
   __device__ bool tile(int L, int& n, int& m) const {
     const int x = L & 7, j = L >> 3, nbg = NB / NG;
     n = (x % NG) * nbg + (j % nbg);
@@ -997,93 +996,57 @@ __global__ __launch_bounds__(256, 1) void gemm16_tail_kernel(const float* __rest
   }
 }
 
-// tail rows [r0, M) of the input projection as gemm16_tail_kernel tiles (one round of ncu workgroups
-// while the rows allow RT <= 5)
-static bool launch_tail_balanced(const float* A16, const float* W16, const float* bias, float* Gin, int Mt, int N, int Kp,
-                                 int ncu, hipStream_t s, int km, int r0, int Mimg) {
-  if (Mt <= 0 || N % 128 != 0) return false;
-  const int units = (Mt + 31) / 32 * (N / 128);
-  const int RT = std::min(5, (units + ncu - 1) / ncu);  // (past 5 x ncu units: more than one round)
-  const int blocks = (Mt + 32 * RT - 1) / (32 * RT) * (N / 128);
-  switch (RT) {
-    case 1: hipLaunchKernelGGL((km ? gemm16_tail_kernel<1, true> : gemm16_tail_kernel<1, false>), dim3(blocks), dim3(256), 0, s, A16, W16, bias, Gin, Mt, N, Kp, r0, Mimg); break;
-    case 2: hipLaunchKernelGGL((km ? gemm16_tail_kernel<2, true> : gemm16_tail_kernel<2, false>), dim3(blocks), dim3(256), 0, s, A16, W16, bias, Gin, Mt, N, Kp, r0, Mimg); break;
-    case 3: hipLaunchKernelGGL((km ? gemm16_tail_kernel<3, true> : gemm16_tail_kernel<3, false>), dim3(blocks), dim3(256), 0, s, A16, W16, bias, Gin, Mt, N, Kp, r0, Mimg); break;
-    case 4: hipLaunchKernelGGL((km ? gemm16_tail_kernel<4, true> : gemm16_tail_kernel<4, false>), dim3(blocks), dim3(256), 0, s, A16, W16, bias, Gin, Mt, N, Kp, r0, Mimg); break;
-    default: hipLaunchKernelGGL((km ? gemm16_tail_kernel<5, true> : gemm16_tail_kernel<5, false>), dim3(blocks), dim3(256), 0, s, A16, W16, bias, Gin, Mt, N, Kp, r0, Mimg); break;
+// tail rows [g.r0, g.M) of the input projection as gemm16_tail_kernel tiles
+template <bool KM>
+static void launch_tail_balanced(const InputGemmPlan& g, const float* A16, const float* W16, const float* bias,
+                                 float* Gin, hipStream_t s) {
+  const int N = 8 * H;
+  const dim3 grid(g.tail_grid), block(256);
+  switch (g.RT) {
+    case 1: hipLaunchKernelGGL((gemm16_tail_kernel<1, KM>), grid, block, 0, s, A16, W16, bias, Gin, g.Mt, N, g.Kp, g.r0, g.M); break;
+    case 2: hipLaunchKernelGGL((gemm16_tail_kernel<2, KM>), grid, block, 0, s, A16, W16, bias, Gin, g.Mt, N, g.Kp, g.r0, g.M); break;
+    case 3: hipLaunchKernelGGL((gemm16_tail_kernel<3, KM>), grid, block, 0, s, A16, W16, bias, Gin, g.Mt, N, g.Kp, g.r0, g.M); break;
+    case 4: hipLaunchKernelGGL((gemm16_tail_kernel<4, KM>), grid, block, 0, s, A16, W16, bias, Gin, g.Mt, N, g.Kp, g.r0, g.M); break;
+    default: hipLaunchKernelGGL((gemm16_tail_kernel<5, KM>), grid, block, 0, s, A16, W16, bias, Gin, g.Mt, N, g.Kp, g.r0, g.M); break;
   }
-  return true;
 }
 
 }  // namespace
 
-hipError_t launch_input_proj_s16_big(const float* X16, int M, int Kp, const float* W16, const float* bias,
-                                     float* Gin, hipStream_t s, int K, int persist, int tail, int km, int lean) {
-  const int N = 8 * H;
-  if (km && (persist != 2 || tail == 1)) return hipErrorInvalidValue;  // the forms that read 16-k-major images
-  if (Kp % (2 * G16_K) != 0 || M <= 0 || N % G16_N != 0) return hipErrorInvalidValue;
-  const int NB = N / G16_N, NM = (M + G16_M - 1) / G16_M;
-  // smallest group count whose W share (NB/NG slices of 256 rows x Kp words) fits 3/4 of an L2
-  int NG = 1;
-  while (NG < 8 && NB % (NG * 2) == 0 && (size_t)(NB / NG) * G16_N * Kp * 4 > (3u << 20)) NG *= 2;
-  const Order16 order{NB, NM, NG};
-  if (persist) {
-    static int ncu = [] {
-      int dev = 0, v = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-      return v > 0 ? v : 256;
-    }();
-    // the persistent kernel runs ceil(K / 32) stages of the Kp-wide images (both zero past K): layer
-    // 0 (K = 720, Kp = 768) skips the all-zero last stage
-    const int nk = (K > 0 && K <= Kp ? K + G16_K - 1 : Kp) / G16_K;
-    // Balanced last round.  NB x NM tiles over ncu workgroups leave a partial last round (B = 256:
-    // 2128 tiles = 8 rounds + 80 tiles, so 80 CUs run a ninth tile while 176 idle; B = 128: 4
-    // rounds + 40).  The persistent kernel takes the first F = floor(NB NM / ncu) rounds (whole row
-    // tiles: F ncu / NB of them, every workgroup exactly F tiles) and the rows after them go to
-    // one launch of 128 x 256 half tiles (gemm16_bias_kernel<4, 1>, one per CU), which run at one
-    // wave per SIMD.  Same per-element arithmetic as the persistent kernel: bitwise equal.
-    int NMm = NM;
-    const int F = NB * NM / ncu;
-    if (tail && F >= 1 && (F * ncu) % NB == 0 && F * ncu / NB < NM) {
-      const int nm = F * ncu / NB;
-      const int tail_rows = M - nm * G16_M, NMt = (tail_rows + 127) / 128;
-      if (NB * NMt <= ncu) NMm = nm;  // the half tiles fit one round
-    }
-    const Order16 om{NB, NMm, NG};
-    const int total = om.blocks();
-    const int Mm = std::min(M, NMm * G16_M);
-    if (persist == 2) {  // ping-pong form: 16-deep stages
-      const int nk16 = (K > 0 && K <= Kp ? K + 15 : Kp) / 16;
-      if (km && lean && nk16 >= 8)
-        hipLaunchKernelGGL(gemm16_pp_lean_kernel, dim3(std::min(total, ncu)), dim3(512), 0, s, X16, W16, bias, Gin, Mm, N,
-                           om, total, nk16, M);
-      else if (km)
-        hipLaunchKernelGGL((gemm16_pp_kernel<0, 1, 0, 0, true>), dim3(std::min(total, ncu)), dim3(512), 0, s, X16, W16, bias,
-                           Gin, Mm, N, Kp, om, total, nk16, M);
-      else
-        hipLaunchKernelGGL((gemm16_pp_kernel<0, 1>), dim3(std::min(total, ncu)), dim3(512), 0, s, X16, W16, bias, Gin, Mm,
-                           N, Kp, om, total, nk16, M);
-    } else {
-      hipLaunchKernelGGL(gemm16_persist_kernel<0>, dim3(std::min(total, ncu)), dim3(512), 0, s, X16, W16, bias, Gin, Mm,
-                         N, Kp, om, total, nk);
-    }
-    if (NMm < NM) {
-      const size_t r0 = (size_t)NMm * G16_M;
-      const int Mt = M - (int)r0, NMt = (Mt + 127) / 128;
-      if (tail == 2 && launch_tail_balanced(km ? X16 : X16 + r0 * Kp, W16, bias, Gin + r0 * N, Mt, N, Kp, ncu, s, km,
-                                            (int)r0, M))
-        return hipGetLastError();
-      // the row-image tail kernel below cannot read a 16-k-block-major image: a km image whose
-      // balanced tail was not taken is refused, never read as rows
-      if (km) return hipErrorInvalidValue;
-      const Order16 ot{NB, NMt, NG};  // XCD grouping of the tail: the same column slices per XCD
-      hipLaunchKernelGGL((gemm16_bias_kernel<4, 1>), dim3(ot.blocks()), dim3(256), 0, s, X16 + r0 * Kp, W16, bias,
-                         Gin + r0 * N, Mt, N, Kp, ot);
-    }
-  } else {
-    hipLaunchKernelGGL(gemm16_bias_kernel<4>, dim3(order.blocks()), dim3(512), 0, s, X16, W16, bias, Gin, M, N, Kp,
-                       order);
+// every decision is the plan's (encode_plan.h plan_input_gemm): form -> kernel here
+hipError_t launch_input_proj_s16_big(const InputGemmPlan& g, const float* X16, const float* W16, const float* bias,
+                                     float* Gin, hipStream_t s) {
+  const int N = 8 * H, M = g.M, Kp = g.Kp;
+  const Order16 om{g.NB, g.NMm, g.NG};
+  const dim3 grid(g.grid), block(512);
+  switch (g.form) {
+    case GEMM16_TILES:
+      hipLaunchKernelGGL(gemm16_bias_kernel<4>, grid, block, 0, s, X16, W16, bias, Gin, M, N, Kp, om);
+      break;
+    case GEMM16_PERSIST:
+      hipLaunchKernelGGL(gemm16_persist_kernel<0>, grid, block, 0, s, X16, W16, bias, Gin, g.Mm, N, Kp, om, g.total, g.nk);
+      break;
+    case GEMM16_PP:  // ping-pong form: 16-deep stages
+      hipLaunchKernelGGL((gemm16_pp_kernel<0, 1>), grid, block, 0, s, X16, W16, bias, Gin, g.Mm, N, Kp, om, g.total,
+                         g.nk16, M);
+      break;
+    case GEMM16_PP_KM:
+      hipLaunchKernelGGL((gemm16_pp_kernel<0, 1, 0, 0, true>), grid, block, 0, s, X16, W16, bias, Gin, g.Mm, N, Kp, om,
+                         g.total, g.nk16, M);
+      break;
+    case GEMM16_PP_LEAN:
+      hipLaunchKernelGGL(gemm16_pp_lean_kernel, grid, block, 0, s, X16, W16, bias, Gin, g.Mm, N, om, g.total, g.nk16, M);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+  const size_t r0 = (size_t)g.r0;
+  if (g.tail == TAIL_BALANCED) {
+    if (g.km) launch_tail_balanced<true>(g, X16, W16, bias, Gin + r0 * N, s);
+    else launch_tail_balanced<false>(g, X16 + r0 * Kp, W16, bias, Gin + r0 * N, s);
+  } else if (g.tail == TAIL_HALF) {
+    const Order16 ot{g.NB, g.NMt, g.NG};  // XCD grouping of the tail: the same column slices per XCD
+    hipLaunchKernelGGL((gemm16_bias_kernel<4, 1>), dim3(g.tail_grid), dim3(256), 0, s, X16 + r0 * Kp, W16, bias,
+                       Gin + r0 * N, g.Mt, N, Kp, ot);
   }
   return hipGetLastError();
 }

@@ -394,82 +394,35 @@ __global__ __launch_bounds__(RG * UW, 2) void rec_layer_kernel(
 
 }  // namespace
 
-// CUs of the current device (the persistent grid wants one workgroup per CU)
-static int rec_cus() {
-  static const int v = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  return v;
-}
-
-// Layout per batch.  32x16 (512 threads: 32 rows x 16 units) while its grid of 16 x ceil(B/32) x 2
-// workgroups needs all the CUs (B = 256: one per CU); 16x16 (256 threads) once 16 x ceil(B/16) x 2
-// workgroups still fit one per CU (B <= 128): twice the workgroups, each with half the rows, so
-// a step's MFMA and cell work per CU halves while the hand-off stays a 16-producer exchange.
-// Measured (rec ms per batch, two interleaved rounds): beam B = 128 2.36-2.37 (32x16) -> 2.01-2.02
-// (16x16); greedy B = 256 2.67-2.71 (32x16) vs 3.08-3.10 (16x16: two workgroups per CU).
-// CASR_OPT_REC_LAYOUT forces one (1 = 32x16, 2 = 16x32, 3 = 16x16).
-int rec_layout(int B, const Tuning& t) {
-  switch (t[CASR_OPT_REC_LAYOUT]) {
-    case 1: return 0;
-    case 2: return 1;
-    case 3: return 2;
-    default: return (H / 16) * ((B + 15) / 16) * 2 <= rec_cus() ? 2 : 0;
-  }
-}
-static int rec_rows(int layout) { return layout == 0 ? 32 : 16; }
-static int rec_units(int layout) { return layout == 1 ? 32 : 16; }
-
-// the three granule buffers, then the placement table (one word per workgroup)
-static size_t rec_granule_words(int B) { return (size_t)3 * 2 * ((B + 31) / 32 * 32) * H; }
-
-size_t rec_layer_granule_bytes(int B, int layout) {
-  return (rec_granule_words(B) + (size_t)rec_layer_grid_blocks(B, layout)) * sizeof(uint32_t);
-}
-
-int rec_layer_waves(int layout) { return rec_rows(layout) * rec_units(layout) / 64; }
-
-int rec_layer_producers(int layout) { return H / rec_units(layout); }
-
-int rec_layer_grid_blocks(int B, int layout) {
-  return (H / rec_units(layout)) * ((B + rec_rows(layout) - 1) / rec_rows(layout)) * 2;
-}
-
+// The facts of the current device the encode plan reads (encode_plan.h DeviceFacts; here because only
+// this file can name the persistent kernels).  Resident workgroups per CU: both arithmetic variants
+// must fit, so the capacity is the smaller of the two (0: the query failed)
 template <int RG, int UW>
 static int occ() {
-  // both arithmetic variants must fit: the capacity is the smaller of the two
-  static const int v = [] {
-    int a = 0, b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, rec_layer_kernel<RG, UW, false>, RG * UW, 0) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rec_layer_kernel<RG, UW, true>, RG * UW, 0) != hipSuccess)
-      return 0;
-    return a < b ? a : b;
-  }();
-  return v;
+  int a = 0, b = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, rec_layer_kernel<RG, UW, false>, RG * UW, 0) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rec_layer_kernel<RG, UW, true>, RG * UW, 0) != hipSuccess)
+    return 0;
+  return a < b ? a : b;
+}
+DeviceFacts read_device_facts() {
+  DeviceFacts f{};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&f.cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (f.cus <= 0) f.cus = 256;
+  f.rec_per_cu[REC_32x16] = occ<32, 16>();
+  f.rec_per_cu[REC_16x32] = occ<16, 32>();
+  f.rec_per_cu[REC_16x16] = occ<16, 16>();
+  return f;
 }
 
-bool rec_layer_fits(int B, int layout) {
-  int per_cu;
-  switch (layout) {
-    case 1: per_cu = occ<16, 32>(); break;
-    case 2: per_cu = occ<16, 16>(); break;
-    default: per_cu = occ<32, 16>(); break;
-  }
-  return rec_layer_grid_blocks(B, layout) <= per_cu * rec_cus();
-}
-
-hipError_t reset_rec_layer(uint32_t* hx, int B, int layout, hipStream_t s) {
-  // Guideline 16: re-initialise every call.  Buffer j is first read at step j (j = 1, 2) or 3
-  // (j = 0), expecting parity 1, 0, 1: fill buffers 0 and 1 with parity 0, buffer 2 with 1.
-  // The placement table after them starts at 0 (no id published).
-  const size_t per = rec_granule_words(B) / 3;
+// Guideline 16: re-initialise every call (the segments: encode_plan.h plan_recurrence)
+hipError_t reset_rec_layer(const RecPlan& r, uint32_t* hx, hipStream_t s) {
   FillList fl;
-  fl.add32(hx, 0u, 2 * per);
-  fl.add32(hx + 2 * per, TAG_BIT, per);
-  fl.add32(hx + 3 * per, 0u, (size_t)rec_layer_grid_blocks(B, layout));
+  fl.add32(hx, 0u, (size_t)r.hx_zero);
+  fl.add32(hx + r.hx_zero, TAG_BIT, (size_t)r.hx_tagged);
+  fl.add32(hx + r.hx_zero + r.hx_tagged, 0u, (size_t)r.hx_table);
   return fill_multi(fl, s);
 }
 
@@ -489,22 +442,13 @@ constexpr int REC_CHAIN_DEVICES = 64;
 hipEvent_t g_rec_chain[REC_CHAIN_DEVICES] = {};
 }  // namespace
 
-hipError_t launch_rec_layer(const float* Whh_f, const float* Gin, const float* xin, float* out,
-                            uint16_t* x16, uint32_t* hx, float* hfin, float* cst, const int32_t* lens, int B, int Tp,
-                            int residual, int s16, int32_t* err, uint32_t* trace, int layout, const Tuning& t,
-                            hipStream_t s, int km) {
-  int Bp = (B + 31) / 32 * 32;  // granule planes padded to 32 rows for every layout
-  const int RG = rec_rows(layout), UW = rec_units(layout);
-  int nrg = (B + RG - 1) / RG;
-  // (-1, the default: no sleep for grids of 64 workgroups or more, one unit below: B <= 16 in the
-  // 16-row layout, 32 workgroups; measured round 6)
-  const int nwg = (H / UW) * nrg * 2;
-  int sleep = t[CASR_OPT_REC_SLEEP] < 0 ? (nwg >= 64 ? 0 : 1) : t[CASR_OPT_REC_SLEEP] > 16 ? 16 : t[CASR_OPT_REC_SLEEP];
-  int gap = t[CASR_OPT_REC_POLL_GAP] < 1 ? 1 : t[CASR_OPT_REC_POLL_GAP] > 8 ? 8 : t[CASR_OPT_REC_POLL_GAP];
-  int plain = t[CASR_OPT_REC_STORE_PLAIN] ? 1 : 0;
-  const dim3 grid((H / UW) * nrg * 2), block(RG * UW);
+hipError_t launch_rec_layer(const RecPlan& r, const float* Whh_f, const float* Gin, const float* xin, float* out,
+                            uint16_t* x16, uint32_t* hx, float* hfin, float* cst, const int32_t* lens, int residual,
+                            int32_t* err, uint32_t* trace, hipStream_t s) {
+  int B = r.B, Bp = r.Bp, Tp = r.Tp, nrg = r.nrg, sleep = r.sleep, gap = r.gap, plain = r.plain, km = r.km;
+  const dim3 grid(r.grid), block(r.block);
   auto go = [&](auto kern) -> hipError_t {
-    if (t[CASR_OPT_REC_COOP] == 1) {
+    if (r.coop == 1) {
       // every workgroup co-resident or an immediate launch error (the hand-off spins need all of them)
       void* args[] = {&Whh_f, &Gin, &xin, &out, &x16, &hx, &hfin, &cst, &lens, &B, &Bp, &Tp, &residual,
                       &err, &trace, &nrg, &sleep, &gap, &plain, &km};
@@ -512,7 +456,7 @@ hipError_t launch_rec_layer(const float* Whh_f, const float* Gin, const float* x
     }
     hipEvent_t chain = nullptr;
     std::unique_lock<std::mutex> lk(g_rec_chain_mu, std::defer_lock);
-    if (t[CASR_OPT_REC_COOP] == 2) {  // ordered after this process's previous persistent grid (above)
+    if (r.coop == 2) {  // ordered after this process's previous persistent grid (above)
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
       int dev = -1;
       hipError_t e = hipStreamIsCapturing(s, &cs);
@@ -535,10 +479,10 @@ hipError_t launch_rec_layer(const float* Whh_f, const float* Gin, const float* x
     if (e == hipSuccess && chain) e = hipEventRecord(chain, s);
     return e;
   };
-  switch (layout) {
-    case 1: return s16 ? go(rec_layer_kernel<16, 32, true>) : go(rec_layer_kernel<16, 32, false>);
-    case 2: return s16 ? go(rec_layer_kernel<16, 16, true>) : go(rec_layer_kernel<16, 16, false>);
-    default: return s16 ? go(rec_layer_kernel<32, 16, true>) : go(rec_layer_kernel<32, 16, false>);
+  switch (r.layout) {
+    case REC_16x32: return r.s16 ? go(rec_layer_kernel<16, 32, true>) : go(rec_layer_kernel<16, 32, false>);
+    case REC_16x16: return r.s16 ? go(rec_layer_kernel<16, 16, true>) : go(rec_layer_kernel<16, 16, false>);
+    default: return r.s16 ? go(rec_layer_kernel<32, 16, true>) : go(rec_layer_kernel<32, 16, false>);
   }
 }
 

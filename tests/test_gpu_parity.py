@@ -769,12 +769,14 @@ def test_model_reruns_f32_on_f16_range_overflow():
     np.testing.assert_array_equal(np.asarray(g.score), np.asarray(g32.score))
 
 
-@pytest.mark.parametrize("B", [256, 128, 37])
+@pytest.mark.parametrize("B", [256, 128, 37, 31])
 def test_input_gemm_tail_split_bitwise(eng, B):
     """s16x3 input projection: the persistent kernel over whole rounds plus the 128 x 256 half-tile
     launch for the rows after them (default), the persistent kernel alone (CASR_OPT_GEMM16_TAIL = 0)
     and the per-tile kernel (CASR_OPT_GEMM16_PERSIST = 0) give bitwise-identical encoder outputs
-    (B = 256 and 128: 80 / 40 tiles past the last whole round; B = 37: 48 tiles in one partial round).
+    (B = 256 and 128: 80 / 40 tiles past the last whole round; B = 37: 48 tiles in one partial round;
+    B = 31: the smallest batch that splits at all, a tail of 54 rows, one whole 32-row unit and a
+    partial one).
     Round 5: the ping-pong persistent kernel (CASR_OPT_GEMM16_PERSIST = 2, the default: 16-deep
     stages, two staggered wave groups, buffer stores that drop rows past M) with and without the
     tail split, against the round-2 persistent kernel and the per-tile kernel; and the balanced tail

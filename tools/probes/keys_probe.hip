@@ -64,8 +64,20 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(dB, bias.data(), A * 4, hipMemcpyHostToDevice));
   CK(hipMemset(dK0, 0, kn * 4));
   CK(hipMemset(dK1, 0, kn * 4));
-  CK(launch_keys_s16(dA, B, Tp, dW, dB, dK0, 0, 0));
-  CK(launch_keys_s16(dA, B, Tp, dW, dB, dK1, 0, 1));
+  // the two forms' plans (row images: CASR_OPT_X16_KM off)
+  int dev = 0;
+  DeviceFacts facts{};
+  CK(hipGetDevice(&dev));
+  CK(hipDeviceGetAttribute(&facts.cus, hipDeviceAttributeMultiprocessorCount, dev));
+  KeysPlan kp[2];
+  for (int form = 0; form < 2; ++form) {
+    Tuning t;
+    t.v[CASR_OPT_X16_KM] = 0;
+    t.v[CASR_OPT_KEYS_ROWS] = form;
+    kp[form] = plan_encode(B, Tp, 0, false, casr_config{}, t, true, false, facts).keys;
+  }
+  CK(launch_keys_s16(kp[0], dA, dW, dB, dK0, 0));
+  CK(launch_keys_s16(kp[1], dA, dW, dB, dK1, 0));
   CK(hipDeviceSynchronize());
   std::vector<float> k0(kn), k1(kn);
   CK(hipMemcpy(k0.data(), dK0, kn * 4, hipMemcpyDeviceToHost));
@@ -86,7 +98,7 @@ int main(int argc, char** argv) {
     for (int form = 0; form < 2; ++form) {
       const int iters = 20;
       CK(hipEventRecord(e0));
-      for (int i = 0; i < iters; ++i) CK(launch_keys_s16(dA, B, Tp, dW, dB, form ? dK1 : dK0, 0, form));
+      for (int i = 0; i < iters; ++i) CK(launch_keys_s16(kp[form], dA, dW, dB, form ? dK1 : dK0, 0));
       CK(hipEventRecord(e1));
       CK(hipEventSynchronize(e1));
       float ms;
