@@ -158,6 +158,51 @@ class Engine:
                    self.handle)
         return feat, flen
 
+    def segment(self, fbank, frames, params=None, s_max=None):
+        """Cut long recordings at their pauses (casr_segment, include/casr.h): fbank [B, T, n_mels]
+        float32 and frames [B] int32 on the device, as log_mel returns them -> device tensors
+        (seg_start [B, s_max], seg_len [B, s_max], n_seg [B], thr [B]), all int32.  n_seg[b] is the
+        true count even above s_max; entries past it are -1.  s_max defaults to the bound
+        (casr.segment.segment_bound).  Returns after enqueueing."""
+        from .segment import SegmentParams, segment_bound
+        params = (params or SegmentParams()).validate()
+        fbank = fbank.to(self.device, torch.float32).contiguous()
+        B, T, _ = fbank.shape
+        frames = torch.as_tensor(frames).to(self.device, torch.int32).contiguous()
+        if frames.shape != (B,):
+            raise ValueError(f"segment: frames must be [B={B}]")
+        s_max = segment_bound(T, params) if s_max is None else int(s_max)
+        start = torch.full((B, s_max), -1, device=self.device, dtype=torch.int32)
+        length = torch.full((B, s_max), -1, device=self.device, dtype=torch.int32)
+        n_seg = torch.empty(B, device=self.device, dtype=torch.int32)
+        thr = torch.empty(B, device=self.device, dtype=torch.int32)
+        c = params.struct()
+        _lib.check(self.lib.casr_segment(self.handle, _ptr(fbank), _ptr(frames), B, T, ctypes.byref(c), s_max,
+                                         _ptr(start), _ptr(length), _ptr(n_seg), _ptr(thr), _stream()), self.handle)
+        self._keep_segment = (fbank, frames)  # read by the enqueued kernels
+        return start, length, n_seg, thr
+
+    def gather_segments(self, fbank, src, start, length, t_seg=None):
+        """Copy S segments of fbank [B, T, n_mels] into a padded batch (casr_gather_segments): src, start,
+        length [S] int (recording, first frame, frames) -> (out [S, t_seg, n_mels], zero past each
+        length; frames_out [S] int32), what features and encode_fbank take.  t_seg defaults to the
+        longest length (one host read when they are device tensors)."""
+        fbank = fbank.to(self.device, torch.float32).contiguous()
+        B, T, n_mels = fbank.shape
+        src, start, length = (torch.as_tensor(x).to(self.device, torch.int32).contiguous() for x in (src, start, length))
+        S = int(src.shape[0])
+        if src.shape != (S,) or start.shape != (S,) or length.shape != (S,):
+            raise ValueError("gather_segments: src, start and length must be [S]")
+        if t_seg is None:
+            t_seg = max(int(length.max()), 1) if S else 1
+        out = torch.empty(S, int(t_seg), n_mels, device=self.device, dtype=torch.float32)
+        frames_out = torch.empty(S, device=self.device, dtype=torch.int32)
+        if S:
+            _lib.check(self.lib.casr_gather_segments(self.handle, _ptr(fbank), B, T, _ptr(src), _ptr(start), _ptr(length),
+                                                     S, int(t_seg), _ptr(out), _ptr(frames_out), _stream()), self.handle)
+        self._keep_gather_seg = (fbank, src, start, length)
+        return out, frames_out
+
     def gather(self, utts, lens, Tp=None):
         """list of B device tensors [T_b, feat_dim] -> padded [B, Tp, feat_dim]."""
         B = len(utts)

@@ -180,6 +180,7 @@ struct casr_handle {
   static constexpr size_t RS_CACHE = 6;
   std::vector<ResampleTable*> rs_tables;
   DevBuf cvt_peak;
+  DevBuf seg_q, seg_hist;  // casr_segment: the frames' levels [B][T] uint16 and the histograms [B][512]
   bool use_persistent = true;
   int precision = CASR_PREC_S16;  // requested (casr_set_precision)
   bool s16_valid = false;           // the bound blob's s16 images are usable (Layout::info)
@@ -578,7 +579,8 @@ void casr_destroy(casr_handle* h) {
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
-                    &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak})
+                    &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
+                    &h->seg_q, &h->seg_hist})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -805,6 +807,98 @@ int casr_convert_audio(casr_handle* h, const float* pcm, const int32_t* n_in, in
   const double lin = std::pow(10.0, (double)norm_db / 20.0);
   const float target = norm ? (float)(a.quantize ? 32768.0 * lin : lin) : 1.f;
   HIP_OK(h, launch_convert(a, B, p, target, s));
+  return CASR_OK;
+}
+
+int casr_segment_default_params(casr_segment_params* p) {
+  if (!p) return fail(nullptr, CASR_ERR_ARG, "casr_segment_default_params: NULL");
+  *p = segment_default_params();
+  return CASR_OK;
+}
+
+int casr_segment_bound(int T, const casr_segment_params* p) { return p ? (int)segment_bound(T, *p) : -1; }
+
+static int segment_params_checked(casr_handle* h, const char* who, const casr_segment_params* p) {
+  if (!p) return fail(h, CASR_ERR_ARG, "%s: NULL parameters", who);
+  if (!segment_params_valid(*p))
+    return fail(h, CASR_ERR_ARG,
+                "%s: invalid parameters (max_frames %d min_frames %d min_pause %d min_speech %d pad %d max_gap %d "
+                "pct_lo %d pct_hi %d rel_q8 %d rise_min %d)",
+                who, p->max_frames, p->min_frames, p->min_pause, p->min_speech, p->pad, p->max_gap, p->pct_lo,
+                p->pct_hi, p->rel_q8, p->rise_min);
+  return CASR_OK;
+}
+
+int casr_segment_host(const float* fbank, const int32_t* frames, int B, int T, int n_mels,
+                      const casr_segment_params* p, int s_max, int32_t* seg_start, int32_t* seg_len, int32_t* n_seg,
+                      int32_t* thr) {
+  const int rc = segment_params_checked(nullptr, "casr_segment_host", p);
+  if (rc != CASR_OK) return rc;
+  if (B < 0 || T < 0 || s_max < 0 || (B > 0 && (!frames || !n_seg)) || (B > 0 && T > 0 && !fbank) ||
+      (B > 0 && s_max > 0 && (!seg_start || !seg_len)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_segment_host: NULL pointer or bad shape (B=%d T=%d s_max=%d)", B, T, s_max);
+  if (n_mels <= 0 || n_mels % SEG_LANES)
+    return fail(nullptr, CASR_ERR_UNSUPPORTED, "casr_segment_host: n_mels %d is not a positive multiple of %d", n_mels,
+                SEG_LANES);
+  for (int b = 0; b < B; ++b)
+    if (frames[b] < 0 || frames[b] > T)
+      return fail(nullptr, CASR_ERR_ARG, "casr_segment_host: frames[%d] = %d not in [0, %d]", b, frames[b], T);
+  for (int b = 0; b < B; ++b)
+    segment_row_host(fbank + (size_t)b * T * n_mels, frames[b], n_mels, *p, s_max,
+                     seg_start + (size_t)b * s_max, seg_len + (size_t)b * s_max, n_seg + b, thr ? thr + b : nullptr);
+  return CASR_OK;
+}
+
+int casr_segment(casr_handle* h, const float* fbank, const int32_t* frames, int B, int T,
+                 const casr_segment_params* p, int s_max, int32_t* seg_start, int32_t* seg_len, int32_t* n_seg,
+                 int32_t* thr, void* stream) {
+  if (!h || !fbank || !frames || !n_seg || (s_max > 0 && (!seg_start || !seg_len)))
+    return fail(h, CASR_ERR_ARG, "casr_segment: NULL handle, fbank, frames, n_seg, seg_start or seg_len");
+  if (B <= 0 || B > 65535 || T <= 0 || T > INT32_MAX - 65536 || s_max < 0)
+    return fail(h, CASR_ERR_ARG, "casr_segment: bad shape (B=%d T=%d s_max=%d)", B, T, s_max);
+  const int rc = segment_params_checked(h, "casr_segment", p);
+  if (rc != CASR_OK) return rc;
+  if (h->cfg.n_mels % SEG_LANES)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_segment: n_mels %d is not a multiple of %d", h->cfg.n_mels, SEG_LANES);
+  HIP_OK(h, hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_segment: guard words not allocated");
+  HIP_OK(h, h->seg_q.ensure((size_t)B * T * sizeof(uint16_t)));
+  HIP_OK(h, h->seg_hist.ensure((size_t)B * SEG_BINS * sizeof(uint32_t)));
+  SegmentArgs a{};
+  a.fbank = fbank;
+  a.frames = frames;
+  a.B = B;
+  a.T = T;
+  a.n_mels = h->cfg.n_mels;
+  a.s_max = s_max;
+  a.p = *p;
+  a.seg_start = seg_start;
+  a.seg_len = seg_len;
+  a.n_seg = n_seg;
+  a.thr = thr;
+  a.q = h->seg_q.as<uint16_t>();
+  a.hist = h->seg_hist.as<uint32_t>();
+  a.err = GUARD(h, 2);
+  HIP_OK(h, launch_segment(a, s));
+  return CASR_OK;
+}
+
+int casr_gather_segments(casr_handle* h, const float* fbank, int B, int T, const int32_t* seg_src,
+                         const int32_t* seg_start, const int32_t* seg_len, int S, int t_seg, float* out,
+                         int32_t* frames_out, void* stream) {
+  if (!h || !fbank || !seg_src || !seg_start || !seg_len || !out || !frames_out)
+    return fail(h, CASR_ERR_ARG, "casr_gather_segments: NULL argument");
+  if (B <= 0 || T <= 0 || S <= 0 || t_seg <= 0)
+    return fail(h, CASR_ERR_ARG, "casr_gather_segments: bad shape (B=%d T=%d S=%d t_seg=%d)", B, T, S, t_seg);
+  if (((uintptr_t)fbank | (uintptr_t)out) & 15)
+    return fail(h, CASR_ERR_ARG, "casr_gather_segments: fbank and out must be 16-byte aligned");
+  if (h->cfg.n_mels % 4)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_gather_segments: n_mels %d is not a multiple of 4", h->cfg.n_mels);
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_gather_segments: guard words not allocated");
+  HIP_OK(h, launch_gather_segments(fbank, B, T, h->cfg.n_mels, seg_src, seg_start, seg_len, S, t_seg, out, frames_out,
+                                   GUARD(h, 2), (hipStream_t)stream));
   return CASR_OK;
 }
 

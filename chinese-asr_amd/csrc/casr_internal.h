@@ -10,6 +10,7 @@
 #include "encode_plan.h"
 #include "ngram_table.h"
 #include "resample_design.h"
+#include "segment_plan.h"
 
 // the s16 arithmetic of this build (casr_common.h CASR_S16_ONE: the s16x1 build)
 #ifndef CASR_S16_ONE
@@ -29,7 +30,7 @@ constexpr int CASR_DEV_NAN_LOGITS = 4;   // no finite maximum in a logit row (gr
 constexpr int CASR_DEV_BAD_CAND = 8;     // beam candidate index not in [0, k*V)
 constexpr int CASR_DEV_BAD_BACKPTR = 16; // back-pointer walk left [0, k)
 constexpr int CASR_DEV_REC_TIMEOUT = 32; // persistent recurrence: a bounded hand-off wait expired
-constexpr int CASR_DEV_BAD_AUDIO = 64;   // front-end: n_samples < 513 (torch.stft raises) or > n_max; convert: n_in outside [0, n_max_in]
+constexpr int CASR_DEV_BAD_AUDIO = 64;   // front-end: n_samples < 513 (torch.stft raises) or > n_max; convert: n_in outside [0, n_max_in]; segment / gather_segments: frames or a segment out of range
 constexpr int CASR_DEV_F16_RANGE = 128;  // s16x3 path: a finite operand beyond the f16 range (>= 65520)
 
 // MFMA-fragment-major weight block: a 16-row x 64-k tile stored as [q=0..3][lane][4] so
@@ -225,6 +226,26 @@ struct ConvertArgs {
 };
 // target: 32768 10^(norm_db / 20) (quantize) or 10^(norm_db / 20), rounded to f32
 hipError_t launch_convert(const ConvertArgs& a, int B, const ResamplePlan& p, float target, hipStream_t s);
+
+// segment.hip: casr_segment's two launches (the histogram words are cleared first) and
+// casr_gather_segments; the decision text is segment_plan.h's
+struct SegmentArgs {
+  const float* fbank;      // [B][T][n_mels]
+  const int32_t* frames;   // [B]
+  int B, T, n_mels, s_max;
+  casr_segment_params p;   // valid (segment_params_valid)
+  int32_t* seg_start;      // [B][s_max]
+  int32_t* seg_len;        // [B][s_max]
+  int32_t* n_seg;          // [B]
+  int32_t* thr;            // [B] or null
+  uint16_t* q;             // [B][T] workspace: the frames' levels
+  uint32_t* hist;          // [B][512] workspace
+  int32_t* err;            // guard word
+};
+hipError_t launch_segment(const SegmentArgs& a, hipStream_t s);
+hipError_t launch_gather_segments(const float* fbank, int B, int T, int n_mels, const int32_t* seg_src,
+                                  const int32_t* seg_start, const int32_t* seg_len, int S, int t_seg, float* out,
+                                  int32_t* frames_out, int32_t* err, hipStream_t s);
 
 // features.hip
 // the layer-0 s16 image straight from fbank (features_rows_kernel<true>): the plan's FEAT_IMAGE

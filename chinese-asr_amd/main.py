@@ -3,8 +3,9 @@
 
 ``parse(path, model, audio_base, lm_model, bw)`` and ``ASR(lm_path=None, bw=None)(path)`` keep
 the reference signatures and results; ``align(path, text, model, audio_base)`` is this path's own
-addition (forced alignment of a given transcript).  The chain wav -> log-mel -> delta/stack -> CMVN
-(eps 1e-6, main.py:37) -> encoder -> greedy / beam (+ second pass with a KenLM-like
+addition (forced alignment of a given transcript), and so is ``transcribe(paths, model, audio_base)``
+(recordings of any length, cut at their pauses on the device: casr_segment).  The chain wav ->
+log-mel -> delta/stack -> CMVN (eps 1e-6, main.py:37) -> encoder -> greedy / beam (+ second pass with a KenLM-like
 ``lm_model.score(s, bos=True)``) runs on the GPU through the casr C ABI.  Format conversion
 (``convert_audio``: ffmpeg + sox, main.py:19-24) uses the external tools where both are present;
 without them a WAV input of any rate and channel count is converted on the device
@@ -106,6 +107,66 @@ def parse_batch(paths, model, audio_base, lm_model=None, bw=None):
     return list(res.pred_text)
 
 
+MIN_SEGMENT_FRAMES = 9  # the delta filters' 9 taps: a shorter segment is returned with empty text
+
+
+def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, batch_size=256):
+    """Recordings of any length -> per recording a list of casr.segment.Segment (start_s, end_s, text,
+    score, truncated), this path's own addition: the log-mel of every recording is cut at its pauses
+    on the device (casr_segment, include/casr.h; ``params`` a casr.segment.SegmentParams) and the
+    segments are decoded as parse decodes an utterance, ``batch_size`` at a time in (recording, time)
+    order.  ``truncated`` marks a segment whose decode used all max_len steps without an EOS (lower
+    ``params.max_frames`` then).  A recording with no speech returns []."""
+    import numpy as np
+    import torch
+    from data import _engine
+    from casr.segment import Segment, SegmentParams, frame_time
+
+    params = (params or SegmentParams()).validate()
+    audios = read_audio(paths)
+    eng = _engine()
+    n = [int(len(a)) for a in audios]
+    if min(n) < 513:  # as log_mel_batch: torch.stft raises on a signal shorter than n_fft (data.py:204)
+        raise RuntimeError(f"audio of {min(n)} samples is shorter than n_fft + 1 = 513")
+    wav = np.zeros((len(audios), max(n)), np.float32)
+    for b, a in enumerate(audios):
+        wav[b, :n[b]] = a
+    fb, frames = eng.log_mel(torch.from_numpy(wav).to(eng.device), torch.tensor(n, dtype=torch.int32),
+                             preemphasis=float(gpd['preemphasis']))
+    start, length, n_seg, _ = eng.segment(fb, frames, params)
+    counts = n_seg.cpu().tolist()  # the one read the decode's shape depends on
+    out = [[] for _ in audios]
+    if sum(counts) == 0:
+        return out
+    src = torch.tensor([b for b, c in enumerate(counts) for _ in range(c)], dtype=torch.int64, device=eng.device)
+    slot = torch.tensor([i for c in counts for i in range(c)], dtype=torch.int64, device=eng.device)
+    starts, lens = start[src, slot], length[src, slot]  # (recording, time) order, no sorting
+    src_h, starts_h, lens_h = src.cpu().tolist(), starts.cpu().tolist(), lens.cpu().tolist()
+    segs = [Segment(frame_time(s), frame_time(s + l), '', 0.0, False) for s, l in zip(starts_h, lens_h)]
+    todo = [i for i, l in enumerate(lens_h) if l >= MIN_SEGMENT_FRAMES]
+    for c0 in range(0, len(todo), int(batch_size)):
+        idx = todo[c0:c0 + int(batch_size)]
+        sel = torch.tensor(idx, dtype=torch.int64, device=eng.device)
+        seg_fb, seg_frames = eng.gather_segments(fb, src[sel], starts[sel], lens[sel], t_seg=max(lens_h[i] for i in idx))
+        feat, flen = eng.features(seg_fb, seg_frames, eps=1e-6)
+        flen = flen.cpu()
+        data = [feat[i, :int(flen[i])] for i in range(len(idx))]
+        if bw is not None:
+            res = model.eval_one_batch_with_beam(model.device, bw, data, flen, None, audio_base.int2word,
+                                                 second_pass=lm_model is not None, lm_model=lm_model,
+                                                 lm_weight=1.5, length_weight=1.5)
+            # no finished hypothesis: the fallback ran to max_len
+            cut = (~model.engine.beam_records()[2].flatten(1).bool().any(1)).cpu().tolist()
+        else:
+            res = model.eval_one_batch_with_greedy(model.device, data, flen, audio_base.int2word, None)
+            cut = (res.text_len >= model.cfg.max_len).cpu().tolist()
+        for j, i in enumerate(idx):
+            segs[i].text, segs[i].score, segs[i].truncated = res.pred_text[j], float(res.score[j]), bool(cut[j])
+    for b, s in zip(src_h, segs):
+        out[b].append(s)
+    return out
+
+
 class ASR:
     """main.py:68-102."""
 
@@ -139,6 +200,11 @@ class ASR:
 
     def __call__(self, path):
         return parse(path, self.model, self.audio_base, self.lm_model, self.bw)
+
+    def transcribe(self, path, params=None):
+        """A recording of any length -> its text: the segments' texts of transcribe(), joined."""
+        segs = transcribe([path], self.model, self.audio_base, self.lm_model, self.bw, params=params)[0]
+        return ''.join(s.text for s in segs)
 
 
 if __name__ == '__main__':

@@ -190,6 +190,100 @@ int casr_resample_plan(int rate_in, int32_t* L, int32_t* M, int32_t* taps);
 int casr_resample_filter(int rate_in, float* table_host);
 int casr_resample_frames(int n_in, int rate_in);
 
+/* Long recordings: cut the log-mel of a recording at its pauses into segments of at most max_frames
+ * frames, which are then transcribed one by one (main.transcribe).  The reference does no segmentation
+ * (its main.py takes one utterance), so, like casr_convert_audio, the operation is DEFINED BY THE
+ * FORMULAS BELOW; tests/segment_ref.py restates them in numpy.  After stage (a) everything is an
+ * integer: the host entry, the device and the restatement agree exactly.  Per recording, on rows
+ * [0, n) of fbank, n = frames[b]:
+ *  (a) level     p_j = fb[t][j] + fb[t][16 + j] + .. (ascending, f32 adds) for j = 0..15, then the fixed
+ *                halving tree p_j += p_{j+8} (j < 8), then += p_{j+4}, p_{j+2}, p_{j+1};
+ *                E[t] = p_0 float32(1 / n_mels) (one f32 product, never fused with the next add);
+ *                q[t] = clamp(floor((E[t] + 24f) 8f), 0, 511), NaN -> 0: bins of 1/8 neper over
+ *                [-24, 40).  n_mels must be a multiple of 16.
+ *  (b) threshold hist = the histogram of q[0..n).  P(pct) = the smallest v with
+ *                sum_{u <= v} hist[u] >= max(1, (n pct + 99) div 100) (64-bit); lo = P(pct_lo),
+ *                hi = P(pct_hi); thr = lo + max(rise_min, ((hi - lo) rel_q8 + 128) >> 8), saturating at
+ *                INT32_MAX; thr = 0 at n = 0.  A0[t] = q[t] >= thr.
+ *  (c) filters   over maximal runs inside [0, n).  A1: every active run of A0 shorter than min_speech is
+ *                cleared.  A2: on A1, every inactive run shorter than min_pause with an active frame on
+ *                both sides is set (leading and trailing quiet is never filled).  The islands are the
+ *                maximal active runs [a, b) of A2, each widened to [max(0, a - pad), min(n, b + pad));
+ *                min_pause > 2 pad keeps widened islands apart.
+ *  (d) split     per island [s, e) in order: while e - s > max_frames, the cut c in
+ *                [s + min_frames, min(s + max_frames, e - min_frames)] that minimises q[c-1] + q[c], the
+ *                LARGEST such c on a tie; the piece [s, c) is emitted and s = c; finally [s, e).
+ *  (e) merge     greedy from the left over the pieces: a segment starts at piece i and absorbs piece j
+ *                while start_j - end <= max_gap and end_j - start_i <= max_frames (the pauses in between
+ *                stay inside the segment).
+ * Output per recording: (start, len) per segment, ascending, disjoint, 1 <= len <= max_frames, inside
+ * [0, n).  n = 0, or no active frame, gives no segment.
+ * A parameter set is valid iff min_speech >= 1, pad >= 0, min_pause > 2 pad, min_frames >= 1,
+ * 2 min_frames <= max_frames, max_gap >= 0, 0 <= pct_lo <= pct_hi <= 100, 0 <= rel_q8 <= 256 and
+ * rise_min >= 0; anything else is CASR_ERR_ARG and nothing is launched or written. */
+typedef struct casr_segment_params {
+  int32_t max_frames;  /* 800  longest segment, in frames */
+  int32_t min_frames;  /* 200  shortest piece a split may leave */
+  int32_t min_pause;   /* 20   shortest quiet run that counts as a pause */
+  int32_t min_speech;  /* 5    shortest active run that is kept */
+  int32_t pad;         /* 8    frames added on each side of a speech island */
+  int32_t max_gap;     /* 100  largest gap across which pieces are merged */
+  int32_t pct_lo;      /* 10   percentile that gives the noise floor */
+  int32_t pct_hi;      /* 95   percentile that gives the speech level */
+  int32_t rel_q8;      /* 90   rise above the floor, as a fraction of hi - lo in units of 1/256 */
+  int32_t rise_min;    /* 12   smallest rise above the floor, in bins */
+} casr_segment_params;
+
+/* The defaults above.  CASR_ERR_ARG for NULL.  Host only. */
+int casr_segment_default_params(casr_segment_params* p);
+
+/* An upper bound of a recording's segment count at T frames: (T + min_pause) / (min_speech + min_pause)
+ * + T / min_frames (islands lie at least min_speech active and min_pause quiet frames apart, and every
+ * split piece but an island's last holds at least min_frames).  -1 on invalid parameters, T < 0 or a
+ * bound that does not fit an int.  Host only. */
+int casr_segment_bound(int T, const casr_segment_params* p);
+
+/* Stages (a) to (e) on the host: every pointer a HOST pointer, no GPU needed.
+ *   fbank [B][T][n_mels], frames [B]
+ *   seg_start, seg_len [B][s_max]; n_seg [B]; thr [B] or NULL
+ * n_seg[b] is the TRUE count even when it exceeds s_max: only the first s_max entries of a row are
+ * written and the rest of it is left untouched, so the caller compares.
+ * CASR_ERR_ARG: a NULL required pointer (seg_start and seg_len may be NULL at s_max = 0), B or T < 0,
+ * s_max < 0, invalid parameters, a frames[b] outside [0, T]; CASR_ERR_UNSUPPORTED: n_mels not a positive
+ * multiple of 16. */
+int casr_segment_host(const float* fbank, const int32_t* frames, int B, int T, int n_mels,
+                      const casr_segment_params* p, int s_max, int32_t* seg_start, int32_t* seg_len,
+                      int32_t* n_seg, int32_t* thr);
+
+/* The same on the device, on the fbank and frames casr_log_mel wrote (n_mels is the handle's): every
+ * pointer a DEVICE pointer, outputs as above with the same s_max rule.  Returns after enqueueing; needs
+ * no weights and no encode.  A frames[b] outside [0, T] is clamped and raises guard bit 64; rows of fbank
+ * past frames[b] are never read as data.  A recording's segments depend only on its own frames and the
+ * parameters: not on B, T, s_max or its neighbours.
+ * Two launches (csrc/segment.hip): the level kernel, 16 lanes per frame, writes q as uint16 into a
+ * handle-owned workspace (2 B T bytes, grows on demand) and adds a per-workgroup LDS histogram to
+ * [B][512] words with integer atomics (cleared per call; no float atomics: the result does not depend
+ * on scheduling); the decision kernel, one workgroup per recording, streams q in tiles of 2,048 frames,
+ * compacts each tile's active runs with ballots and feeds them to the run filters, the split and the
+ * merge of csrc/segment_plan.h, the text casr_segment_host compiles too.  Not among the timed kernel
+ * classes, never replayed as a hipGraph.
+ * CASR_ERR_ARG: a NULL handle or required pointer, B outside [1, 65535], T < 1, s_max < 0 or invalid
+ * parameters; CASR_ERR_UNSUPPORTED: the handle's n_mels not a multiple of 16. */
+int casr_segment(casr_handle* h, const float* fbank, const int32_t* frames, int B, int T,
+                 const casr_segment_params* p, int s_max, int32_t* seg_start, int32_t* seg_len,
+                 int32_t* n_seg, int32_t* thr, void* stream);
+
+/* Copy S segments of fbank [B][T][n_mels] into the padded batch casr_features and casr_encode_fbank
+ * take: out [S][t_seg][n_mels], segment s = rows [seg_start[s], seg_start[s] + seg_len[s]) of recording
+ * seg_src[s]; rows past the length are exactly zero; frames_out [S] = the length.  All device pointers
+ * (seg_src, seg_start, seg_len [S] int32); fbank and out 16-byte aligned (dwordx4 loads and stores).
+ * A seg_src[s] outside [0, B), or a range leaving [0, T) or longer than t_seg, is clamped and raises
+ * guard bit 64.  Returns after enqueueing; not among the timed kernel classes.
+ * CASR_ERR_ARG: a NULL argument, B, T, S or t_seg < 1, or a misaligned fbank or out. */
+int casr_gather_segments(casr_handle* h, const float* fbank, int B, int T, const int32_t* seg_src,
+                         const int32_t* seg_start, const int32_t* seg_len, int S, int t_seg, float* out,
+                         int32_t* frames_out, void* stream);
+
 /* The list-of-tensors boundary of Model.eval_one_batch_* (model.py:514-516): gather B
  * device rows [lens[b]][feat_dim] (utt_ptrs is a DEVICE array of B device pointers) into
  * the padded batch-major [B][Tp][feat_dim] layout. */
@@ -347,7 +441,8 @@ int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, doubl
  * row, 8 beam candidate, 16 back-pointer) is clamped and reported here instead of faulting
  * the device; 32 = a bounded hand-off wait of the persistent recurrence expired (results of
  * that casr_encode are invalid); 64 = casr_log_mel got an utterance shorter than 513
- * samples or longer than n_max, or casr_convert_audio one with n_in outside [0, n_max_in]; 128 = s16x3 arithmetic met a finite activation beyond the f16
+ * samples or longer than n_max, or casr_convert_audio one with n_in outside [0, n_max_in], or casr_segment a
+ * frames[b] outside [0, T], or casr_gather_segments a segment outside its fbank or longer than t_seg; 128 = s16x3 arithmetic met a finite activation beyond the f16
  * range (|x| >= 65520: a layer input split by the encoder), so the split images and every
  * result after them are wrong: re-run the batch with casr_set_precision(CASR_PREC_F32) (the
  * Python Model does this itself, chinese-asr_amd/casr/engine.py run_checked).
