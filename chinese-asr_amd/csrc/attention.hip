@@ -35,7 +35,7 @@
 namespace casr {
 
 constexpr int AT_WAVES = AT_THREADS / 64;
-constexpr int AT_NQ = HD / 16;  // query partials per row at most (dec_q_slots: one per LSTMCell column block)
+constexpr int AT_NQ = HD / 16;  // query partials per row at most (DecodePlan::q_slots: one per LSTMCell column block)
 // (the LDS layout arithmetic, attn_tq .. attn_smem_floats: attention_lds.h, shared with the decode plan)
 
 // Split exponential form of the score tanh.  tanh(k + q) = 1 - 2 / (1 + e^{2k} e^{2q}): with
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(AT_THREADS) void attention_kernel(
       float4 pv[AT_NQ];
 #pragma unroll
       for (int p = 0; p < AT_NQ; ++p) pv[p] = p < nq ? qp[(size_t)p * R * (A / 4)] : make_float4(0.f, 0.f, 0.f, 0.f);
-      // 16-unit slots are summed in pairs first: a 32-unit slot (dec_q_slots) holds exactly that
+      // 16-unit slots are summed in pairs first: a 32-unit slot (DecodePlan::q_slots = 16) holds exactly that
       // pair sum, so q has the same bits whichever LSTMCell shape wrote the partials
       if (nq == AT_NQ) {
 #pragma unroll
@@ -899,7 +899,7 @@ static hipError_t launch_kpb(const DecodeArgs& a, float* st, const float* qpart,
   const float* ekT = a.keysT + (size_t)a.B * A * attn_tq(a.Tp);  // KeysEpi: [keys | exp(2 keys)]
   hipLaunchKernelGGL((attention_kernel<KPB, CELL>), grid, dim3(AT_THREADS), shm, s, st, qpart, a.keysT, ekT, a.enc,
                      a.lens, a.W + a.L.v, a.B * a.k, a.k, a.Tp, align, newdone, l, total, npf, a.plan.attn_direct,
-                     dec_q_slots(a.B * a.k), a.V, cell);
+                     a.plan.q_slots, a.V, cell);
   return hipGetLastError();
 }
 
@@ -921,7 +921,7 @@ static hipError_t launch_greedy_split(const DecodeArgs& a, float* st, int32_t* n
   const float* ekT = a.keysT + (size_t)a.B * A * attn_tq(a.Tp);
   hipLaunchKernelGGL((attention_kernel<1, 1, true>), dim3(a.B, cell.split), dim3(AT_THREADS), shm, s, st, nullptr,
                      a.keysT, ekT, a.enc, a.lens, a.W + a.L.v, a.B, 1, a.Tp, nullptr, newdone, l, total, npf,
-                     a.plan.attn_direct, dec_q_slots(a.B), a.V, cell);
+                     a.plan.attn_direct, a.plan.q_slots, a.V, cell);
   return hipGetLastError();
 }
 

@@ -1164,11 +1164,12 @@ struct DecodeCall {
 };
 
 // One API call's decode: the plan (decode_plan.h), the workspaces it needs, and the launchers' arguments
-static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, DecodeCall& c) {
+static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, DecodeCall& c, int score_len = 0) {
   if (!h->encoded) return fail(h, CASR_ERR_STATE, "decode before casr_encode");
   const int B = h->B, Tp = h->Tp, L = h->cfg.max_len, V = h->cfg.vocab;
   const BlobFacts blob{h->s16(), h->fold_ready, h->proj_small, h->dec_small};
-  const DecodePlan plan = plan_decode(caller, B, Tp, k, want_align, h->cfg, h->L.VP, h->tune, blob, attention_static_lds());
+  const DecodePlan plan = plan_decode(caller, B, Tp, k, want_align, h->cfg, h->L.VP, h->tune, blob, attention_static_lds(),
+                                      score_len);
   switch (plan.status) {
     case PLAN_BAD_K: return fail(h, CASR_ERR_ARG, "beam width %d not in [1, %d]", k, KMAX_BEAM);
     case PLAN_LDS:
@@ -1184,7 +1185,7 @@ static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, De
   const int R = plan.R;
   DecodeBufs& d = h->d;
   d = DecodeBufs{};
-  HIP_OK(h, h->st.ensure(carve_state(nullptr, R, d)));
+  HIP_OK(h, h->st.ensure(carve_state(nullptr, plan, d)));
   HIP_OK(h, h->logits.ensure(carve_logits(nullptr, R, V, d)));
   HIP_OK(h, h->small.ensure(carve_small(nullptr, B, R, L, d)));
   HIP_OK(h, h->bp.ensure((size_t)L * R * sizeof(int32_t)));
@@ -1218,7 +1219,7 @@ static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, De
     buf[DP_GATES] = h->fgates.p;
   }
 
-  carve_state(buf[DP_STATE], R, d);
+  carve_state(buf[DP_STATE], plan, d);
   carve_logits(buf[DP_LOGITS], R, V, d);
   carve_small(buf[DP_SMALL], B, R, L, d);
   carve_records(buf[DP_RECORDS], B, L, plan.k, d);
@@ -1348,7 +1349,7 @@ int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, i
   if (L < 1 || L > h->cfg.max_len) return fail(h, CASR_ERR_ARG, "casr_score: L = %d not in [1, %d]", L, h->cfg.max_len);
   HIP_OK(h, hipSetDevice(h->device));
   DecodeCall c;
-  int rc = prepare_decode(h, PLAN_SCORE, 1, false, c);
+  int rc = prepare_decode(h, PLAN_SCORE, 1, false, c, L);
   if (rc) return rc;
   HIP_OK(h, h->scorebuf.ensure(score_workspace_bytes(h->B, L)));
   const ScoreBufs sb = score_carve(h->scorebuf.p, h->B, L);

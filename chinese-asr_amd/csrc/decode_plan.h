@@ -1,8 +1,11 @@
 // How a decode chooses its kernels: plan_decode() takes one API call's shapes, the handle's options
 // and the bound blob's facts, and returns every path decision of that call as one DecodePlan.  The
 // drivers (casr_capi.hip, decoder.hip, attention.hip, score.hip) read the plan and decide nothing
-// themselves.  Also here, because they must agree with the plan: the option table, the decode
-// workspaces' layouts, and the hipGraph key of a captured decode.
+// themselves: that includes the block shape, grid and arguments of every decode GEMM launch (a
+// DgemmPlan each, of the shape table in decode_gemm_shapes.h), from which the counts that other
+// kernels must agree with (row partials per row, query partials per row) are derived.  Also here,
+// because they must agree with the plan: the option table, the decode workspaces' layouts, and the
+// hipGraph key of a captured decode.
 // Pure host C++ (no HIP runtime): tests/host_plan/plan_check.cpp builds from this header alone.
 #pragma once
 #include <stddef.h>
@@ -14,6 +17,7 @@
 #include "attention_lds.h"
 #include "casr.h"
 #include "casr_dims.h"
+#include "decode_gemm_shapes.h"
 
 namespace casr {
 
@@ -93,16 +97,36 @@ inline int fold_gtile0(int V) { return (fold_vtiles(V) + FOLD_NT - 1) / FOLD_NT 
 
 // the greedy folded GEMM's k split at R <= 32 (decoder.hip dgemm_kernel KS): DG_KS blocks per
 // output block, at most DG_KS_GROUPS output blocks of 2 epilogue waves
-constexpr int DG_KS = 4, DG_KS_GROUPS = 64, DG_KS_COUNTERS = 2 * DG_KS_GROUPS;
+constexpr int DG_KS_GROUPS = 64, DG_KS_COUNTERS = 2 * DG_KS_GROUPS;
 constexpr size_t DG_KS_PART_BYTES = (size_t)DG_KS_COUNTERS * DG_KS * FOLD_NT * 64 * 16;  // f32x4 per lane
 static_assert((KPROJ / 64) % DG_KS == 0, "the fused GEMM's 64-deep k tiles split evenly over DG_KS blocks");
 
-// decode rows at which the LSTMCell (128 x 128) and projection (256 x 160) blocks of decoder.hip
-// fill the CUs in one round; below it the narrower blocks do
+// Within a class every shape has the same tiles per wave column, so the row partials a select reads
+// (one per wave column: DecodePlan::nbp) do not depend on R: 5 in the projection (GreedyPart), a
+// whole FOLD_NT wave column of the fused image in the folded GEMM
+constexpr int PROJ_WAVE_TILES = 5;
+static_assert(dg_shapes_ok(DG_LSTM_32x64, DG_LSTM_128x128, 0) &&
+                  dg_shapes_ok(DG_PROJ_32x80, DG_PROJ_256x160_ONE, PROJ_WAVE_TILES) &&
+                  dg_shapes_ok(DG_FOLD_32x112_KS, DG_FOLD_128x224_ONE, FOLD_NT),
+              "decode GEMM shapes: 8 waves, the ring within the LDS, one partial block width per class");
+
+// Which shape runs (the measurements behind each rule: decoder.hip, above launch_dec_lstm).
+// decode rows at which the LSTMCell (128 x 128), projection (256 x 160) and beam fold (256 x 224)
+// blocks fill the CUs in one round; below it the narrower blocks do
 inline bool dec_wide(int R) { return R >= 2048; }
-// attention query partials per decoder row: one per LSTMCell column block (decoder.hip
-// launch_dec_lstm), 16 units each, 32 units at dec_wide(R)
-inline int dec_q_slots(int R) { return dec_wide(R) ? HD / 32 : HD / 16; }
+inline int dec_lstm_shape(int R) {
+  return R <= 256 ? DG_LSTM_32x64 : R <= 512 ? DG_LSTM_64x64 : !dec_wide(R) ? DG_LSTM_128x64 : DG_LSTM_128x128;
+}
+// one: the one-accumulator shapes (s16 in effect and every |W_p| < 16)
+inline int proj_shape(int R, bool one) {
+  if (R <= 512) return R <= 32 ? DG_PROJ_32x80 : R <= 256 ? DG_PROJ_64x80 : DG_PROJ_128x80;
+  return !one ? DG_PROJ_128x160 : !dec_wide(R) ? DG_PROJ_128x160_ONE : DG_PROJ_256x160_ONE;
+}
+// (the beam fold runs under s16 with small weights only: plan_decode's fold rule)
+inline int fold_gemm_shape(bool beam, int R, bool ksplit) {
+  if (beam) return dec_wide(R) ? DG_FOLD_256x224_ONE : DG_FOLD_128x224_ONE;
+  return ksplit ? DG_FOLD_32x112_KS : R <= 32 ? DG_FOLD_32x112 : DG_FOLD_64x112;
+}
 
 // ---------------------------------------------------------------- the plan
 enum { PLAN_GREEDY = 0, PLAN_BEAM = 1, PLAN_SCORE = 2 };  // the API call that decodes
@@ -131,6 +155,7 @@ struct DecodePlan {
   int32_t lds_bytes;  // LDS of one three-launch attention block without the value prefetch
   // the inputs a captured sequence bakes in
   int32_t caller, B, Tp, k, R, align, s16, proj_small, attn_direct;
+  int32_t score_len;      // casr_score: the target length (the batched projection has score_len x B rows), else 0
   int32_t kpb;            // beam rows per attention block
   int32_t fold;           // the folded step (CASR_OPT_DEC_FOLD in effect)
   int32_t build_fold32;   // the f32 fused image must exist before this decode (greedy fold under f32)
@@ -144,6 +169,12 @@ struct DecodePlan {
   int32_t asplit, tc, split;  // the split greedy attention: ranges asked for, steps per range, ranges; 0 = unsplit
   int32_t K2;             // beam select width (candidates kept per utterance): 4, 8, 16 or 32
   int32_t fin_lds;        // beam finalize: LDS of the wave form, or 0 = the thread-per-utterance form
+  int32_t q_slots;        // attention query partials per decoder row: one per LSTMCell column block
+  // the decode GEMM launches (all zero where the call has no such launch)
+  DgemmPlan lstm;         // the LSTMCell (the folded step: step 0 only)
+  DgemmPlan proj;         // the three-launch step's projection; casr_score: the batched one, score_len x B rows
+  DgemmPlan fold_gates;   // the folded GEMM at the steps that also compute the next gates
+  DgemmPlan fold_last;    // ... and at the last step (vocabulary tiles only)
 };
 
 // beam rows per block at k > 2 (CASR_OPT_ATTN_KPB, 0 = auto).  4 rows per block at B < 256: 8 rows
@@ -172,9 +203,10 @@ inline size_t attention_lds_bytes(int kpb, int Tp, const AttnStaticLds& st, bool
 }
 
 // cfg: vocab, max_len and temperature are read.  VP: the vocabulary padded to the blob's projection
-// tiles (Layout::VP).  want_align: greedy with an alignment output.
+// tiles (Layout::VP).  want_align: greedy with an alignment output.  score_len: the target length of
+// casr_score (validated by the caller), 0 for the other callers.
 inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align, const casr_config& cfg, int VP,
-                              const Tuning& t, const BlobFacts& blob, const AttnStaticLds& lds) {
+                              const Tuning& t, const BlobFacts& blob, const AttnStaticLds& lds, int score_len = 0) {
   DecodePlan p{};
   const int V = cfg.vocab, L = cfg.max_len;
   const bool greedy = caller == PLAN_GREEDY, beam = caller == PLAN_BEAM;
@@ -183,6 +215,7 @@ inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align,
   p.B = B;
   p.Tp = Tp;
   p.k = k;
+  p.score_len = caller == PLAN_SCORE ? score_len : 0;
   if (k < 1 || k > KMAX_BEAM) {
     p.status = PLAN_BAD_K;
     return p;
@@ -204,7 +237,7 @@ inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align,
   // the beam guards, never the greedy clause (its fused GEMM would pick the one-accumulator shapes)
   const bool fold_beam = beam && R >= 1024 && blob.proj_small && blob.dec_small && p.kpb >= 4;
   // (a vocabulary beyond the 64 seven-tile partial blocks of the fused GEMM keeps the three-launch step)
-  const int fold_blocks = fold_gtile0(V) / FOLD_NT;
+  const int VT = fold_vtiles(V), VG = fold_gtile0(V), fold_blocks = VG / FOLD_NT;
   const bool fold_vocab = fold_blocks <= GP_NB;
   // the folded greedy attention (attention_kernel<1, 1>) holds its cell-phase area on top of the
   // three-launch step's LDS: at Tp where only the latter fits, greedy keeps the three-launch step
@@ -216,11 +249,31 @@ inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align,
   // caller builds first); the beam fold's one-accumulator shapes and its s16 query need the s16 images
   p.build_fold32 = fold_shape && greedy && !p.s16;
   p.fold = fold_shape && (p.s16 ? blob.s16_images != 0 : greedy);
+  // the decode GEMM launches.  The LSTMCell: 4 gate tiles per 16 units, and one query partial per row
+  // from each of its column blocks; the projection over R rows (casr_score: score_len x B at once)
+  p.lstm = plan_dgemm(dec_lstm_shape(R), R, FOLD_GT, FOLD_GT, KDEC);
+  p.q_slots = HD / (4 * DG_SHAPES[p.lstm.shape].NT);
+  const int RP = caller == PLAN_SCORE ? p.score_len * B : R;
+  if (!p.fold) p.proj = plan_dgemm(proj_shape(RP, p.s16 && p.proj_small), RP, VP / 16, VP / 16, KPROJ);
+  // greedy fold at R <= 32 (CASR_OPT_DEC_KSPLIT): DG_KS blocks per 32 x 112 output block while the
+  // launch's column blocks fit the arrival counters
+  const bool ks = greedy && R <= 32 && t[CASR_OPT_DEC_KSPLIT];
+  auto fold_gemm = [&](int cover) {
+    const DgemmPlan g = plan_dgemm(fold_gemm_shape(beam, R, false), R, VG + FOLD_GT, cover, KPROJ);
+    return ks && g.NB <= DG_KS_GROUPS ? plan_dgemm(fold_gemm_shape(beam, R, true), R, VG + FOLD_GT, cover, KPROJ) : g;
+  };
+  if (p.fold) {
+    p.fold_gates = fold_gemm(VG + FOLD_GT);
+    p.fold_last = fold_gemm(VT);
+    p.ksplit = p.fold_gates.shape == DG_FOLD_32x112_KS;
+    p.ksplit_last = p.fold_last.shape == DG_FOLD_32x112_KS;
+  }
   // per-block row partials from the projection epilogue: the vocabulary must fit the 64 partial
-  // blocks; beam search uses them at temperature 1 only (they are of x, not x / T).  The folded
-  // step's: one per 7-tile wave column in every shape; the three-launch step's: one per 5-tile wave
-  // column in every launch_proj shape, so the select's partial sums do not depend on R
-  const int blocks = p.fold ? fold_blocks : (VP / 16 + 4) / 5;
+  // blocks; beam search uses them at temperature 1 only (they are of x, not x / T).  One per wave
+  // column of the planned shape over the vocabulary's tiles (the same in every shape of a class, so
+  // the select's partial sums do not depend on R)
+  const DgShape& psh = DG_SHAPES[p.fold ? p.fold_gates.shape : p.proj.shape];
+  const int blocks = ((p.fold ? VT : VP / 16) + dg_wave_tiles(psh) - 1) / dg_wave_tiles(psh);
   p.partials = blocks <= GP_NB && (!beam || cfg.temperature == 1.0f);
   p.nbp = p.partials ? blocks : 0;
   if (caller == PLAN_SCORE && !p.partials) {
@@ -235,12 +288,6 @@ inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align,
   // k = 8 at 4 rows per attention block (both blocks of an utterance run the select, CELL 4)
   if (beam)
     p.fuse_select = p.fold && t[CASR_OPT_FUSE_SELECT] && (k == 4 || k == 8) && (p.kpb == k || (k == 8 && p.kpb == 4));
-  // greedy fold at R <= 32 (CASR_OPT_DEC_KSPLIT): DG_KS blocks per 32 x 112 output block while the
-  // launch's column blocks fit the arrival counters
-  if (greedy && p.fold && R <= 32 && t[CASR_OPT_DEC_KSPLIT]) {
-    p.ksplit = (fold_gtile0(V) + FOLD_GT + FOLD_NT - 1) / FOLD_NT <= DG_KS_GROUPS;
-    p.ksplit_last = fold_blocks <= DG_KS_GROUPS;
-  }
   // greedy fold at R <= 64 (CASR_OPT_ATTN_SPLIT; 1: ranges by R, 2..AT_SPLIT_MAX: that many): ranges
   // of a multiple of 4 steps; not with an alignment output, and a short input stays unsplit
   if (greedy && p.fold && R <= 64 && t[CASR_OPT_ATTN_SPLIT] && !p.align) {
@@ -266,7 +313,7 @@ struct DecodeBufs {
   float* st[2];          // [R][ST]
   float* logits;         // [R][V]
   GreedyPart part;       // per-block row partials of the projection (after the logits)
-  float* qpart;          // [dec_q_slots(R)][R][A] attention query partials, one per LSTMCell column block
+  float* qpart;          // [plan.q_slots][R][A] attention query partials, one per LSTMCell column block
   int32_t* tok[2];       // [R]
   int32_t* src[2];       // [R]
   float* score[2];       // [R]
@@ -325,11 +372,12 @@ class Carver {
 
 // Each carve_*(base, ...) fills its pointers from base (nullptr: sizes only) and returns the bytes.
 // st [2][R][ST] | qpart
-inline size_t carve_state(void* base, int R, DecodeBufs& d) {
+inline size_t carve_state(void* base, const DecodePlan& p, DecodeBufs& d) {
   Carver c(base);
-  d.st[0] = c.rows((size_t)R * ST);
-  d.st[1] = c.rows((size_t)R * ST);
-  d.qpart = c.rows((size_t)dec_q_slots(R) * R * A);
+  const size_t R = (size_t)p.R;
+  d.st[0] = c.rows(R * ST);
+  d.st[1] = c.rows(R * ST);
+  d.qpart = c.rows((size_t)p.q_slots * R * A);
   return c.bytes();
 }
 // logits | row partials | tile maxima

@@ -95,7 +95,7 @@ __device__ __forceinline__ bool xcd_tile(int NB, int NR, int& nb, int& rb, int L
   return nb < NB;
 }
 
-inline unsigned xcd_grid(int NB, int NR) { return (unsigned)(8 * ((NB + 7) / 8) * NR); }
+// (the launch's grid: xcd_grid, decode_gemm_shapes.h)
 
 // lds_dma16 (casr_common.h): global_load_lds_dwordx4 from inline asm
 
@@ -164,20 +164,21 @@ template <int WR, int NT, int S, class ASrc, class Epi, bool S16 = false, int RS
 __global__ __launch_bounds__(512, 2) void dgemm_kernel(int NB, int NR, int ntiles, int nkt,
                                                     const float* __restrict__ Wf, ASrc asrc, Epi epi,
                                                     f32x4* __restrict__ kspart, int* __restrict__ kscnt) {
-  constexpr int KQ = 8 / (WR * WC), QPW = 4 / KQ, BM = 16 * WR * RS, NTW = NT / WC;
-  static_assert(WR * WC * KQ == 8 && NT % WC == 0 && KQ <= 4, "8 waves = row groups x column groups x k slices");
+  // the shape's arithmetic is the shape table's (decode_gemm_shapes.h), which the decode plan reads too
+  constexpr DgShape SH{"", WR, NT, S, RS, WC, IL, BKW, ONE, SA, KS};
+  constexpr int KQ = dg_k_slices(SH), QPW = 4 / KQ, BM = dg_block_rows(SH), NTW = dg_wave_tiles(SH);
+  static_assert(dg_shape_ok(SH), "8 waves = row groups x column groups x k slices; the ring fits the LDS");
   constexpr bool B32 = BKW == 32;
-  static_assert(BKW == 64 || (B32 && S16), "32-deep stages: s16 images only");
-  static_assert(!ONE || S16, "one accumulator: s16 images only");
+  static_assert(S16 || !dg_s16_only(SH), "32-deep stages, one accumulator: s16 images only");
   constexpr int WFR = B32 ? FRAG / 2 : FRAG;       // W floats of one column tile per stage
   constexpr int RPI = B32 ? 8 : 4, WPI = B32 ? 2 : 4;  // A rows / W DMA instructions per 1 KB DMA
-  constexpr int ATILE = BM * BKW, WTILE = NT * WFR;
+  constexpr int ATILE = dg_a_tile(SH), WTILE = dg_w_tile(SH);
+  static_assert(FRAG == DG_FRAG && WTILE == NT * WFR, "the shape table's W fragment block");
   constexpr int STG = ATILE + WTILE;          // floats per stage: [A tile | W tile]
   constexpr int NA = BM / RPI, NDMA = NA + WPI * NT;  // DMA instructions per stage: A + W
   constexpr int NSLOT = (NDMA + 7) / 8;      // per wave (at most)
   const int nkb = B32 ? nkt / 2 : nkt;        // 64-deep fragment blocks per W column tile
   static_assert(S >= 2 && S <= 6, "ring of 2..6 stage buffers");
-  static_assert((S * STG + (SA - S) * ATILE) * 4 <= 160 * 1024, "ring fits the LDS");
   static_assert((S - 2) * NSLOT < 64, "vmcnt range");
   constexpr bool ASYM = SA > S;
   constexpr int JA = NA / 8;  // ASYM: slots j < JA are A DMAs in every wave, the rest W
@@ -562,32 +563,20 @@ __global__ __launch_bounds__(512, 2) void dgemm_kernel(int NB, int NR, int ntile
   stamp(4);
 }
 
-template <int WR, int NT, int S, int RS = 1, int WC = 1, bool IL = false, int BKW = 64, bool ONE = false, int SA = S,
-          int KS = 1, class ASrc, class Epi>
-static void launch_dg(int NB, int R, int ntiles, int nkt, const float* Wf, const ASrc& asrc, const Epi& epi,
-                      int s16, hipStream_t s, f32x4* kspart = nullptr, int* kscnt = nullptr) {
-  constexpr int BM = 16 * WR * RS;
-  const int NR = (R + BM - 1) / BM;
-  if constexpr (KS > 1) {  // (64-deep stages, nkt % KS == 0: the host's check)
-    if (s16)
-      hipLaunchKernelGGL((dgemm_kernel<WR, NT, S, ASrc, Epi, true, RS, WC, IL, 64, false, S, KS>),
-                         dim3(xcd_grid(NB, NR) * KS), dim3(512), 0, s, NB, NR, ntiles, nkt, Wf, asrc, epi, kspart, kscnt);
-    else
-      hipLaunchKernelGGL((dgemm_kernel<WR, NT, S, ASrc, Epi, false, RS, WC, false, 64, false, S, KS>),
-                         dim3(xcd_grid(NB, NR) * KS), dim3(512), 0, s, NB, NR, ntiles, nkt, Wf, asrc, epi, kspart, kscnt);
-    return;
-  }
-  if constexpr (BKW == 32 || ONE) {  // s16 only (the f32 form of the same shape does not fit the LDS)
-    hipLaunchKernelGGL((dgemm_kernel<WR, NT, S, ASrc, Epi, true, RS, WC, IL, BKW, ONE, SA>), dim3(xcd_grid(NB, NR)),
-                       dim3(512), 0, s, NB, NR, ntiles, nkt * (64 / BKW), Wf, asrc, epi, nullptr, nullptr);
-  } else {
-    if (s16)
-      hipLaunchKernelGGL((dgemm_kernel<WR, NT, S, ASrc, Epi, true, RS, WC, IL>), dim3(xcd_grid(NB, NR)), dim3(512), 0,
-                         s, NB, NR, ntiles, nkt, Wf, asrc, epi, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL((dgemm_kernel<WR, NT, S, ASrc, Epi, false, RS, WC>), dim3(xcd_grid(NB, NR)), dim3(512), 0, s,
-                         NB, NR, ntiles, nkt, Wf, asrc, epi, nullptr, nullptr);
-  }
+// One launch of shape ID (decode_gemm_shapes.h) as the plan laid it out (grid, block counts, tiles
+// and stages: DgemmPlan).  What is left to choose here is the arithmetic's kernel: the f32 kernel of
+// a shape has no IL, and the 32-deep and one-accumulator shapes have the s16 kernel only (their f32
+// form would not fit the LDS; the plan never picks them under f32).  kspart, kscnt: the k split's.
+template <int ID, class ASrc, class Epi>
+static void launch_dg(const DgemmPlan& g, const float* Wf, const ASrc& asrc, const Epi& epi, int s16, hipStream_t s,
+                      f32x4* kspart = nullptr, int* kscnt = nullptr) {
+  constexpr DgShape H = DG_SHAPES[ID];
+  if (dg_s16_only(H) || s16)
+    hipLaunchKernelGGL((dgemm_kernel<H.WR, H.NT, H.S, ASrc, Epi, true, H.RS, H.WC, H.IL != 0, H.BKW, H.ONE != 0, H.SA, H.KS>),
+                       dim3(g.grid), dim3(512), 0, s, g.NB, g.NR, g.ntiles, g.nkt, Wf, asrc, epi, kspart, kscnt);
+  else if constexpr (!dg_s16_only(H))
+    hipLaunchKernelGGL((dgemm_kernel<H.WR, H.NT, H.S, ASrc, Epi, false, H.RS, H.WC, false, 64, false, H.S, H.KS>),
+                       dim3(g.grid), dim3(512), 0, s, g.NB, g.NR, g.ntiles, g.nkt, Wf, asrc, epi, kspart, kscnt);
 }
 
 // A rows of the decoder LSTM: [embed(tok[r]) | st_old[src[r]][0:1024] = ctx | h]; a 64-deep
@@ -697,7 +686,7 @@ struct DecLstmEpi {
   DecLstmA rows;      // guarded predecessor lookup
   const int32_t* newdone;
   const float* w_hidden;  // [HD][A]
-  float* qpart;           // [dec_q_slots(R)][R][A]
+  float* qpart;           // [DecodePlan::q_slots][R][A]: one slot per column block of the planned shape
   int R, l, total;
   int hw = 0;  // s16x3 arithmetic: the hardware-exp cell (casr_common.h lstm_cell_hw, as the encoder's)
   // operands loaded before the k loop: gate biases, predecessor rows, this lane's W_hidden
@@ -748,7 +737,7 @@ struct DecLstmEpi {
     constexpr int UG = NTN / 4;
     // per row-slab wave (<= 8 per block): the h tile [row][unit] of its UG unit groups.  The query
     // partial of each 16-unit group is its own MFMA chain; a two-group block stores their sum in
-    // slot nb (dec_q_slots), which is the pair sum the attention forms from two 16-unit slots, so
+    // slot nb (DecodePlan::q_slots), which is the pair sum the attention forms from two 16-unit slots, so
     // q has the same bits at every R
     __shared__ float ht[8][16][16 * UG + 1];
     const int lane = threadIdx.x & 63, ws = (row0 >> 4) & 7, g = lane >> 4;
@@ -1552,6 +1541,9 @@ __global__ void beam_records_kernel(int B, int k, int L, const int32_t* __restri
 }
 
 // ------------------------------------------------------------------ decode GEMM launch shapes
+// Which shape runs at which R is decided by plan_decode (decode_plan.h: dec_lstm_shape, proj_shape,
+// fold_gemm_shape) from the shape table (decode_gemm_shapes.h); the launchers below map the planned
+// shape of their class to its kernel and decide nothing.  What was measured for each rule:
 // Tile choice per row count (one 512-thread block per CU, 256 blocks at R = 256):
 //   LSTMCell (N = 2048, 16 units x 4 gates per block): R <= 256: 32 rows, ring 4; R <= 512:
 //   64 rows, ring 4; else 128 rows, ring 3.
@@ -1571,32 +1563,40 @@ __global__ void beam_records_kernel(int B, int k, int L, const int32_t* __restri
 // blocks), 1.59 for 32 x 64 ring 6 (LDS then admits one of its 2.5 blocks per CU); the LSTMCell
 // is 0.92 at ring 2, 4 and 6 alike: past one tile in flight a CU's intake from MALL/HBM-latency
 // sources does not grow with depth (about 26-35 GB/s per CU in every variant).
+// LSTMCell at R >= 2048: 128 rows x 128 columns (two 16-unit groups), two 64-deep stages: at
+// R = 2048 one round of 256 blocks, 1.3 MB per block, instead of two rounds of 128 x 64 blocks
+// (ring 3) at 0.98 MB each (at R = 1024 the 128 x 64 blocks are one round: 256 blocks)
+// Projection at R <= 32 (BASELINE config 2): 32-row blocks, so no block stages and multiplies 32
+// padding rows.  s16 at R >= 2048 with |W_p| < 16: 256 x 160 blocks of 32-deep stages, ring 3, one
+// accumulator (one round of 256 blocks at R = 2048, 1.7 MB per block, against two rounds of
+// 128 x 160 blocks at 1.2 MB each; at R = 1024 the 128 x 160 blocks are one round: 256 blocks)
+// (each launcher: the planned shape of its own class, else an error: a plan of another class)
 template <class ASrc, class Epi>
-static void launch_dec_lstm(int R, const float* Wf, const ASrc& asrc, const Epi& epi, int s16, hipStream_t s) {
-  const int NB = HD / 16, ntiles = 4 * NB, nkt = KDEC / DG_BK;
-  if (R <= 256) launch_dg<2, 4, 4>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  else if (R <= 512) launch_dg<4, 4, 4>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  else if (!dec_wide(R)) launch_dg<8, 4, 3, 1, 1, true>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  // R >= 2048: 128 rows x 128 columns (two 16-unit groups), two 64-deep stages: at R = 2048 one
-  // round of 256 blocks, 1.3 MB per block, instead of two rounds of 128 x 64 blocks (ring 3) at
-  // 0.98 MB each (at R = 1024 the 128 x 64 blocks are one round: 256 blocks)
-  else launch_dg<8, 8, 2, 1, 1, true>(NB / 2, R, ntiles, nkt, Wf, asrc, epi, s16, s);
+static hipError_t launch_dec_lstm(const DgemmPlan& g, const float* Wf, const ASrc& asrc, const Epi& epi, int s16,
+                                  hipStream_t s) {
+  switch (g.shape) {
+    case DG_LSTM_32x64: launch_dg<DG_LSTM_32x64>(g, Wf, asrc, epi, s16, s); break;
+    case DG_LSTM_64x64: launch_dg<DG_LSTM_64x64>(g, Wf, asrc, epi, s16, s); break;
+    case DG_LSTM_128x64: launch_dg<DG_LSTM_128x64>(g, Wf, asrc, epi, s16, s); break;
+    case DG_LSTM_128x128: launch_dg<DG_LSTM_128x128>(g, Wf, asrc, epi, s16, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipSuccess;
 }
 
 template <class ASrc, class Epi>
-static void launch_proj(int R, int ntiles, const float* Wf, const ASrc& asrc, const Epi& epi, int s16, int small_w,
-                        hipStream_t s) {
-  const int nkt = KPROJ / DG_BK, NB = (ntiles + 4) / 5;  // 5 column tiles per block (10 at R > 512)
-  // R <= 32 (BASELINE config 2): 32-row blocks, so no block stages and multiplies 32 padding rows
-  if (R <= 32) launch_dg<2, 5, 4>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  else if (R <= 256) launch_dg<4, 5, 4>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  else if (R <= 512) launch_dg<8, 5, 3>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  else if (!s16 || !small_w) launch_dg<4, 10, 2, 2, 2, true>((ntiles + 9) / 10, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  else if (!dec_wide(R)) launch_dg<4, 10, 2, 2, 2, true, 64, true>((ntiles + 9) / 10, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  // s16 at R >= 2048 with |W_p| < 16: 256 x 160 blocks of 32-deep stages, ring 3, one accumulator
-  // (one round of 256 blocks at R = 2048, 1.7 MB per block, against two rounds of 128 x 160 blocks
-  // at 1.2 MB each; at R = 1024 the 128 x 160 blocks are one round: 256 blocks)
-  else launch_dg<4, 10, 3, 4, 2, true, 32, true>((ntiles + 9) / 10, R, ntiles, nkt, Wf, asrc, epi, s16, s);
+static hipError_t launch_proj(const DgemmPlan& g, const float* Wf, const ASrc& asrc, const Epi& epi, int s16,
+                              hipStream_t s) {
+  switch (g.shape) {
+    case DG_PROJ_32x80: launch_dg<DG_PROJ_32x80>(g, Wf, asrc, epi, s16, s); break;
+    case DG_PROJ_64x80: launch_dg<DG_PROJ_64x80>(g, Wf, asrc, epi, s16, s); break;
+    case DG_PROJ_128x80: launch_dg<DG_PROJ_128x80>(g, Wf, asrc, epi, s16, s); break;
+    case DG_PROJ_128x160: launch_dg<DG_PROJ_128x160>(g, Wf, asrc, epi, s16, s); break;
+    case DG_PROJ_128x160_ONE: launch_dg<DG_PROJ_128x160_ONE>(g, Wf, asrc, epi, s16, s); break;
+    case DG_PROJ_256x160_ONE: launch_dg<DG_PROJ_256x160_ONE>(g, Wf, asrc, epi, s16, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipSuccess;
 }
 
 // the folded step's GEMM (KB) over the 441 tiles (313 vocabulary + 128 gate) of the fused image.
@@ -1606,26 +1606,25 @@ static void launch_proj(int R, int ntiles, const float* Wf, const ASrc& asrc, co
 // 1.29-1.34 against 1.00 ms per greedy batch).  Beam (one-accumulator s16x3, 32-deep stages, wave tiles of
 // 16 RS rows x 112 columns, the 7-tile column blocks of the greedy shapes): 256 x 224 blocks, a W ring
 // of two 28 KB stages and an A ring of three 32 KB stages (dgemm_kernel SA), at R >= 2048 (8 x 32 = 256 blocks at R = 2048, 1.97 MB each against 1.7 MB
-// + 1.3 MB); 128 x 224, ring of three, below (R = 1024: 256 blocks)
-constexpr int FOLD_NT_BEAM = 2 * FOLD_NT;
+// + 1.3 MB); 128 x 224, ring of three, below (R = 1024: 256 blocks; 128 x 224 in two rounds at
+// R = 2048 measured 12.07 against 11.47 ms per batch).  The A ring of three beside the W ring of two
+// (152 KB): fused GEMM 3.96-4.02 -> 3.88-3.92 ms per beam batch (interleaved A/B, two rounds; a
+// version unrolled by 6 with static A buffers spilled 11 VGPRs).
+// Greedy: s16x3, or the exact-f32 MFMAs on the f32 fused image; the k split (DecodePlan::ksplit,
+// R <= 32, NB <= DG_KS_GROUPS): DG_KS blocks per 32 x 112 output block.
 template <class ASrc, class Epi>
-static void launch_fold_gemm(int R, bool beam, int NB, int ntiles, const float* Wf, const ASrc& asrc, const Epi& epi,
-                             int s16, hipStream_t s, f32x4* kspart = nullptr, int* kscnt = nullptr) {
-  const int nkt = KPROJ / DG_BK;
-  if (!beam) {  // (greedy: s16x3, or the exact-f32 MFMAs on the f32 fused image)
-    // the k split (DecodePlan::ksplit, R <= 32, NB <= DG_KS_GROUPS): DG_KS blocks per 32 x 112 output block
-    static_assert(DG_BK == 64, "decode_plan.h checks KPROJ / 64 % DG_KS");
-    if (kspart)
-      launch_dg<2, FOLD_NT, 3, 1, 1, false, 64, false, 3, DG_KS>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s, kspart, kscnt);
-    else if (R <= 32) launch_dg<2, FOLD_NT, 3>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-    else launch_dg<4, FOLD_NT, 3>(NB, R, ntiles, nkt, Wf, asrc, epi, s16, s);
-  } else if (dec_wide(R)) {  // (128 x 224 in two rounds at R = 2048 measured 12.07 against 11.47 ms per batch)
-    // A ring of three beside the W ring of two (152 KB): fused GEMM 3.96-4.02 -> 3.88-3.92 ms per beam
-    // batch (interleaved A/B, two rounds; a version unrolled by 6 with static A buffers spilled 11 VGPRs)
-    launch_dg<4, FOLD_NT_BEAM, 2, 4, 2, true, 32, true, 3>(NB, R, ntiles, nkt, Wf, asrc, epi, 1, s);
-  } else {
-    launch_dg<4, FOLD_NT_BEAM, 3, 2, 2, true, 32, true>(NB, R, ntiles, nkt, Wf, asrc, epi, 1, s);
+static hipError_t launch_fold_gemm(const DgemmPlan& g, const float* Wf, const ASrc& asrc, const Epi& epi, int s16,
+                                   hipStream_t s, f32x4* kspart, int* kscnt) {
+  static_assert(DG_BK == 64, "decode_plan.h checks KPROJ / 64 % DG_KS");
+  switch (g.shape) {
+    case DG_FOLD_32x112_KS: launch_dg<DG_FOLD_32x112_KS>(g, Wf, asrc, epi, s16, s, kspart, kscnt); break;
+    case DG_FOLD_32x112: launch_dg<DG_FOLD_32x112>(g, Wf, asrc, epi, s16, s); break;
+    case DG_FOLD_64x112: launch_dg<DG_FOLD_64x112>(g, Wf, asrc, epi, s16, s); break;
+    case DG_FOLD_256x224_ONE: launch_dg<DG_FOLD_256x224_ONE>(g, Wf, asrc, epi, s16, s); break;
+    case DG_FOLD_128x224_ONE: launch_dg<DG_FOLD_128x224_ONE>(g, Wf, asrc, epi, s16, s); break;
+    default: return hipErrorInvalidValue;
   }
+  return hipSuccess;
 }
 
 // ------------------------------------------------------------------ host drivers
@@ -1644,6 +1643,7 @@ static hipError_t decode_step(const DecodeArgs& a, DecodeBufs& d, int l, int tot
   const int R = a.B * a.k;
   const float* st_old = d.st[l & 1];
   float* st_new = d.st[(l + 1) & 1];
+  hipError_t e;
   {
     ProfScope ps(a.prof, CASR_K_DEC_LSTM, s);
     DecLstmA asrc{a.W + (a.plan.s16 ? a.L.emb16 : a.L.emb), st_old, d.tok[l & 1], d.src[l & 1], d.err, R, a.V, a.plan.s16};
@@ -1653,9 +1653,9 @@ static hipError_t decode_step(const DecodeArgs& a, DecodeBufs& d, int l, int tot
     }
     DecLstmEpi epi{a.W + a.L.dec_b, st_old, st_new, asrc, d.newdone, a.W + a.L.w_hidden, d.qpart, R, l, total};
     epi.hw = a.plan.s16;
-    launch_dec_lstm(R, a.W + (a.plan.s16 ? a.L.dec_w16 : a.L.dec_w), asrc, epi, a.plan.s16, s);
+    e = launch_dec_lstm(a.plan.lstm, a.W + (a.plan.s16 ? a.L.dec_w16 : a.L.dec_w), asrc, epi, a.plan.s16, s);
   }
-  hipError_t e;
+  if (e != hipSuccess) return e;
   {
     ProfScope ps(a.prof, CASR_K_ATTENTION, s);
     e = launch_attention_step(a, st_new, d.qpart, align, d.newdone, l, total, s);
@@ -1667,7 +1667,8 @@ static hipError_t decode_step(const DecodeArgs& a, DecodeBufs& d, int l, int tot
     // greedy: per-block partials instead of logits; beam at temperature 1: logits and partials
     ProjEpi epi{a.W + a.L.proj_b, a.plan.store_logits ? d.logits : nullptr, d.newdone, R, a.V, l, total, d.err,
                 plan_partials(a, d)};
-    launch_proj(R, a.L.VP / 16, a.W + (a.plan.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.plan.s16, a.plan.proj_small, s);
+    e = launch_proj(a.plan.proj, a.W + (a.plan.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.plan.s16, s);
+    if (e != hipSuccess) return e;
   }
   return hipGetLastError();
 }
@@ -1722,21 +1723,17 @@ void dg_trace_dump() {
 // the folded greedy step's GEMM (KB) on st_new = [ctx | h] of step l: partials of step l and, unless
 // l is the last step, the next step's gate pre-activations
 // beam: logits, and at temperature 1 the row partials and tile maxima, as decode_step's projection
-static void fold_gemm_step(const DecodeArgs& a, DecodeBufs& d, int l, int total, hipStream_t s) {
-  const int R = a.B * a.k;
-  const bool beam = a.plan.caller == PLAN_BEAM;
-  const int VT = fold_vtiles(a.V), VG = fold_gtile0(a.V), NT = beam ? FOLD_NT_BEAM : FOLD_NT;
-  const bool gates = l + 1 < a.max_len;
-  const int ntiles = VG + FOLD_GT;
-  const int NB = ((gates ? ntiles : VT) + NT - 1) / NT;
+static hipError_t fold_gemm_step(const DecodeArgs& a, DecodeBufs& d, int l, int total, hipStream_t s) {
+  const int R = a.plan.R;
+  const DgemmPlan& g = l + 1 < a.max_len ? a.plan.fold_gates : a.plan.fold_last;
   ProfScope ps(a.prof, CASR_K_PROJ, s);
   ProjA asrc{d.st[(l + 1) & 1], R, a.plan.s16};
-  FoldEpi epi{a.W + a.L.proj_b, d.newdone, R, a.V, VT, l, total, d.err, plan_partials(a, d), a.fb.gates,
-              a.plan.store_logits ? d.logits : nullptr, VG};
-  const bool ks = gates ? a.plan.ksplit : a.plan.ksplit_last;
+  FoldEpi epi{a.W + a.L.proj_b, d.newdone, R, a.V, fold_vtiles(a.V), l, total, d.err, plan_partials(a, d), a.fb.gates,
+              a.plan.store_logits ? d.logits : nullptr, fold_gtile0(a.V)};
   dg_trace_step_gate(l, true, s);
-  launch_fold_gemm(R, beam, NB, ntiles, a.fb.wfold, asrc, epi, a.plan.s16, s, ks ? reinterpret_cast<f32x4*>(d.kspart) : nullptr, d.kscnt);
+  const hipError_t e = launch_fold_gemm(g, a.fb.wfold, asrc, epi, a.plan.s16, s, reinterpret_cast<f32x4*>(d.kspart), d.kscnt);
   dg_trace_step_gate(l, false, s);
+  return e;
 }
 
 // the folded step's attention with its cell prologue (steps l >= 1): greedy with the fused select
@@ -1778,10 +1775,10 @@ static hipError_t run_greedy_fold(const DecodeArgs& a, DecodeBufs& d, int32_t* t
   for (int l = 0; l < a.max_len; ++l) {
     float* al = align ? align + (size_t)l * a.Tp * R : nullptr;
     const GreedySel gs{d.part, nbp, l - 1, a.max_len, a.eos, finished, out_len, accum, tokens, d.newdone};
-    const hipError_t e = l == 0 ? decode_step(a, d, 0, R, al, s, nullptr, false)
-                                : fold_attention_step(a, d, l, R, al, fuse, gs, s);
+    hipError_t e = l == 0 ? decode_step(a, d, 0, R, al, s, nullptr, false)
+                          : fold_attention_step(a, d, l, R, al, fuse, gs, s);
+    if (e == hipSuccess) e = fold_gemm_step(a, d, l, R, s);
     if (e != hipSuccess) return e;
-    fold_gemm_step(a, d, l, R, s);
     if (fuse && l + 1 < a.max_len) continue;
     ProfScope ps(a.prof, CASR_K_SELECT, s);
     hipLaunchKernelGGL(greedy_select_part_kernel, dim3((R + 3) / 4), dim3(256), 0, s, d.part, nbp, a.V, R, l,
@@ -1862,13 +1859,14 @@ hipError_t score_steps(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, 
 // of the history, so the step projection's A source (ProjA) serves unchanged
 hipError_t score_project(const DecodeArgs& a, const DecodeBufs& d, const ScoreBufs& sb, int L, hipStream_t s) {
   const int R = L * a.B;
+  if (a.plan.caller != PLAN_SCORE || a.plan.score_len != L) return hipErrorInvalidValue;  // a.plan.proj: L B rows
   ProfScope ps(a.prof, CASR_K_PROJ, s);
   ProjA asrc{sb.hist + (size_t)a.B * ST, R, a.plan.s16};
   GreedyPart gp = sb.part;
   gp.tmx = nullptr;
   ScoreEpi epi{a.W + a.L.proj_b, R, a.V, d.err, gp, sb.xsum, sb.tgt, sb.tl};
-  launch_proj(R, a.L.VP / 16, a.W + (a.plan.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.plan.s16, a.plan.proj_small, s);
-  return hipGetLastError();
+  const hipError_t e = launch_proj(a.plan.proj, a.W + (a.plan.s16 ? a.L.proj_w16 : a.L.proj_w), asrc, epi, a.plan.s16, s);
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 // the select of step l: logits and partials of step l's GEMM, scores of step l in, step l + 1's
@@ -1914,8 +1912,8 @@ hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float l
       const BeamSelArgs bs = beam_sel_args(a, d, l - 1);
       e = fold_attention_step(a, d, l, a.B, nullptr, false, GreedySel{}, s, fsel ? &bs : nullptr);
     }
+    if (e == hipSuccess && a.plan.fold) e = fold_gemm_step(a, d, l, a.B, s);
     if (e != hipSuccess) return e;
-    if (a.plan.fold) fold_gemm_step(a, d, l, a.B, s);
     if (fsel && l + 1 < a.max_len) continue;
     ProfScope ps(a.prof, CASR_K_SELECT, s);
     switch (a.plan.K2) {

@@ -5,6 +5,8 @@
 // The expected values are the decisions the drivers made before the plan existed (prepare_decode,
 // decoder.hip's row_partials / proj_col_blocks / fsel, attention.hip's attention_kpb), read from that
 // code and worked out by hand here; the sizes in check_carving are that code's allocation formulas.
+// The decode GEMM shapes, grids and arguments (check_shape_table, check_gemm_plans) are those of the
+// block-shape ladders decoder.hip's launchers held before the plan named them.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,7 +28,7 @@ using namespace casr;
 struct In {
   int caller = PLAN_GREEDY, B = 256, Tp = 266, k = 1;
   bool align = false;
-  int V = 5004, L = 40;
+  int V = 5004, L = 40, score_len = 0;
   float T = 1.f;
   Tuning t;
   BlobFacts blob{1, 1, 1, 1};
@@ -53,7 +55,23 @@ static DecodePlan plan(const In& in) {
   cfg.vocab = in.V;
   cfg.max_len = in.L;
   cfg.temperature = in.T;
-  return plan_decode(in.caller, in.B, in.Tp, in.k, in.align, cfg, (in.V + 63) / 64 * 64, in.t, in.blob, kLds);
+  return plan_decode(in.caller, in.B, in.Tp, in.k, in.align, cfg, (in.V + 63) / 64 * 64, in.t, in.blob, kLds,
+                     in.score_len);
+}
+static In score(int B, int L) {
+  In in;
+  in.caller = PLAN_SCORE;
+  in.B = B;
+  in.score_len = L;
+  return in;
+}
+static In with_blob(In in, BlobFacts b) {
+  in.blob = b;
+  return in;
+}
+static In with_vocab(In in, int V) {
+  in.V = V;
+  return in;
 }
 
 static void check_greedy() {
@@ -201,6 +219,183 @@ static void check_score() {
   EXPECT(plan(in).status == PLAN_VOCAB);
 }
 
+// ---------------------------------------------------------------- the decode GEMM shapes
+// Expected values: the block-shape ladders the launchers of decoder.hip held before the plan named
+// the shapes (launch_dec_lstm, launch_proj, launch_fold_gemm, launch_dg), worked out by hand.
+// At V = 5004: 316 projection tiles (VP = 5056), 313 vocabulary tiles, the gate tiles from tile 315,
+// 443 tiles of the fused image; 128 LSTM gate tiles; 20 / 16 64-deep k tiles (K = 1280 / 1024).
+static bool same(const DgemmPlan& g, int shape, int NB, int NR, int grid, int ntiles, int nkt) {
+  return g.shape == shape && g.NB == NB && g.NR == NR && g.grid == grid && g.ntiles == ntiles && g.nkt == nkt;
+}
+static bool unused(const DgemmPlan& g) { return same(g, 0, 0, 0, 0, 0, 0); }
+
+static void check_shape_table() {
+  // dgemm_kernel's template arguments of each rung: WR NT S RS WC IL BKW ONE SA KS
+  const int want[DG_SHAPE_COUNT][10] = {
+      {2, 4, 4, 1, 1, 0, 64, 0, 4, 1},    // LSTMCell R <= 256          <2,4,4>
+      {4, 4, 4, 1, 1, 0, 64, 0, 4, 1},    //          R <= 512          <4,4,4>
+      {8, 4, 3, 1, 1, 1, 64, 0, 3, 1},    //          R < 2048          <8,4,3,1,1,IL>
+      {8, 8, 2, 1, 1, 1, 64, 0, 2, 1},    //          R >= 2048         <8,8,2,1,1,IL>
+      {2, 5, 4, 1, 1, 0, 64, 0, 4, 1},    // projection R <= 32         <2,5,4>
+      {4, 5, 4, 1, 1, 0, 64, 0, 4, 1},    //          R <= 256          <4,5,4>
+      {8, 5, 3, 1, 1, 0, 64, 0, 3, 1},    //          R <= 512          <8,5,3>
+      {4, 10, 2, 2, 2, 1, 64, 0, 2, 1},   //          R > 512           <4,10,2,2,2,IL>
+      {4, 10, 2, 2, 2, 1, 64, 1, 2, 1},   //          ... s16, small    <4,10,2,2,2,IL,64,ONE>
+      {4, 10, 3, 4, 2, 1, 32, 1, 3, 1},   //          ... R >= 2048     <4,10,3,4,2,IL,32,ONE>
+      {2, 7, 3, 1, 1, 0, 64, 0, 3, 4},    // fold greedy, k split       <2,7,3,1,1,-,64,-,3,4>
+      {2, 7, 3, 1, 1, 0, 64, 0, 3, 1},    //          R <= 32           <2,7,3>
+      {4, 7, 3, 1, 1, 0, 64, 0, 3, 1},    //          otherwise         <4,7,3>
+      {4, 14, 2, 4, 2, 1, 32, 1, 3, 1},   // fold beam R >= 2048        <4,14,2,4,2,IL,32,ONE,3>
+      {4, 14, 3, 2, 2, 1, 32, 1, 3, 1},   //          otherwise         <4,14,3,2,2,IL,32,ONE>
+  };
+  const int ids[DG_SHAPE_COUNT] = {DG_LSTM_32x64,   DG_LSTM_64x64,       DG_LSTM_128x64,      DG_LSTM_128x128,
+                                   DG_PROJ_32x80,   DG_PROJ_64x80,       DG_PROJ_128x80,      DG_PROJ_128x160,
+                                   DG_PROJ_128x160_ONE, DG_PROJ_256x160_ONE, DG_FOLD_32x112_KS, DG_FOLD_32x112,
+                                   DG_FOLD_64x112,  DG_FOLD_256x224_ONE, DG_FOLD_128x224_ONE};
+  for (int i = 0; i < DG_SHAPE_COUNT; ++i) {
+    EXPECT(ids[i] == i);
+    const DgShape& s = DG_SHAPES[i];
+    const int got[10] = {s.WR, s.NT, s.S, s.RS, s.WC, s.IL, s.BKW, s.ONE, s.SA, s.KS};
+    EXPECT(std::memcmp(got, want[i], sizeof got) == 0 && s.name && s.name[0]);
+    // rows, columns, tiles per wave column, k slices
+    const int BM = 16 * want[i][0] * want[i][3];
+    EXPECT(dg_block_rows(s) == BM && dg_block_cols(s) == 16 * want[i][1]);
+    EXPECT(dg_wave_tiles(s) == want[i][1] / want[i][4] && dg_k_slices(s) * want[i][0] * want[i][4] == 8);
+    // the ring as the kernel's static_assert sized it: S stages of [A | W], SA - S more A tiles
+    const int BKW = want[i][6], atile = BM * BKW, wtile = want[i][1] * (BKW == 32 ? 512 : 1024);
+    const int ring = (want[i][2] * (atile + wtile) + (want[i][8] - want[i][2]) * atile) * 4;
+    EXPECT(dg_ring_bytes(s) == ring && ring <= 160 * 1024 && dg_shape_ok(s));
+    EXPECT(dg_s16_only(s) == (want[i][6] == 32 || want[i][7] == 1));
+    // one partial block width per class
+    if (i >= DG_PROJ_32x80 && i <= DG_PROJ_256x160_ONE) EXPECT(dg_wave_tiles(s) == 5);
+    if (i >= DG_FOLD_32x112_KS) EXPECT(dg_wave_tiles(s) == 7 && dg_wave_tiles(s) == FOLD_NT);
+  }
+  EXPECT(dg_ring_bytes(DG_SHAPES[DG_PROJ_256x160_ONE]) == 159744);  // 3 x (256 x 32 + 10 x 512) floats
+  EXPECT(dg_ring_bytes(DG_SHAPES[DG_FOLD_256x224_ONE]) == 152 * 1024);  // 2 x (8192 + 7168) + 8192 floats
+  EXPECT(dg_ring_bytes(DG_SHAPES[DG_PROJ_128x80]) == 159744 && dg_ring_bytes(DG_SHAPES[DG_LSTM_32x64]) == 98304);
+  EXPECT(xcd_grid(64, 1) == 64 && xcd_grid(45, 4) == 192 && xcd_grid(1, 1) == 8 && xcd_grid(16, 16) == 256);
+}
+
+static void check_gemm_plans() {
+  const BlobFacts f32{0, 1, 1, 1}, big_w{1, 1, 0, 1};
+  auto nofold = [](In in) { return in.opt(CASR_OPT_DEC_FOLD, 0); };
+  // LSTMCell by R (greedy: R = B), either arithmetic; the query slots follow its column blocks
+  const struct { int R, shape, NB, NR, grid, q; } lstm[] = {
+      {32, DG_LSTM_32x64, 32, 1, 32, 32},    {256, DG_LSTM_32x64, 32, 8, 256, 32},
+      {257, DG_LSTM_64x64, 32, 5, 160, 32},  {512, DG_LSTM_64x64, 32, 8, 256, 32},
+      {513, DG_LSTM_128x64, 32, 5, 160, 32}, {2047, DG_LSTM_128x64, 32, 16, 512, 32},
+      {2048, DG_LSTM_128x128, 16, 16, 256, 16}, {4096, DG_LSTM_128x128, 16, 32, 512, 16}};
+  for (const auto& c : lstm)
+    for (const BlobFacts& b : {BlobFacts{1, 1, 1, 1}, f32})
+      for (int fold = 0; fold < 2; ++fold) {
+        const DecodePlan p = plan(with_blob(greedy(c.R).opt(CASR_OPT_DEC_FOLD, fold), b));
+        EXPECT(p.status == PLAN_OK && p.fold == fold && same(p.lstm, c.shape, c.NB, c.NR, c.grid, 128, 20));
+        EXPECT(p.q_slots == c.q && p.q_slots == HD / (4 * DG_SHAPES[p.lstm.shape].NT));
+      }
+  EXPECT(same(plan(beam(256, 8)).lstm, DG_LSTM_128x128, 16, 16, 256, 128, 20) && plan(beam(256, 8)).q_slots == 16);
+  EXPECT(same(plan(beam(40, 8)).lstm, DG_LSTM_64x64, 32, 5, 160, 128, 20) && plan(beam(40, 8)).q_slots == 32);
+
+  // the step projection by R: s16 with every |W_p| < 16, s16 with a large weight, f32
+  // (shape2 ...: what a large weight or f32 plans instead, the two-accumulator 128 x 160 at R > 512)
+  const struct { int R, shape, NB, NR, grid, nkt, shape2, NR2, grid2; } proj[] = {
+      {32, DG_PROJ_32x80, 64, 1, 64, 16, DG_PROJ_32x80, 1, 64},
+      {33, DG_PROJ_64x80, 64, 1, 64, 16, DG_PROJ_64x80, 1, 64},
+      {256, DG_PROJ_64x80, 64, 4, 256, 16, DG_PROJ_64x80, 4, 256},
+      {257, DG_PROJ_128x80, 64, 3, 192, 16, DG_PROJ_128x80, 3, 192},
+      {512, DG_PROJ_128x80, 64, 4, 256, 16, DG_PROJ_128x80, 4, 256},
+      {513, DG_PROJ_128x160_ONE, 32, 5, 160, 16, DG_PROJ_128x160, 5, 160},
+      {2047, DG_PROJ_128x160_ONE, 32, 16, 512, 16, DG_PROJ_128x160, 16, 512},
+      {2048, DG_PROJ_256x160_ONE, 32, 8, 256, 32, DG_PROJ_128x160, 16, 512}};
+  for (const auto& c : proj) {
+    DecodePlan p = plan(nofold(greedy(c.R)));
+    EXPECT(!p.fold && same(p.proj, c.shape, c.NB, c.NR, c.grid, 316, c.nkt) && p.nbp == 64);
+    EXPECT(unused(p.fold_gates) && unused(p.fold_last) && !p.ksplit && !p.ksplit_last);
+    p = plan(with_blob(nofold(greedy(c.R)), big_w));
+    EXPECT(p.s16 && !p.fold && same(p.proj, c.shape2, c.NB, c.NR2, c.grid2, 316, 16) && p.nbp == 64);
+    p = plan(with_blob(nofold(greedy(c.R)), f32));
+    EXPECT(!p.s16 && !p.fold && same(p.proj, c.shape2, c.NB, c.NR2, c.grid2, 316, 16) && p.nbp == 64);
+  }
+  // beam callers take the same projection rules (R = B k)
+  EXPECT(same(plan(beam(40, 8)).proj, DG_PROJ_128x80, 64, 3, 192, 316, 16));                // R = 320
+  EXPECT(same(plan(beam(72, 8)).proj, DG_PROJ_128x160_ONE, 32, 5, 160, 316, 16));           // R = 576
+  EXPECT(same(plan(with_blob(beam(72, 8), big_w)).proj, DG_PROJ_128x160, 32, 5, 160, 316, 16));
+  EXPECT(same(plan(with_blob(beam(256, 8), big_w)).proj, DG_PROJ_128x160, 32, 16, 512, 316, 16) &&
+         !plan(with_blob(beam(256, 8), big_w)).fold);
+
+  // the folded GEMM: greedy by R and the k split, at a gate-computing step and at the last step
+  DecodePlan p = plan(greedy(32));
+  EXPECT(p.fold && unused(p.proj) && p.nbp == 45);
+  EXPECT(same(p.fold_gates, DG_FOLD_32x112_KS, 64, 1, 256, 443, 16) && p.ksplit);
+  EXPECT(same(p.fold_last, DG_FOLD_32x112_KS, 45, 1, 192, 443, 16) && p.ksplit_last);
+  p = plan(greedy(32).opt(CASR_OPT_DEC_KSPLIT, 0));
+  EXPECT(same(p.fold_gates, DG_FOLD_32x112, 64, 1, 64, 443, 16) && same(p.fold_last, DG_FOLD_32x112, 45, 1, 48, 443, 16));
+  EXPECT(!p.ksplit && !p.ksplit_last);
+  p = plan(greedy(33));
+  EXPECT(same(p.fold_gates, DG_FOLD_64x112, 64, 1, 64, 443, 16) && same(p.fold_last, DG_FOLD_64x112, 45, 1, 48, 443, 16));
+  p = plan(with_blob(greedy(256), f32));
+  EXPECT(same(p.fold_gates, DG_FOLD_64x112, 64, 4, 256, 443, 16) && same(p.fold_last, DG_FOLD_64x112, 45, 4, 192, 443, 16));
+  EXPECT(p.nbp == 45 && !p.ksplit);
+  // V = 5204: 326 vocabulary tiles, gates from tile 329, 457 tiles = 66 blocks > 64 counters: the
+  // gate steps keep the unsplit 32 x 112 shape, the last step's 47 blocks split
+  p = plan(with_vocab(greedy(32), 5204));
+  EXPECT(same(p.fold_gates, DG_FOLD_32x112, 66, 1, 72, 457, 16) && !p.ksplit);
+  EXPECT(same(p.fold_last, DG_FOLD_32x112_KS, 47, 1, 192, 457, 16) && p.ksplit_last && p.nbp == 47);
+  // beam: 224-column blocks, 32-deep stages (R = 2047 is no B k of a folding beam: 2040 stands in)
+  p = plan(beam(128, 8));
+  EXPECT(same(p.fold_gates, DG_FOLD_128x224_ONE, 32, 8, 256, 443, 32) && same(p.fold_last, DG_FOLD_128x224_ONE, 23, 8, 192, 443, 32));
+  p = plan(beam(255, 8));
+  EXPECT(p.fold && same(p.fold_gates, DG_FOLD_128x224_ONE, 32, 16, 512, 443, 32) && p.nbp == 45 && p.q_slots == 32);
+  p = plan(beam(256, 8));
+  EXPECT(same(p.fold_gates, DG_FOLD_256x224_ONE, 32, 8, 256, 443, 32) && same(p.fold_last, DG_FOLD_256x224_ONE, 23, 8, 192, 443, 32));
+  EXPECT(unused(p.proj) && !p.ksplit && !p.ksplit_last);
+
+  // casr_score: the LSTMCell at R = B, the batched projection at R = L B on either side of 512 and 2048
+  p = plan(score(16, 32));
+  EXPECT(p.status == PLAN_OK && p.score_len == 32 && same(p.lstm, DG_LSTM_32x64, 32, 1, 32, 128, 20) && p.q_slots == 32);
+  EXPECT(same(p.proj, DG_PROJ_128x80, 64, 4, 256, 316, 16) && p.nbp == 64);
+  EXPECT(same(plan(score(16, 33)).proj, DG_PROJ_128x160_ONE, 32, 5, 160, 316, 16) && plan(score(16, 33)).nbp == 64);
+  EXPECT(same(plan(with_blob(score(16, 33), f32)).proj, DG_PROJ_128x160, 32, 5, 160, 316, 16));
+  EXPECT(same(plan(with_blob(score(16, 33), big_w)).proj, DG_PROJ_128x160, 32, 5, 160, 316, 16));
+  EXPECT(same(plan(score(64, 31)).proj, DG_PROJ_128x160_ONE, 32, 16, 512, 316, 16));  // R = 1984
+  EXPECT(same(plan(score(64, 32)).proj, DG_PROJ_256x160_ONE, 32, 8, 256, 316, 32));   // R = 2048
+  EXPECT(same(plan(with_blob(score(64, 32), f32)).proj, DG_PROJ_128x160, 32, 16, 512, 316, 16));
+  EXPECT(plan(score(64, 32)).q_slots == 32 && plan(greedy(16)).score_len == 0);
+  {  // the scored length is an input of the score caller only
+    In in = greedy(16);
+    in.score_len = 7;
+    const DecodePlan a = plan(in), b = plan(greedy(16));
+    EXPECT(std::memcmp(&a, &b, sizeof a) == 0);
+  }
+
+  // over every caller, R, arithmetic and option: an s16-only shape is never planned under f32, the
+  // k split only within the arrival counters, nbp from the planned shape's tiles per wave column
+  for (int R : {1, 32, 33, 256, 257, 512, 513, 1024, 2040, 2048, 4096})
+    for (int V : {16, 1000, 5004, 5120, 5204})
+      for (const BlobFacts& b : {BlobFacts{1, 1, 1, 1}, f32, big_w, BlobFacts{1, 1, 1, 0}})
+        for (int fold = 0; fold < 2; ++fold)
+          for (int caller : {PLAN_GREEDY, PLAN_BEAM, PLAN_SCORE}) {
+            In in = caller == PLAN_BEAM ? beam((R + 7) / 8, 8) : caller == PLAN_SCORE ? score((R + 39) / 40, 40) : greedy(R);
+            in.V = V;
+            in.blob = b;
+            in.opt(CASR_OPT_DEC_FOLD, fold);
+            const DecodePlan q = plan(in);
+            if (q.status != PLAN_OK) continue;
+            const int vtiles = (V + 15) / 16, ptiles = (V + 63) / 64 * 4;
+            for (const DgemmPlan* g : {&q.lstm, &q.proj, &q.fold_gates, &q.fold_last}) {
+              if (unused(*g)) continue;
+              EXPECT(g->shape >= 0 && g->shape < DG_SHAPE_COUNT && g->grid > 0);
+              EXPECT(q.s16 || !dg_s16_only(DG_SHAPES[g->shape]));
+              EXPECT(g->shape != DG_FOLD_32x112_KS || (g->NB <= DG_KS_GROUPS && q.R <= 32));
+              EXPECT(g->NB * DG_SHAPES[g->shape].NT >= (g == &q.fold_last ? vtiles : g->ntiles));
+            }
+            EXPECT(unused(q.proj) == (q.fold != 0) && unused(q.fold_gates) == !q.fold && unused(q.fold_last) == !q.fold);
+            EXPECT(q.ksplit == (q.fold && q.fold_gates.shape == DG_FOLD_32x112_KS));
+            EXPECT(q.ksplit_last == (q.fold && q.fold_last.shape == DG_FOLD_32x112_KS));
+            if (q.partials)
+              EXPECT(q.nbp == (q.fold ? (vtiles + 6) / 7 : (ptiles + 4) / 5) && q.nbp <= GP_NB);
+          }
+}
+
 static void check_keys() {
   const DecodePlan p = plan(beam(256, 8));
   const float sc[2] = {0.25f, 0.5f};
@@ -260,8 +455,11 @@ static void check_carving() {
     const size_t R = (size_t)B * k, f = sizeof(float);
     DecodeBufs d{};
     size_t size;
-    char* base = carved([&](void* p) { return carve_state(p, (int)R, d); }, &size);
+    const DecodePlan pl = plan(beam(B, k));
+    EXPECT(pl.status == PLAN_OK && pl.R == (int)R);
+    char* base = carved([&](void* p) { return carve_state(p, pl, d); }, &size);
     const size_t slots = R >= 2048 ? HD / 32 : HD / 16;
+    EXPECT((size_t)pl.q_slots == slots);
     check_regions(base, size, (2 * R * ST + slots * R * A) * f,
                   {{d.st[0], R * ST * f, 16}, {d.st[1], R * ST * f, 16}, {d.qpart, slots * R * A * f, 16}});
     std::free(base);
@@ -330,6 +528,8 @@ int main() {
   check_greedy();
   check_beam();
   check_score();
+  check_shape_table();
+  check_gemm_plans();
   check_keys();
   check_carving();
   check_options();

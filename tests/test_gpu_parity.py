@@ -942,3 +942,53 @@ def test_greedy_split_attention_small_batch(eng, B, graphs):
     r = O.greedy_decode(feats, [f.shape[0] for f in feats], enc_sd, dec_sd)
     assert toks == r["tokens"]
     np.testing.assert_allclose(score, r["score"], atol=2e-3, rtol=0)
+
+
+_MID_ROWS = {"R320": (40, None), "R576_big_w": (72, (777, 300))}
+_mid_rows_cache = {}
+
+
+def _mid_rows_reference(case):
+    """(frames, enc_sd, dec_sd, the CPU oracle's beam-8 result), computed once per case and shared by
+    both arithmetics (about 10 s each: the oracle's full sort of k V scores per utterance and step)."""
+    if case not in _mid_rows_cache:
+        B, big = _MID_ROWS[case]
+        enc_sd, dec_sd = synthetic_state_dicts(CFG, peaked=True)
+        if big:
+            dec_sd = dict(dec_sd)
+            w = dec_sd["proj_linear.weight"].copy()
+            w[big] = 16.5
+            dec_sd["proj_linear.weight"] = w
+        frames = [120 - 3 * (b % 5) for b in range(B - 1)] + [57]
+        feats = [O.features_from_fbank(fbank_for(b, t)) for b, t in enumerate(frames)]
+        _mid_rows_cache[case] = (frames, enc_sd, dec_sd,
+                                 O.beam_decode(feats, [f.shape[0] for f in feats], enc_sd, dec_sd, 8))
+    return _mid_rows_cache[case]
+
+
+@pytest.mark.parametrize("case", sorted(_MID_ROWS))
+def test_beam_mid_row_counts_match_oracle(eng, case):
+    """The two least-covered decode GEMM shapes (csrc/decode_gemm_shapes.h) on whole batches against
+    the CPU oracle, beam 8 on short inputs (T about 120 frames):
+      R320: B = 40, R = 320 rows in (256, 512]: the 64 x 64 LSTMCell and the 128 x 80 step
+        projection (elsewhere only test_sharded_chain_equals_full_batch[64-8] runs them, under
+        s16x3, against its own shards);
+      R576_big_w: B = 72, R = 576 rows > 512 on a blob with one projection weight of 16.5: below
+        the s16 limit, so the s16 arithmetic stays in effect, but not every |W_p| < 16, so the
+        one-accumulator shapes and the fold are off and s16 runs the two-accumulator 128 x 160
+        projection (f32 its f32 form), with the 128 x 64 LSTMCell and a partial last row block
+        (test_large_projection_weight_beam_takes_three_launch_step checks 4 rows of R = 1024).
+    Tokens identical to the oracle's on every utterance (no near-tie allowance: on these inputs the
+    oracle and its torch port, which sums in another order, decode to the same tokens with scores
+    within 8e-5), scores within 2e-3 as test_beam_matches_reference, device flags 0."""
+    frames, enc_sd, dec_sd, ref = _mid_rows_reference(case)
+    eng.bind(pack_weights(CFG, enc_sd, dec_sd))
+    assert eng.precision() == eng.requested
+    fb, fr = batch_fbank(frames, eng.device)
+    eng.encode_fbank(fb, fr)
+    r = eng.beam(8)
+    assert eng.device_flags() == 0
+    toks = r["tokens"].cpu().numpy()
+    blen = r["length"].cpu().numpy()
+    near_tie_beam_check([toks[b, :blen[b]].tolist() for b in range(len(frames))], r["score"].cpu().numpy(), ref,
+                        atol=2e-3, max_flips=0)
