@@ -182,7 +182,7 @@ class BeamShardDecoder:
     position)."""
 
     def __init__(self, engine, k, lm_model=None, int2word=None, lm_weight=0.0, length_weight=0.0,
-                 keep_records=False, max_batch=256, rescorer=None):
+                 keep_records=False, max_batch=256, rescorer=None, fusion=False):
         # engine: an Engine, or a casr.pipeline.StreamPipeline (or its limited() view), whose
         # handles then take the shard's batches in turn, several in flight
         self.engine, self.k = engine, int(k)
@@ -198,14 +198,21 @@ class BeamShardDecoder:
         # the host path, and any other lm_model has no other
         from .ngram import NgramLM
         self.device_lm = isinstance(lm_model, NgramLM) and rescorer is None and not keep_records
+        # fusion: on that device path, the LM fused into the first pass (casr_beam_lm) and no second pass
+        if fusion and not self.device_lm:
+            raise TypeError("fusion=True needs a casr.ngram.NgramLM as lm_model, no rescorer and no keep_records")
+        self.fusion = bool(fusion)
         self._slots = {}
         self._next = 0
         self.stats = {}
 
     def _batch(self, e, fbank, frames, key):
         e.encode_fbank(fbank, frames)
-        r = e.beam(self.k, self.lm_weight, self.length_weight)
-        if self.device_lm:
+        if self.fusion:
+            r = e.beam_lm(self.lm_model, self.k, self.lm_weight, self.length_weight)
+        else:
+            r = e.beam(self.k, self.lm_weight, self.length_weight)
+        if self.device_lm and not self.fusion:
             steps = r["steps"]
             r = e.beam_rescore(self.lm_model, self.lm_weight, self.length_weight)
             r["steps"] = steps

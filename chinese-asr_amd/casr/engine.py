@@ -316,6 +316,47 @@ class Engine:
         self._keep_lm = (lm,)
         return dict(tokens=toks, length=blen, score=score, lm=best_lm, rec_lm=rec_lm)
 
+    def lm_terms(self, lm, ctx, nc, eos=None):
+        """Term rows of an n-gram LM on the device (casr_lm_terms): ctx [n, 3] LM ids (nearest
+        predecessor first), nc [n] -> terms [n, V] float32, the bits NgramLM.terms gives on the host."""
+        dev = self.device
+        ctx = torch.as_tensor(ctx).to(dev, torch.int32).contiguous()
+        nc = torch.as_tensor(nc).to(dev, torch.int32).contiguous()
+        if ctx.dim() != 2 or ctx.shape[1] != 3 or nc.shape != (ctx.shape[0],):
+            raise ValueError("lm_terms: ctx must be [n, 3] and nc [n]")
+        n = ctx.shape[0]
+        terms = torch.empty(n, self.cfg.vocab, dtype=torch.float32, device=dev)
+        _lib.check(self.lib.casr_lm_terms(self.handle, lm.on(self), _ptr(ctx), _ptr(nc), n,
+                                          -1 if eos is None else int(eos), _ptr(terms), _stream()), self.handle)
+        self._keep_lm = (lm, ctx, nc)  # read by the enqueued kernel
+        return terms
+
+    def beam_lm(self, lm, k, lm_weight, length_weight):
+        """Beam search with the n-gram LM fused into the first pass (casr_beam_lm): lm a
+        casr.ngram.NgramLM.  Returns tokens [B, max_len] (-1 past the length), length [B], score [B]
+        (the choice's acoustic log-probability), lm [B] (its LM score) and steps [1]."""
+        B, L = self._B, self.cfg.max_len
+        dev = self.device
+        toks = torch.empty(B, L, dtype=torch.int32, device=dev)
+        blen = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        best_lm = torch.empty(B, dtype=torch.float32, device=dev)
+        steps = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.casr_beam_lm(self.handle, lm.on(self), int(k), ctypes.c_float(lm_weight),
+                                         ctypes.c_float(length_weight), _ptr(toks), _ptr(blen), _ptr(score),
+                                         _ptr(best_lm), _ptr(steps), _stream()), self.handle)
+        self._k = k
+        self._keep_lm = (lm,)
+        return dict(tokens=toks, length=blen, score=score, lm=best_lm, steps=steps)
+
+    def beam_record_lm(self):
+        """rec_lm [B, max_len, k]: the LM score of every valid record of the last beam_lm() (0
+        elsewhere), beside beam_records()' tokens and acoustic scores."""
+        B, L, k = self._B, self.cfg.max_len, self._k
+        rec_lm = torch.empty(B, L, k, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.casr_beam_record_lm(self.handle, _ptr(rec_lm), _stream()), self.handle)
+        return rec_lm
+
     def score(self, targets, tgt_len, alignment=False, best=False, mean=False):
         """Teacher-forced pass over the last encode (casr_score): targets [B, L] int (1 <= L <=
         max_len), tgt_len [B] scored positions per utterance.  Returns token_logp [B, L] (0 past

@@ -25,6 +25,7 @@ EXPORTS = [
     "casr_set_option", "casr_get_option", "casr_score",
     "casr_convert_audio", "casr_resample_plan", "casr_resample_filter", "casr_resample_frames",
     "casr_lm_create", "casr_lm_destroy", "casr_lm_score_host", "casr_lm_score", "casr_beam_rescore",
+    "casr_lm_terms_host", "casr_lm_terms", "casr_beam_lm", "casr_beam_record_lm",
     "casr_segment_default_params", "casr_segment_bound", "casr_segment_host", "casr_segment",
     "casr_gather_segments",
 ]
@@ -132,6 +133,10 @@ def load(path=None, variant=None):
         "casr_lm_score_host": (i32, [vp, vp, vp, i32, i32, i32, vp]),
         "casr_lm_score": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "casr_beam_rescore": (i32, [vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, vp]),
+        "casr_lm_terms_host": (i32, [vp, vp, vp, i32, i32, vp]),
+        "casr_lm_terms": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+        "casr_beam_lm": (i32, [vp, vp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp, vp]),
+        "casr_beam_record_lm": (i32, [vp, vp, vp]),
         "casr_segment_default_params": (i32, [vp]),
         "casr_segment_bound": (i32, [i32, vp]),
         "casr_segment_host": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]),

@@ -184,6 +184,21 @@ class NgramLM:
         _lib.check(rc, lib=self._lib)
         return q
 
+    def terms(self, ctx, nc, eos=None):
+        """Term rows float32 [n, V] on the host (casr_lm_terms_host): row i holds the term of every ASR
+        token after the context ctx[i] ([n, 3] LM ids, nearest predecessor first, the first nc[i] of
+        them read); token ``eos`` scores </s>."""
+        ctx = np.ascontiguousarray(ctx, np.int32)
+        nc = np.ascontiguousarray(nc, np.int32)
+        if ctx.ndim != 2 or ctx.shape[1] != 3 or nc.shape != (ctx.shape[0],):
+            raise ValueError("terms: ctx must be [n, 3] and nc [n]")
+        out = np.empty((ctx.shape[0], self.vocab), np.float32)
+        rc = self._lib.casr_lm_terms_host(self._host, ctx.ctypes.data_as(ctypes.c_void_p),
+                                          nc.ctypes.data_as(ctypes.c_void_p), ctx.shape[0],
+                                          -1 if eos is None else int(eos), out.ctypes.data_as(ctypes.c_void_p))
+        _lib.check(rc, lib=self._lib)
+        return out
+
     def ids_of(self, sentence):
         """LM ids of a sentence's whitespace-separated words: the ASR id, or <unk> for a word outside
         the ASR vocabulary.  (An ASR id the model has no unigram for scores as <unk> too, in the

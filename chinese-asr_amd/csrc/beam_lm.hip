@@ -1,0 +1,478 @@
+// Shallow fusion of the backoff n-gram LM into the beam search's first pass (include/casr.h
+// casr_lm_terms, casr_beam_lm): the term row of a context (ngram_succ.h's row query, one workgroup
+// per row), the select that ranks by (am + lm_weight lm) + len_l and carries am and lm separately,
+// and the final choice.  The decode steps are run_beam's (decoder.hip run_beam_lm drives them).
+//
+// The term rows go through a workspace [R][V]: lm_terms_kernel writes a row once, the select reads
+// it beside the logits row.  A row is assembled in LDS (4 V bytes), so the successors' scattered
+// overwrites never leave the CU and the row goes out in one coalesced pass.
+#include "beam_select.h"
+#include "casr_internal.h"
+
+namespace casr {
+
+// ------------------------------------------------------------------ term rows
+constexpr int LMT_THREADS = 256;
+
+// One workgroup per row.  tree == 0: row i's context is ctx[i][0..3) / nc[i] (LM ids in [0, V + 3)).
+// tree == 1: row i = b k + j of decode step l; its context is read off the beam tree (the tokens
+// before, <s> before step 0), and the workgroup leaves at once where the select of step l would not
+// run or not read the row (the early exit; step 0 ranks beam 0 only).
+__global__ __launch_bounds__(LMT_THREADS) void lm_terms_kernel(NgramView m, NgramSuccView s, LmTermsSrc src,
+                                                               int eos_token, float* __restrict__ terms,
+                                                               int32_t* __restrict__ err) {
+  extern __shared__ __attribute__((aligned(16))) float trow[];
+  __shared__ NgramRow row;
+  __shared__ int flags;
+  const int i = blockIdx.x, tid = threadIdx.x, V = m.V;
+  if (src.tree) {
+    if (done_before(src.newdone, src.l) >= src.B) return;
+    if (src.l == 0 && i % src.k != 0) return;
+  }
+  if (tid == 0) {
+    int32_t c[NGRAM_MAX_ORDER - 1] = {0, 0, 0};
+    int nc = 0, fl = 0;
+    if (src.tree) {
+      const int b = i / src.k;
+      int slot = i - b * src.k, st = src.l - 1;
+      for (int j = 1; j < m.order; ++j) {
+        if (st < 0) {
+          c[nc++] = V;  // <s>
+          break;
+        }
+        const size_t ix = (size_t)st * src.R + b * src.k + slot;
+        const int t = src.tk[ix];
+        if ((unsigned)t >= (unsigned)V) fl |= CASR_DEV_BAD_TOKEN;
+        c[nc++] = (unsigned)t < (unsigned)V ? t : V + 2;
+        int p = src.bp[ix];
+        if ((unsigned)p >= (unsigned)src.k) {
+          if (st > 0) fl |= CASR_DEV_BAD_BACKPTR;  // (step 0 has no predecessor node)
+          p = 0;
+        }
+        slot = p;
+        --st;
+      }
+    } else {
+      nc = src.nc[i];
+      for (int j = 0; j < NGRAM_MAX_ORDER - 1; ++j) c[j] = src.ctx[(size_t)i * (NGRAM_MAX_ORDER - 1) + j];
+    }
+    NgramRow r;
+    ngram_row_prepare(m, s, c, nc, V + 3, &r);
+    if (r.bad) fl |= CASR_DEV_BAD_TOKEN;
+    row = r;
+    flags = fl;
+  }
+  __syncthreads();
+  for (int v = tid; v < V; v += LMT_THREADS) trow[v] = ngram_row_dense(m, row, v, eos_token);
+  // orders ascending, a barrier between: the highest order wins (a list holds a word once)
+  for (int n = 2; n <= row.nc + 1; ++n) {
+    __syncthreads();
+    const NgramSucc* e = s.list[n - 2] + row.succ[n - 2].offset;
+    const uint32_t cnt = row.succ[n - 2].count;
+    for (uint32_t q = tid; q < cnt; q += LMT_THREADS) {
+      const NgramSucc x = e[q];
+      if (ngram_row_takes(m, x.w, eos_token)) trow[x.w] = ngram_row_value(row, n, x.prob);
+    }
+  }
+  __syncthreads();
+  float* out = terms + (size_t)i * V;
+  for (int v = tid; v < V; v += LMT_THREADS) out[v] = trow[v];
+  if (tid == 0 && flags) atomicOr(err, flags);
+}
+
+bool lm_terms_supported(int V) { return (size_t)V * sizeof(float) <= LM_TERMS_LDS_BYTES; }
+
+hipError_t launch_lm_terms(const NgramView& m, const NgramSuccView& sv, const LmTermsSrc& src, int n, int eos_token,
+                           float* terms, int32_t* err, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(lm_terms_kernel, dim3(n), dim3(LMT_THREADS), (size_t)m.V * sizeof(float), s, m, sv, src,
+                     eos_token, terms, err);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the fused select
+// LDS of one select: the rows' sorted lists and log-sum-exps, the utterance's list, and per wave its
+// threshold candidates
+template <int K2, int NR, int NWV>
+struct BeamLmSelLds {
+  float rv[NR][K2];
+  int ri[NR][K2];
+  float lse[NR];
+  float cv[K2];
+  int ci[K2];
+  float cvs[NWV][BS_CAP];
+  int cis[NWV][BS_CAP];
+  int cnt[NWV];
+};
+
+// One block per utterance, one wave per beam row (rows j = w, w + 8), as beam_select_block.  Per row:
+// its log-sum-exp formed exactly as beam_select_block forms it at the same plan (from the projection's
+// partials, or from the row), then every candidate's
+//   am = (x / T - lse) + a,  lm = l == 0 ? term : g + term,  val = (am + lm_weight lm) + len_l
+// (each operation rounded on its own) ranked to the row's top 2k: a lane computes its vals once and
+// holds them; a threshold is found (the 2k-th largest of the lanes' two best), the candidates at or
+// above it are collected, and those are ranked by counting.  The rows' lists are ranked the same way into the utterance's top 2k.  The
+// bookkeeping is beam_select_block's on that ranking; the chosen candidates pass on am and lm, which
+// their lane recomputes from the same operands (the same bits).
+template <int K2, bool UNIT_T>
+__global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(BeamSelArgs a, BeamLmArgs g) {
+  constexpr int NWV = bs_waves<K2>(), NTH = 64 * NWV;
+  __shared__ BeamLmSelLds<K2, KMAX_BEAM, NWV> S;
+  if (done_before(a.newdone, a.l) >= a.B) return;
+  const float* __restrict__ logits = a.logits;
+  const float* __restrict__ terms = g.terms;
+  const int V = a.V, B = a.B, k = a.k, l = a.l, L = a.L, eos = a.eos, b = blockIdx.x;
+  const float temperature = a.temperature;
+  const GreedyPart& gp = a.gp;
+  const int nbp = a.nbp;
+  const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
+  const int R = B * k;
+  const int nrows = (l == 0) ? 1 : k;  // step 0 ranks beam 0 only
+  const int n2k = 2 * k;
+  const bool vec = (V & 3) == 0;
+  const float lmw = g.lm_weight, len_l = g.len_l;
+  auto xt = [&](float x) { return UNIT_T ? x : x / temperature; };
+
+  for (int j = wv; j < nrows; j += NWV) {
+    const size_t row = (size_t)(b * k + j);
+    const float* x = logits + row * V;
+    const float* t = terms + row * V;
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    const float4* t4 = reinterpret_cast<const float4*>(t);
+    const float sc = a.score_cur[row];
+    const float gc = l == 0 ? 0.f : g.g_cur[row];
+    float lse;
+    if (UNIT_T && nbp > 0 && gp.tmx && vec) {  // beam_select_block's first form: from the partials
+      float mb = -INFINITY, sb = 0.f;
+      if (ln < nbp) {
+        mb = gp.mx[row * GP_NB + ln];
+        sb = gp.se[row * GP_NB + ln];
+      }
+      const float M = wave_max(mb);
+      const float s = wave_sum((sb > 0.f) ? sb * expf(mb - M) : 0.f);
+      lse = logf(s) + M;
+    } else {  // ... and its second: from the row
+      float lm = -INFINITY;
+      if (vec) {
+#pragma unroll 4
+        for (int i = ln; i < V / 4; i += 64) {
+          const float4 q = x4[i];
+          lm = fmaxf(lm, fmaxf(fmaxf(xt(q.x), xt(q.y)), fmaxf(xt(q.z), xt(q.w))));
+        }
+      } else {
+        for (int v = ln; v < V; v += 64) lm = fmaxf(lm, xt(x[v]));
+      }
+      const float mm = wave_max(lm);
+      float s = 0.f;
+      if (vec) {
+#pragma unroll 4
+        for (int i = ln; i < V / 4; i += 64) {
+          const float4 q = x4[i];
+          s += expf(xt(q.x) - mm) + expf(xt(q.y) - mm) + expf(xt(q.z) - mm) + expf(xt(q.w) - mm);
+        }
+      } else {
+        for (int v = ln; v < V; v += 64) s += expf(xt(x[v]) - mm);
+      }
+      s = wave_sum(s);
+      lse = logf(s) + mm;
+    }
+    if (ln == 0) S.lse[j] = lse;
+    auto val = [&](float xv, float tv) {
+      const float am = (xt(xv) - lse) + sc;
+      const float lm = l == 0 ? tv : __fadd_rn(gc, tv);
+      return __fadd_rn(__fadd_rn(am, __fmul_rn(lmw, lm)), len_l);
+    };
+    // this lane's largest and second-largest candidate values (distinct elements), then tau = the
+    // 2k-th largest of the lanes' values: a lower bound of the row's 2k-th best
+    float lt = -INFINITY, lt2 = -INFINITY;
+    auto top2 = [&](float y) {
+      lt2 = fmaxf(lt2, fminf(lt, y));
+      lt = fmaxf(lt, y);
+    };
+    // a row of at most 64 x LMS_QB float4 (V <= 5,120): the lane's vals stay in registers between the
+    // two passes, so the logits row and the term row are read once
+    constexpr int LMS_QB = 20;
+    const bool held = vec && V <= 4 * 64 * LMS_QB;
+    float vq[LMS_QB][4];
+    if (held) {
+#pragma unroll
+      for (int u = 0; u < LMS_QB; ++u) {
+        const int i = ln + 64 * u;
+        if (i < V / 4) {
+          const float4 q = x4[i], w4 = t4[i];
+          vq[u][0] = val(q.x, w4.x);
+          vq[u][1] = val(q.y, w4.y);
+          vq[u][2] = val(q.z, w4.z);
+          vq[u][3] = val(q.w, w4.w);
+        } else {
+          vq[u][0] = vq[u][1] = vq[u][2] = vq[u][3] = -INFINITY;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) top2(vq[u][e]);
+      }
+    } else {
+      for (int v = ln; v < V; v += 64) top2(val(x[v], t[v]));  // (a longer or unaligned row: two passes)
+    }
+    float tau = -INFINITY;
+    for (int c = 0; c < n2k; ++c) {
+      const float mx = wave_max(lt);
+      tau = mx;
+      const unsigned long long hit = __ballot(lt == mx);
+      if (hit && ln == __ffsll((long long)hit) - 1) {
+        lt = lt2;
+        lt2 = -INFINITY;
+      }
+    }
+    if (ln == 0) S.cnt[wv] = 0;
+    __builtin_amdgcn_wave_barrier();
+    // (an integer LDS counter hands out the slots; their order varies, the ranking below does not)
+    auto offer = [&](float v, int idx) {
+      if (v >= tau) {
+        const int slot = atomicAdd(&S.cnt[wv], 1);
+        if (slot < BS_CAP) {
+          S.cvs[wv][slot] = v;
+          S.cis[wv][slot] = idx;
+        }
+      }
+    };
+    if (held) {
+#pragma unroll
+      for (int u = 0; u < LMS_QB; ++u) {
+        const int i = ln + 64 * u;
+        if (i < V / 4) {  // (the padding never qualifies, whatever tau is)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) offer(vq[u][e], j * V + 4 * i + e);
+        }
+      }
+    } else {
+      for (int v = ln; v < V; v += 64) offer(val(x[v], t[v]), j * V + v);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const int nc = S.cnt[wv];
+    if (nc <= BS_CAP) {
+      // a candidate's slot is the number of candidates better than it (better(): value, then lower
+      // flat index; indices are distinct, so ranks are); unreached slots keep the sentinel
+      if (ln < n2k) {
+        S.rv[j][ln] = -INFINITY;
+        S.ri[j][ln] = 0x7fffffff;
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (int p = ln; p < nc; p += 64) {
+        const float pv = S.cvs[wv][p];
+        const int pi = S.cis[wv][p];
+        int rank = 0;
+        for (int q = 0; q < nc; ++q) rank += better(S.cvs[wv][q], S.cis[wv][q], pv, pi) ? 1 : 0;
+        if (rank < n2k) {
+          S.rv[j][rank] = pv;
+          S.ri[j][rank] = pi;
+        }
+      }
+    } else {  // more ties at tau than the buffer holds: every element through sorted lane lists
+      TopList<K2> tl;
+      tl.init();
+      for (int v = ln; v < V; v += 64) tl.insert(val(x[v], t[v]), j * V + v);
+      wave_merge<K2>(tl, n2k, S.rv[j], S.ri[j]);
+    }
+  }
+  if (tid < n2k) {
+    S.cv[tid] = -INFINITY;
+    S.ci[tid] = 0x7fffffff;
+  }
+  __syncthreads();  // every row's sorted list is in S.rv / S.ri
+  // the utterance's top 2k: one thread per list entry (at most 16 x 32 = NTH), its slot the number
+  // of entries of all lists better than it; sentinels write nothing
+  for (int e = tid; e < nrows * n2k; e += NTH) {
+    const int j = e / n2k, p = e - j * n2k;
+    const float pv = S.rv[j][p];
+    const int pi = S.ri[j][p];
+    if (pi == 0x7fffffff) continue;
+    int rank = 0;
+    for (int jj = 0; jj < nrows; ++jj)
+      for (int q = 0; q < n2k; ++q) rank += better(S.rv[jj][q], S.ri[jj][q], pv, pi) ? 1 : 0;
+    if (rank < n2k) {
+      S.cv[rank] = pv;
+      S.ci[rank] = pi;
+    }
+  }
+  __syncthreads();
+
+  // bookkeeping (beam_select_block's, on the val ranking), one lane of wave 0 per ranked candidate
+  if (wv == 0) {
+    const int c = ln;
+    const bool inr = c < n2k;
+    int cc = inr ? S.ci[c] : 0;
+    const bool bad = inr && (unsigned)cc >= (unsigned)(nrows * V);  // NaN rows leave empty slots
+    if (bad) cc = 0;
+    if (__ballot(bad) && ln == 0) atomicOr(a.err, CASR_DEV_BAD_CAND);
+    const int beam = cc / V, tok = cc - beam * V;
+    const bool f = inr && tok == eos;
+    const size_t srow = (size_t)(b * k + beam);
+    float am = 0.f, lm = 0.f;
+    if (inr) {
+      const float tv = terms[srow * V + tok];
+      am = (xt(logits[srow * V + tok]) - S.lse[beam]) + a.score_cur[srow];
+      lm = l == 0 ? tv : __fadd_rn(g.g_cur[srow], tv);
+    }
+    if (c < k) {  // finished hypotheses among the first k candidates
+      const size_t ri = ((size_t)b * L + l) * k + c;
+      a.rec_valid[ri] = f;
+      if (f) {
+        a.rec_score[ri] = am;
+        g.rec_lm[ri] = lm;
+        a.rec_src[ri] = beam;
+      }
+    }
+    if (ln == 0 && !a.topfin[b] && tok == eos) {  // candidate 0
+      a.topfin[b] = 1;
+      atomicAdd(&a.newdone[l], 1);
+    }
+    // active = first k non-EOS candidates in rank order, then EOS ones
+    const unsigned long long ne = __ballot(inr && !f), eo = __ballot(f);
+    const unsigned long long below = (1ull << c) - 1ull;
+    const int slot = f ? __popcll(ne) + __popcll(eo & below) : __popcll(ne & below);
+    if (inr && slot < k) {
+      const int rw = b * k + slot;
+      a.tok_next[rw] = tok;
+      a.src_next[rw] = b * k + beam;
+      a.score_next[rw] = am;
+      g.g_next[rw] = lm;
+      a.bp[(size_t)l * R + rw] = beam;
+      a.tk[(size_t)l * R + rw] = tok;
+    }
+  }
+}
+
+template <int K2>
+static void launch_beam_lm_select_k(const BeamSelArgs& a, const BeamLmArgs& g, hipStream_t s) {
+  auto kern = a.temperature == 1.0f ? beam_lm_select_kernel<K2, true> : beam_lm_select_kernel<K2, false>;
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * bs_waves<K2>()), 0, s, a, g);
+}
+
+hipError_t launch_beam_lm_select(const BeamSelArgs& a, const BeamLmArgs& g, int K2, hipStream_t s) {
+  switch (K2) {
+    case 4: launch_beam_lm_select_k<4>(a, g, s); break;
+    case 8: launch_beam_lm_select_k<8>(a, g, s); break;
+    case 16: launch_beam_lm_select_k<16>(a, g, s); break;
+    default: launch_beam_lm_select_k<32>(a, g, s);
+  }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the final choice
+// executed loop steps: the step at which the cumulative count of newdone reached `total`, + 1
+__device__ __forceinline__ int lmf_executed_steps(const int32_t* newdone, int L, int total) {
+  int cum = 0;
+  for (int s = 0; s < L; ++s) {
+    cum += newdone[s];
+    if (cum >= total) return s + 1;
+  }
+  return L;
+}
+
+__device__ __forceinline__ float lmf_comb(float am, float lm, float lmw, float lenw, int l) {
+  const float len_l = (float)((double)lenw * (double)(l + 1));
+  return __fadd_rn(__fadd_rn(am, __fmul_rn(lmw, lm)), len_l);
+}
+
+// One thread per utterance: the first maximum of (rec_score + lm_weight rec_lm) + len_l over its
+// valid records in (step, rank) order, or without a record the first maximum over the k live rows of
+// the last executed step; tokens by walking the back-pointers.
+__global__ void beam_lm_finalize_kernel(int B, int k, int L, float lmw, float lenw, const float* __restrict__ score0,
+                                        const float* __restrict__ score1, const float* __restrict__ g0,
+                                        const float* __restrict__ g1, const int32_t* __restrict__ bp,
+                                        const int32_t* __restrict__ tk, const float* __restrict__ rec_score,
+                                        const float* __restrict__ rec_lm, const int32_t* __restrict__ rec_src,
+                                        const uint8_t* __restrict__ rec_valid, const int32_t* __restrict__ newdone,
+                                        int32_t* __restrict__ best_tokens, int32_t* __restrict__ best_len,
+                                        float* __restrict__ best_score, float* __restrict__ best_lm,
+                                        int32_t* __restrict__ steps_out, int32_t* __restrict__ err) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  const int steps = lmf_executed_steps(newdone, L, B);
+  if (b == 0) steps_out[0] = steps;
+  if (b >= B) return;
+  const int R = B * k;
+  int bl = -1, bc = -1;
+  float bv = 0.f, bs = 0.f, bq = 0.f;
+  for (int l = 0; l < steps; ++l)
+    for (int c = 0; c < k; ++c) {
+      const size_t ri = ((size_t)b * L + l) * k + c;
+      if (!rec_valid[ri]) continue;
+      const float v = lmf_comb(rec_score[ri], rec_lm[ri], lmw, lenw, l);
+      if (bl < 0 || v > bv) {
+        bl = l;
+        bc = c;
+        bv = v;
+        bs = rec_score[ri];
+        bq = rec_lm[ri];
+      }
+    }
+  int32_t* out = best_tokens + (size_t)b * L;
+  int len, slot, from;
+  if (bl >= 0) {
+    len = bl;
+    slot = rec_src[((size_t)b * L + bl) * k + bc];
+    from = bl - 1;
+  } else {  // the select of step l writes score[(l + 1) & 1]; the last executed step is steps - 1
+    const float* sf = (steps & 1) ? score1 : score0;
+    const float* gf = (steps & 1) ? g1 : g0;
+    const int ll = steps - 1;
+    int bj = 0;
+    for (int j = 0; j < k; ++j) {
+      const float v = lmf_comb(sf[b * k + j], gf[b * k + j], lmw, lenw, ll);
+      if (j == 0 || v > bv) {
+        bv = v;
+        bj = j;
+      }
+    }
+    bs = sf[b * k + bj];
+    bq = gf[b * k + bj];
+    len = ll + 1;
+    slot = bj;
+    from = ll;
+  }
+  for (int s = from; s >= 0; --s) {
+    if ((unsigned)slot >= (unsigned)k) {
+      atomicOr(err, CASR_DEV_BAD_BACKPTR);
+      slot = 0;
+    }
+    const size_t ix = (size_t)s * R + b * k + slot;
+    out[s] = tk[ix];
+    slot = bp[ix];
+  }
+  for (int s = len; s < L; ++s) out[s] = -1;
+  best_len[b] = len;
+  best_score[b] = bs;
+  best_lm[b] = bq;
+}
+
+hipError_t launch_beam_lm_finalize(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float lm_weight,
+                                   float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
+                                   float* best_lm, int32_t* steps, hipStream_t s) {
+  hipLaunchKernelGGL(beam_lm_finalize_kernel, dim3((a.B + 63) / 64), dim3(64), 0, s, a.B, a.k, a.max_len, lm_weight,
+                     length_weight, d.score[0], d.score[1], w.g[0], w.g[1], d.bp, d.tk, d.rec_score, w.rec_lm,
+                     d.rec_src, d.rec_valid, d.newdone, best_tokens, best_len, best_score, best_lm, steps, d.err);
+  return hipGetLastError();
+}
+
+// rec_lm of the valid records of the executed steps, 0 elsewhere
+__global__ void beam_record_lm_kernel(int B, int k, int L, const float* __restrict__ rec_lm,
+                                      const uint8_t* __restrict__ rec_valid, const int32_t* __restrict__ newdone,
+                                      float* __restrict__ out) {
+  const size_t n = (size_t)B * L * k;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int steps = lmf_executed_steps(newdone, L, B);
+  const int l = (int)((i / k) % L);
+  out[i] = (l < steps && rec_valid[i]) ? rec_lm[i] : 0.f;
+}
+
+hipError_t run_beam_record_lm(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float* rec_lm,
+                              hipStream_t s) {
+  const size_t n = (size_t)a.B * a.max_len * a.k;
+  hipLaunchKernelGGL(beam_record_lm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.B, a.k, a.max_len,
+                     w.rec_lm, d.rec_valid, d.newdone, rec_lm);
+  return hipGetLastError();
+}
+
+}  // namespace casr

@@ -213,6 +213,8 @@ struct casr_handle {
   Profiler prof;
   int dec_k = 0;
   bool beam_done = false;
+  bool beam_lm_done = false;  // the last beam was casr_beam_lm: lmws holds its rec_lm
+  DevBuf lmws;                // casr_beam_lm: term rows, LM sums, rec_lm (carve_beam_lm)
   float beam_lm_weight = 0.f, beam_length_weight = 0.f;  // the last casr_beam's (casr_beam_rescore's fallback)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
@@ -230,8 +232,10 @@ struct casr_handle {
 struct casr_lm {
   int device = -1;
   NgramTables host;
-  void* dev[2 + NGRAM_MAX_ORDER - 1] = {};  // uni, redirect, tab[0..2]
+  NgramSuccTables succ;  // the successor lists (ngram_succ.h): casr_lm_terms, casr_beam_lm
+  void* dev[11] = {};    // uni, redirect, tab[0..2]; succ: list[0..2], dir, ctab[0..1]
   NgramView dview{};
+  NgramSuccView dsucc{};
 };
 
 static int fail(casr_handle* h, int code, const char* fmt, ...);
@@ -580,7 +584,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist})
+                    &h->seg_q, &h->seg_hist, &h->lmws})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1300,6 +1304,7 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
   hipStream_t s = (hipStream_t)stream;
   h->dec_k = k;
   h->beam_done = true;
+  h->beam_lm_done = false;
   h->beam_lm_weight = lm_weight;
   h->beam_length_weight = length_weight;
   if (!decode_graph_ok(h)) {
@@ -1370,17 +1375,24 @@ int casr_lm_create(int device, int order, int vocab, const int64_t* count, const
     delete lm;
     return fail(nullptr, rc, "casr_lm_create: %s", why.c_str());
   }
+  ngram_succ_build(lm->host, count, ids, prob, &lm->succ);
   lm->device = device;
   if (device >= 0) {
     const NgramTables& t = lm->host;
-    const void* src[5] = {t.uni.data(), t.redirect.data(), t.tab[0].data(), t.tab[1].data(), t.tab[2].data()};
-    const size_t bytes[5] = {t.uni.size() * sizeof(NgramUni), t.redirect.size() * sizeof(int32_t),
-                             t.tab[0].size() * sizeof(NgramEntry), t.tab[1].size() * sizeof(NgramEntry),
-                             t.tab[2].size() * sizeof(NgramEntry)};
+    const NgramSuccTables& u = lm->succ;
+    const void* src[11] = {t.uni.data(), t.redirect.data(), t.tab[0].data(), t.tab[1].data(), t.tab[2].data(),
+                           u.list[0].data(), u.list[1].data(), u.list[2].data(), u.dir.data(), u.ctab[0].data(),
+                           u.ctab[1].data()};
+    const size_t bytes[11] = {t.uni.size() * sizeof(NgramUni), t.redirect.size() * sizeof(int32_t),
+                              t.tab[0].size() * sizeof(NgramEntry), t.tab[1].size() * sizeof(NgramEntry),
+                              t.tab[2].size() * sizeof(NgramEntry), u.list[0].size() * sizeof(NgramSucc),
+                              u.list[1].size() * sizeof(NgramSucc), u.list[2].size() * sizeof(NgramSucc),
+                              u.dir.size() * sizeof(NgramSuccRange), u.ctab[0].size() * sizeof(NgramCtxEntry),
+                              u.ctab[1].size() * sizeof(NgramCtxEntry)};
     hipError_t e = hipSetDevice(device);
-    for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-      e = hipMalloc(&lm->dev[i], bytes[i]);
-      if (e == hipSuccess) e = hipMemcpy(lm->dev[i], src[i], bytes[i], hipMemcpyHostToDevice);
+    for (int i = 0; i < 11 && e == hipSuccess; ++i) {
+      e = hipMalloc(&lm->dev[i], bytes[i] ? bytes[i] : 16);  // (an order without reachable n-grams: an empty list)
+      if (e == hipSuccess && bytes[i]) e = hipMemcpy(lm->dev[i], src[i], bytes[i], hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
       casr_lm_destroy(lm);
@@ -1390,6 +1402,10 @@ int casr_lm_create(int device, int order, int vocab, const int64_t* count, const
     lm->dview.uni = static_cast<const NgramUni*>(lm->dev[0]);
     lm->dview.redirect = static_cast<const int32_t*>(lm->dev[1]);
     for (int i = 0; i < NGRAM_MAX_ORDER - 1; ++i) lm->dview.tab[i] = static_cast<const NgramEntry*>(lm->dev[2 + i]);
+    lm->dsucc = u.view();
+    for (int i = 0; i < NGRAM_MAX_ORDER - 1; ++i) lm->dsucc.list[i] = static_cast<const NgramSucc*>(lm->dev[5 + i]);
+    lm->dsucc.dir = static_cast<const NgramSuccRange*>(lm->dev[8]);
+    for (int i = 0; i < NGRAM_MAX_ORDER - 2; ++i) lm->dsucc.ctab[i] = static_cast<const NgramCtxEntry*>(lm->dev[9 + i]);
   }
   *out = lm;
   return CASR_OK;
@@ -1437,6 +1453,8 @@ int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, doubl
   if (!h || !lm || !best_tokens || !best_len || !best_score)
     return fail(h, CASR_ERR_ARG, "casr_beam_rescore: NULL handle, LM or output");
   if (!h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_rescore before casr_beam");
+  if (h->beam_lm_done)
+    return fail(h, CASR_ERR_STATE, "casr_beam_rescore after casr_beam_lm: the second pass rescores a casr_beam");
   if (lm->device != h->device)
     return fail(h, CASR_ERR_ARG, "casr_beam_rescore: the LM is %s, the handle on device %d",
                 lm->device < 0 ? "host-only" : "on another device", h->device);
@@ -1451,6 +1469,86 @@ int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, doubl
   if (rc) return rc;
   HIP_OK(h, run_beam_rescore(c.a, h->d, lm->dview, lm_weight, length_weight, h->beam_lm_weight, h->beam_length_weight,
                              best_tokens, best_len, best_score, best_lm, rec_lm, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+// the refusals casr_lm_terms and casr_beam_lm share with casr_lm_score
+static int lm_on_handle(casr_handle* h, const casr_lm* lm, const char* who) {
+  if (lm->device != h->device)
+    return fail(h, CASR_ERR_ARG, "%s: the LM is %s, the handle on device %d", who,
+                lm->device < 0 ? "host-only" : "on another device", h->device);
+  if (lm->host.V != h->cfg.vocab)
+    return fail(h, CASR_ERR_ARG, "%s: the LM's vocab %d is not the handle's %d", who, lm->host.V, h->cfg.vocab);
+  if (!lm_terms_supported(lm->host.V))
+    return fail(h, CASR_ERR_UNSUPPORTED, "%s: a term row of %d words is past the %d KB of LDS it is assembled in", who,
+                lm->host.V, (int)(LM_TERMS_LDS_BYTES / 1024));
+  return CASR_OK;
+}
+
+int casr_lm_terms_host(const casr_lm* lm, const int32_t* ctx, const int32_t* nc, int n, int eos_token, float* terms) {
+  if (!lm || n < 0 || (n > 0 && (!ctx || !nc || !terms)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_lm_terms_host: NULL argument or n < 0");
+  const NgramView m = lm->host.view();
+  const NgramSuccView sv = lm->succ.view();
+  bool bad = false;
+  for (int i = 0; i < n; ++i)
+    ngram_terms_row(m, sv, ctx + (size_t)i * (NGRAM_MAX_ORDER - 1), nc[i], eos_token, terms + (size_t)i * m.V, &bad);
+  return CASR_OK;
+}
+
+int casr_lm_terms(casr_handle* h, const casr_lm* lm, const int32_t* ctx, const int32_t* nc, int n, int eos_token,
+                  float* terms, void* stream) {
+  if (!h || !lm || n < 0 || (n > 0 && (!ctx || !nc || !terms)))
+    return fail(h, CASR_ERR_ARG, "casr_lm_terms: NULL argument or n < 0");
+  int rc = lm_on_handle(h, lm, "casr_lm_terms");
+  if (rc) return rc;
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_lm_terms: no guard words");
+  const LmTermsSrc src{0, ctx, nc, nullptr, nullptr, nullptr, 0, 1, 0, 0};
+  HIP_OK(h, launch_lm_terms(lm->dview, lm->dsucc, src, n, eos_token, terms, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, float length_weight,
+                 int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm, int32_t* steps,
+                 void* stream) {
+  if (!h || !lm || !best_tokens || !best_len || !best_score || !best_lm || !steps)
+    return fail(h, CASR_ERR_ARG, "casr_beam_lm: NULL handle, LM or output");
+  if (!h->W) return fail(h, CASR_ERR_STATE, "casr_beam_lm before casr_bind_weights");
+  if (!h->encoded) return fail(h, CASR_ERR_STATE, "casr_beam_lm before casr_encode");
+  int rc = lm_on_handle(h, lm, "casr_beam_lm");
+  if (rc) return rc;
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  rc = prepare_decode(h, PLAN_BEAM_LM, k, false, c);
+  if (rc) return rc;
+  const DecodeArgs& a = c.a;
+  BeamLmBufs w{};
+  HIP_OK(h, h->lmws.ensure(carve_beam_lm(nullptr, a.B, a.plan.R, a.max_len, a.k, a.V, w)));
+  carve_beam_lm(h->lmws.p, a.B, a.plan.R, a.max_len, a.k, a.V, w);
+  h->dec_k = k;
+  h->beam_done = true;
+  h->beam_lm_done = true;
+  h->beam_lm_weight = lm_weight;
+  h->beam_length_weight = length_weight;
+  // (never a hipGraph: launched eagerly whatever casr_set_graphs says)
+  dg_trace_init();  // CASR_DG_TRACE diagnostics only
+  HIP_OK(h, run_beam_lm(a, h->d, w, lm->dview, lm->dsucc, lm_weight, length_weight, best_tokens, best_len, best_score,
+                        best_lm, steps, (hipStream_t)stream));
+  dg_trace_dump();
+  return CASR_OK;
+}
+
+int casr_beam_record_lm(casr_handle* h, float* rec_lm, void* stream) {
+  if (!h || !h->beam_done || !h->beam_lm_done) return fail(h, CASR_ERR_STATE, "casr_beam_record_lm before casr_beam_lm");
+  if (!rec_lm) return fail(h, CASR_ERR_ARG, "casr_beam_record_lm: NULL output");
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_BEAM_LM, h->dec_k, false, c);
+  if (rc) return rc;
+  BeamLmBufs w{};
+  carve_beam_lm(h->lmws.p, c.a.B, c.a.plan.R, c.a.max_len, c.a.k, c.a.V, w);
+  HIP_OK(h, run_beam_record_lm(c.a, h->d, w, rec_lm, (hipStream_t)stream));
   return CASR_OK;
 }
 

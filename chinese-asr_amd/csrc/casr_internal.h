@@ -8,6 +8,7 @@
 
 #include "casr.h"
 #include "encode_plan.h"
+#include "ngram_succ.h"
 #include "ngram_table.h"
 #include "resample_design.h"
 #include "segment_plan.h"
@@ -472,5 +473,56 @@ hipError_t run_beam_rescore(const DecodeArgs& a, const DecodeBufs& d, const Ngra
                             double length_weight, float beam_lm_weight, float beam_length_weight,
                             int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
                             float* rec_lm, hipStream_t s);
+
+// beam_lm.hip: the LM fused into the beam's first pass (casr_lm_terms, casr_beam_lm).
+// Where a term row's context comes from: tree == 0 the arrays ctx [n][3] / nc [n]; tree == 1 the beam
+// tree at decode step l (row i = b k + j: its tokens before, <s> before step 0), skipping the rows the
+// select of step l does not read
+struct LmTermsSrc {
+  int tree;
+  const int32_t* ctx;
+  const int32_t* nc;
+  const int32_t* bp;
+  const int32_t* tk;
+  const int32_t* newdone;
+  int l, k, B, R;
+};
+constexpr size_t LM_TERMS_LDS_BYTES = 64 * 1024;  // a term row (4 V bytes) is assembled in LDS
+bool lm_terms_supported(int V);
+// terms [n][V] of n rows; m and sv hold device pointers
+hipError_t launch_lm_terms(const NgramView& m, const NgramSuccView& sv, const LmTermsSrc& src, int n, int eos_token,
+                           float* terms, int32_t* err, hipStream_t s);
+// the fused beam's own buffers (handle-owned, beside DecodeBufs)
+struct BeamLmBufs {
+  float* terms;   // [R][V] the step's term rows
+  float* g[2];    // [R] the LM sums (ping-pong, as DecodeBufs::score)
+  float* rec_lm;  // [B][L][k] LM sum of each finished record
+};
+inline size_t carve_beam_lm(void* base, int B, int R, int L, int k, int V, BeamLmBufs& w) {
+  Carver c(base);
+  w.terms = c.rows((size_t)R * V);
+  for (int i = 0; i < 2; ++i) w.g[i] = c.take<float>(R);
+  w.rec_lm = c.take<float>((size_t)B * L * k);
+  return c.bytes(256);
+}
+// what the fused select has beyond a beam select's operands (BeamSelArgs)
+struct BeamLmArgs {
+  const float* terms;
+  const float* g_cur;
+  float* g_next;
+  float* rec_lm;
+  float lm_weight, len_l;  // len_l = (float)((double)length_weight (l + 1))
+};
+hipError_t launch_beam_lm_select(const BeamSelArgs& a, const BeamLmArgs& g, int K2, hipStream_t s);
+hipError_t launch_beam_lm_finalize(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float lm_weight,
+                                   float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
+                                   float* best_lm, int32_t* steps, hipStream_t s);
+hipError_t run_beam_record_lm(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float* rec_lm,
+                              hipStream_t s);
+// decoder.hip: run_beam's steps (a.plan: the PLAN_BEAM_LM caller's) with the term rows and the fused
+// select after each
+hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, const NgramView& m,
+                       const NgramSuccView& sv, float lm_weight, float length_weight, int32_t* best_tokens,
+                       int32_t* best_len, float* best_score, float* best_lm, int32_t* steps, hipStream_t s);
 
 }  // namespace casr

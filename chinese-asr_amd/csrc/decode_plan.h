@@ -129,7 +129,9 @@ inline int fold_gemm_shape(bool beam, int R, bool ksplit) {
 }
 
 // ---------------------------------------------------------------- the plan
-enum { PLAN_GREEDY = 0, PLAN_BEAM = 1, PLAN_SCORE = 2 };  // the API call that decodes
+// the API call that decodes.  PLAN_BEAM_LM (casr_beam_lm): casr_beam's steps at that shape; the select,
+// which ranks with the LM term, is always a launch of its own (it reads the whole logits row)
+enum { PLAN_GREEDY = 0, PLAN_BEAM = 1, PLAN_SCORE = 2, PLAN_BEAM_LM = 3 };
 enum {
   PLAN_OK = 0,
   PLAN_BAD_K,     // beam width outside [1, KMAX_BEAM]: an argument error
@@ -209,7 +211,7 @@ inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align,
                               const Tuning& t, const BlobFacts& blob, const AttnStaticLds& lds, int score_len = 0) {
   DecodePlan p{};
   const int V = cfg.vocab, L = cfg.max_len;
-  const bool greedy = caller == PLAN_GREEDY, beam = caller == PLAN_BEAM;
+  const bool greedy = caller == PLAN_GREEDY, beam = caller == PLAN_BEAM || caller == PLAN_BEAM_LM;
   if (!beam) k = 1;
   p.caller = caller;
   p.B = B;
@@ -286,7 +288,7 @@ inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align,
     p.fuse_select = t[CASR_OPT_FUSE_SELECT] && p.partials;
   // beam: the folded step with one attention block per utterance (k = 4 or 8 rows per block), or
   // k = 8 at 4 rows per attention block (both blocks of an utterance run the select, CELL 4)
-  if (beam)
+  if (caller == PLAN_BEAM)
     p.fuse_select = p.fold && t[CASR_OPT_FUSE_SELECT] && (k == 4 || k == 8) && (p.kpb == k || (k == 8 && p.kpb == 4));
   // greedy fold at R <= 64 (CASR_OPT_ATTN_SPLIT; 1: ranges by R, 2..AT_SPLIT_MAX: that many): ranges
   // of a multiple of 4 steps; not with an alignment output, and a short input stays unsplit

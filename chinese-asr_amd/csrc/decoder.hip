@@ -1942,4 +1942,43 @@ hipError_t run_beam_records(const DecodeArgs& a, DecodeBufs& d, int32_t* rec_tok
   return hipGetLastError();
 }
 
+// casr_beam_lm: run_beam's steps as the plan picks them for casr_beam at this shape (fuse_select is
+// off for this caller, so the folded attention takes the select's tokens from d.tok / d.src), and
+// after each step the term rows of the rows' contexts (beam_lm.hip) and the fused select
+hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, const NgramView& m,
+                       const NgramSuccView& sv, float lm_weight, float length_weight, int32_t* best_tokens,
+                       int32_t* best_len, float* best_score, float* best_lm, int32_t* steps, hipStream_t s) {
+  const int R = a.B * a.k;
+  if (a.plan.caller != PLAN_BEAM_LM || a.plan.fuse_select) return hipErrorInvalidValue;
+  FillList fl;
+  fl.add32(d.newdone, 0, a.max_len);
+  fl.add8(d.topfin, 0, a.B);
+  hipError_t e0 = fill_multi(fl, s);
+  if (e0 != hipSuccess) return e0;
+  hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, a.k,
+                     a.sos, d.tok[0], d.src[0], d.score[0], nullptr);
+  for (int l = 0; l < a.max_len; ++l) {
+    hipError_t e;
+    if (!a.plan.fold) {
+      e = decode_step(a, d, l, a.B, nullptr, s);
+    } else if (l == 0) {
+      e = decode_step(a, d, 0, a.B, nullptr, s, nullptr, false);
+    } else {
+      e = fold_attention_step(a, d, l, a.B, nullptr, false, GreedySel{}, s, nullptr);
+    }
+    if (e == hipSuccess && a.plan.fold) e = fold_gemm_step(a, d, l, a.B, s);
+    if (e != hipSuccess) return e;
+    ProfScope ps(a.prof, CASR_K_SELECT, s);
+    const LmTermsSrc src{1, nullptr, nullptr, d.bp, d.tk, d.newdone, l, a.k, a.B, R};
+    e = launch_lm_terms(m, sv, src, R, a.eos, w.terms, d.err, s);
+    if (e != hipSuccess) return e;
+    const BeamLmArgs g{w.terms, w.g[l & 1], w.g[(l + 1) & 1], w.rec_lm, lm_weight,
+                       (float)((double)length_weight * (double)(l + 1))};
+    e = launch_beam_lm_select(beam_sel_args(a, d, l), g, a.plan.K2, s);
+    if (e != hipSuccess) return e;
+  }
+  return launch_beam_lm_finalize(a, d, w, lm_weight, length_weight, best_tokens, best_len, best_score, best_lm, steps,
+                                 s);
+}
+
 }  // namespace casr

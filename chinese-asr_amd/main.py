@@ -69,8 +69,8 @@ def features_for(audios):
     return [feat[b, :int(lens[b])] for b in range(len(audios))], lens
 
 
-def parse(path, model, audio_base, lm_model, bw):
-    """main.py:27-65: one file -> predicted text."""
+def parse(path, model, audio_base, lm_model, bw, fusion=False):
+    """main.py:27-65: one file -> predicted text.  ``fusion``: Model.eval_one_batch_with_beam's."""
     data, lens = features_for(read_audio([path]))
     text = None
     if bw is not None:
@@ -78,7 +78,7 @@ def parse(path, model, audio_base, lm_model, bw):
             print(f"[INFO] Beam Decode [bw={bw}]...")
         res = model.eval_one_batch_with_beam(model.device, bw, data, lens, text, audio_base.int2word,
                                              second_pass=True if lm_model is not None else False,
-                                             lm_model=lm_model, lm_weight=1.5, length_weight=1.5)
+                                             lm_model=lm_model, lm_weight=1.5, length_weight=1.5, fusion=fusion)
     else:
         res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, text)
     return res.pred_text[0]
@@ -94,14 +94,14 @@ def align(path, text, model, audio_base):
     return [(ch, float(start[i]), float(res.token_logp[0][i])) for i, ch in enumerate(text)]
 
 
-def parse_batch(paths, model, audio_base, lm_model=None, bw=None):
+def parse_batch(paths, model, audio_base, lm_model=None, bw=None, fusion=False):
     """Batched form of parse (the reference's __init__.py names it but never defines it): all
     files go through the GPU path as one batch."""
     data, lens = features_for(read_audio(paths))
     if bw is not None:
         res = model.eval_one_batch_with_beam(model.device, bw, data, lens, None, audio_base.int2word,
                                              second_pass=lm_model is not None, lm_model=lm_model,
-                                             lm_weight=1.5, length_weight=1.5)
+                                             lm_weight=1.5, length_weight=1.5, fusion=fusion)
     else:
         res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, None)
     return list(res.pred_text)
@@ -110,7 +110,7 @@ def parse_batch(paths, model, audio_base, lm_model=None, bw=None):
 MIN_SEGMENT_FRAMES = 9  # the delta filters' 9 taps: a shorter segment is returned with empty text
 
 
-def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, batch_size=256):
+def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, batch_size=256, fusion=False):
     """Recordings of any length -> per recording a list of casr.segment.Segment (start_s, end_s, text,
     score, truncated), this path's own addition: the log-mel of every recording is cut at its pauses
     on the device (casr_segment, include/casr.h; ``params`` a casr.segment.SegmentParams) and the
@@ -154,7 +154,7 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
         if bw is not None:
             res = model.eval_one_batch_with_beam(model.device, bw, data, flen, None, audio_base.int2word,
                                                  second_pass=lm_model is not None, lm_model=lm_model,
-                                                 lm_weight=1.5, length_weight=1.5)
+                                                 lm_weight=1.5, length_weight=1.5, fusion=fusion)
             # no finished hypothesis: the fallback ran to max_len
             cut = (~model.engine.beam_records()[2].flatten(1).bool().any(1)).cpu().tolist()
         else:
@@ -170,9 +170,11 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
 class ASR:
     """main.py:68-102."""
 
-    def __init__(self, lm_path=None, bw=None, ckpt='./pretrain-0.06328.ckpt', lm_backend="kenlm"):
+    def __init__(self, lm_path=None, bw=None, ckpt='./pretrain-0.06328.ckpt', lm_backend="kenlm", fusion=False):
         """lm_backend "kenlm" (default: the reference's import) or "casr": the library's own ARPA
-        n-gram LM (casr.ngram.NgramLM), rescored on the device."""
+        n-gram LM (casr.ngram.NgramLM), rescored on the device; with ``fusion`` (the "casr" backend
+        only) fused into the beam's first pass instead (Model.eval_one_batch_with_beam)."""
+        self.fusion = bool(fusion)
         if lm_backend not in ("kenlm", "casr"):
             raise ValueError(f"lm_backend must be 'kenlm' or 'casr', got {lm_backend!r}")
         want_lm = lm_path is not None and bw is not None and bw > 1
@@ -199,11 +201,12 @@ class ASR:
         self.bw = bw
 
     def __call__(self, path):
-        return parse(path, self.model, self.audio_base, self.lm_model, self.bw)
+        return parse(path, self.model, self.audio_base, self.lm_model, self.bw, fusion=self.fusion)
 
     def transcribe(self, path, params=None):
         """A recording of any length -> its text: the segments' texts of transcribe(), joined."""
-        segs = transcribe([path], self.model, self.audio_base, self.lm_model, self.bw, params=params)[0]
+        segs = transcribe([path], self.model, self.audio_base, self.lm_model, self.bw, params=params,
+                          fusion=self.fusion)[0]
         return ''.join(s.text for s in segs)
 
 

@@ -130,9 +130,26 @@ class Model(object):
     @torch.no_grad()
     def eval_one_batch_with_beam(self, device, bmsz, data, lens, text, int2word,
                                  second_pass=gpd['second_pass'], lm_model=None,
-                                 lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight']):
-        """model.py:604-987."""
+                                 lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight'], fusion=False):
+        """model.py:604-987.  ``fusion`` (this path's own addition, default off): with an NgramLM as
+        ``lm_model`` the LM is fused into the first pass on the device (casr_beam_lm: every candidate
+        ranked by logp + lm_weight lm + length_weight (l + 1), the ranking model.py:843-857 was designed
+        for) and no second pass runs; ``score`` is the choice's acoustic log-probability.  A duck-typed
+        host scorer cannot be fused: TypeError."""
         self.model.eval()
+        if fusion:
+            if not isinstance(lm_model, NgramLM):
+                raise TypeError(f"fusion=True needs a casr.ngram.NgramLM as lm_model, got {type(lm_model).__name__}")
+            bsz, _, r = self._run(data, lens, lambda: self.engine.beam_lm(lm_model, bmsz, lm_weight, length_weight))
+            toks, blen, bscore = (r[n].cpu().numpy() for n in ('tokens', 'length', 'score'))
+            i2w = self._int2word(int2word)
+            pred_text = [''.join([i2w[idx] for idx in toks[b, :blen[b]].tolist()]) for b in range(bsz)]
+            wer = None
+            if text is not None:
+                text = [''.join([i2w[idx] for idx in ele]) for ele in text]
+                wer = np.mean([get_wer(p, t) for p, t in zip(pred_text, text)])
+            return EvalOutput(pred_text=pred_text, score=[float(s) for s in bscore], text=text, wer=wer, n=bsz,
+                              alignment=None, audio_feat_len=None, text_len=None)
         # an NgramLM (casr/ngram.py) is rescored on the device from the beam tree: no record copy and
         # no host pass; any other lm_model keeps the host second pass below
         on_device = bool(second_pass) and isinstance(lm_model, NgramLM)

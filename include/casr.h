@@ -435,6 +435,69 @@ int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, doubl
                       int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
                       float* rec_lm, void* stream);
 
+/* The term of EVERY ASR token under one context, per row: terms[i][v], v in [0, V), is the Word term
+ * above of w(v) after row i's context, where w(v) = </s> for v == eos_token (pass -1 for none) and v
+ * itself otherwise (redirected to <unk> without a unigram, as everywhere).  ctx [n][3]: the up to
+ * three LM ids before, NEAREST FIRST, of which the first nc[i] (0 .. N - 1) are read.  An id outside
+ * [0, V + 3) scores as <unk>, an nc outside [0, N - 1] is clamped; both raise guard bit 1.
+ * The result is the per-word query's, bit for bit, but a row costs V sequential reads plus its
+ * context's successors instead of V hash queries: casr_lm_create also builds, per order n = 2..N,
+ * successor lists (csrc/ngram_succ.h): the n-grams that start with an (n - 1)-word context stored as
+ * {int32 w, f32 prob}, contiguous per context and ascending in w; the context is located through a
+ * direct array [V + 3] of {offset, count} at n = 2 and through an open-addressing table {uint64 key,
+ * uint32 offset, uint32 count} at n = 3, 4 (the key packing, slot function and linear probing of the
+ * n-gram tables; independent of them, since a context with successors need not itself be an n-gram).
+ * N-grams with a word that has no unigram are left out (no redirected query reaches them).  A row:
+ * (1) the context's up to three backoffs, looked up once; (2) the dense chain ((uni[w].prob + bo_1) +
+ * bo_2) + bo_3 over the backoffs that exist (the m = 1 case); (3) the successors of orders 2, 3, 4 in
+ * that order, each overwriting with prob_m plus the backoffs of orders >= m, so the highest order
+ * wins; (4) <unk> (every token without a unigram) and </s> by one ordinary query each.
+ * casr_lm_terms_host: HOST pointers, any LM object, no GPU.  casr_lm_terms: DEVICE pointers, one
+ * workgroup per row, which assembles the row in LDS and writes it once; returns after enqueueing.
+ * CASR_ERR_ARG: a NULL argument, n < 0, an LM that is host-only or on another device, or whose vocab
+ * is not the handle's.  CASR_ERR_UNSUPPORTED: a row past the LDS it is assembled in (4 V bytes > 64 KB:
+ * V > 16,384).  Nothing is launched or written on an error. */
+int casr_lm_terms_host(const casr_lm* lm, const int32_t* ctx, const int32_t* nc, int n, int eos_token,
+                       float* terms);
+int casr_lm_terms(casr_handle* h, const casr_lm* lm, const int32_t* ctx, const int32_t* nc, int n, int eos_token,
+                  float* terms, void* stream);
+
+/* Beam search with the n-gram LM fused into the first pass (shallow fusion; the ranking the reference's
+ * beam was designed for, model.py:843-857): the LM decides which hypotheses stay in the beam, not only
+ * which finished one wins.  Every beam row carries two f32 sums: a, the acoustic log-probabilities
+ * (exactly what casr_beam carries as its score), and g, the LM terms.  At step l, row r ranks
+ * candidate v by
+ *     am  = (x_v / T - lse_r) + a_r         casr_beam's value, the same bits
+ *     lm  = l == 0 ? term : g_r + term      term = the Word term of v after r's up to N - 1 tokens
+ *                                           before (<s> before step 0); v == eos scores </s>
+ *     val = (am + lm_weight lm) + len_l     len_l = (float)((double)length_weight (double)(l + 1))
+ * each operation an f32 operation rounded on its own (never contracted).  Top 2k of val per utterance,
+ * ties to the lower flat index, step 0 ranking beam 0 only; the record, early-stop and active-set
+ * bookkeeping is casr_beam's, on that ranking.  The chosen candidates pass on am and lm, not val: a
+ * finished record stores am (casr_beam_records returns it) and lm (casr_beam_record_lm: rec_lm
+ * [B][max_len][k], 0 where there is no valid record), so a record's lm is its Sentence score under bos,
+ * the same adds in the same order.  The best hypothesis is the first maximum over an utterance's valid
+ * records, in (step, rank) order, of (rec_score + lm_weight rec_lm) + len_l (l the record's step);
+ * without a record, the first maximum over the k live rows of the same expression at the last executed
+ * step.  best_score is the choice's am, best_lm its lm.  With both weights 0 every output equals
+ * casr_beam's bit for bit.
+ * A row's context is read off the beam tree on the device.  The decode steps are those casr_beam runs
+ * at the same shape; the select is always a launch of its own (CASR_OPT_FUSE_SELECT does not apply)
+ * that reads the whole logits row and the row's terms, which casr_lm_terms' kernel wrote to a handle-
+ * owned workspace of R V floats just before (41 MB at R = 2,048).  It counts under CASR_K_SELECT.
+ * Never replayed as a hipGraph; no float atomics; results do not depend on scheduling.  A token id
+ * outside [0, V) in the tree scores as <unk> (guard bit 1), a back-pointer outside [0, k) is clamped
+ * (guard bit 16).  Returns after enqueueing.
+ * CASR_ERR_STATE before an encode or before weights are bound; CASR_ERR_ARG: a NULL handle, LM or
+ * output, an LM that is host-only or on another device, or whose vocab is not the handle's, k outside
+ * 1..16; CASR_ERR_UNSUPPORTED: V > 16,384 (a term row is assembled in 64 KB of LDS, 4 V bytes).  After
+ * it, casr_beam_rescore returns CASR_ERR_STATE (its fallback assumes casr_beam's scores) until the next
+ * casr_beam; casr_beam_record_lm returns CASR_ERR_STATE unless the last beam was a casr_beam_lm. */
+int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, float length_weight,
+                 int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm, int32_t* steps,
+                 void* stream);
+int casr_beam_record_lm(casr_handle* h, float* rec_lm, void* stream);
+
 /* Guard bits raised by the device since the previous casr_device_flags call (read and clear;
  * they accumulate over every encode / decode / log-mel call in between, so one read after a
  * series of calls vouches for all of them; 0 = clean): a data-dependent index out of range (1 token, 2 predecessor row, 4 NaN logit
