@@ -357,6 +357,62 @@ class Engine:
         _lib.check(self.lib.casr_beam_record_lm(self.handle, _ptr(rec_lm), _stream()), self.handle)
         return rec_lm
 
+    def edit_distance(self, a, a_len, b, b_len, ops=False):
+        """Edit distances of n pairs on the device (casr_edit_distance): a [n, La], b [n, Lb] int32
+        symbols (1 <= La, Lb <= casr.lib.EDIT_MAX_LEN), a_len and b_len [n] -> dist [n] int32, and with
+        ``ops`` the (insert, delete, replace) counts [n, 3] of the script turning a into b; the values
+        casr.lib.edit_distance_host gives.  Needs no weights and no encode; returns after enqueueing."""
+        dev = self.device
+        a = torch.as_tensor(a).to(dev, torch.int32).contiguous()
+        b = torch.as_tensor(b).to(dev, torch.int32).contiguous()
+        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+            raise ValueError("edit_distance: a must be [n, La] and b [n, Lb]")
+        n = a.shape[0]
+        a_len = torch.as_tensor(a_len).to(dev, torch.int32).contiguous()
+        b_len = torch.as_tensor(b_len).to(dev, torch.int32).contiguous()
+        if a_len.shape != (n,) or b_len.shape != (n,):
+            raise ValueError(f"edit_distance: a_len and b_len must be [n={n}]")
+        dist = torch.empty(n, dtype=torch.int32, device=dev)
+        counts = torch.empty(n, 3, dtype=torch.int32, device=dev) if ops else None
+        _lib.check(self.lib.casr_edit_distance(self.handle, _ptr(a), _ptr(a_len), int(a.shape[1]), _ptr(b), _ptr(b_len),
+                                               int(b.shape[1]), n, _ptr(dist), _ptr(counts), _stream()), self.handle)
+        self._keep_edit = (a, a_len, b, b_len)  # read by the enqueued kernel
+        return (dist, counts) if ops else dist
+
+    def beam_mbr(self, scale, lm=None, lm_weight=0.0, length_weight=0.0, records=False):
+        """The minimum-Bayes-risk choice over the last beam()'s finished hypotheses on the device
+        (casr_beam_mbr): per utterance the record with the lowest expected edit distance to the
+        others under the posterior exp(scale (c - c_max)), c the second pass's combined score.  With
+        ``lm`` (a casr.ngram.NgramLM) the rescore runs first for the records' LM scores.  Returns
+        tokens [B, max_len] (-1 past the length), length [B], score [B] (the choice's first-pass
+        score), index [B] (step k + rank, -1 where the utterance had no record and keeps beam()'s
+        fallback), risk [B] float64, and with ``records`` rec_risk [B, max_len, k]."""
+        B, L, k = self._B, self.cfg.max_len, self._k
+        dev = self.device
+        rec_lm = None
+        if lm is not None:
+            rec_lm = self.beam_rescore(lm, lm_weight, length_weight, records=True)["rec_lm"]
+        toks = torch.empty(B, L, dtype=torch.int32, device=dev)
+        blen = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        index = torch.empty(B, dtype=torch.int32, device=dev)
+        risk = torch.empty(B, dtype=torch.float64, device=dev)
+        rec_risk = torch.empty(B, L, k, dtype=torch.float64, device=dev) if records else None
+        _lib.check(self.lib.casr_beam_mbr(self.handle, float(scale), _ptr(rec_lm), float(lm_weight if lm is not None else 0.0),
+                                          float(length_weight), _ptr(toks), _ptr(blen), _ptr(score), _ptr(index),
+                                          _ptr(risk), _ptr(rec_risk), _stream()), self.handle)
+        self._keep_mbr = (rec_lm,)  # read by the enqueued kernels
+        return dict(tokens=toks, length=blen, score=score, index=index, risk=risk, rec_risk=rec_risk, rec_lm=rec_lm)
+
+    def beam_mbr_distances(self):
+        """The distances of the last beam_mbr() (casr_beam_mbr_distances): dist [B, max_len k, max_len k]
+        uint8 over each utterance's valid records in (step, rank) order, and their counts [B]."""
+        B, LK = self._B, self.cfg.max_len * self._k
+        dist = torch.empty(B, LK, LK, dtype=torch.uint8, device=self.device)
+        n_rec = torch.empty(B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.casr_beam_mbr_distances(self.handle, _ptr(dist), _ptr(n_rec), _stream()), self.handle)
+        return dist, n_rec
+
     def score(self, targets, tgt_len, alignment=False, best=False, mean=False):
         """Teacher-forced pass over the last encode (casr_score): targets [B, L] int (1 <= L <=
         max_len), tgt_len [B] scored positions per utterance.  Returns token_logp [B, L] (0 past

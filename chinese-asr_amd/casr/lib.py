@@ -28,6 +28,7 @@ EXPORTS = [
     "casr_lm_terms_host", "casr_lm_terms", "casr_beam_lm", "casr_beam_record_lm",
     "casr_segment_default_params", "casr_segment_bound", "casr_segment_host", "casr_segment",
     "casr_gather_segments",
+    "casr_edit_distance_host", "casr_edit_distance", "casr_mbr_host", "casr_beam_mbr", "casr_beam_mbr_distances",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -44,7 +45,7 @@ OPTIONS = {"FUSE_SELECT": 0, "REC_LAYOUT": 1, "REC_STORE_PLAIN": 2, "REC_SLEEP":
            "REC_COOP": 5, "GEMM16_PERSIST": 6, "GEMM16_TAIL": 7, "ATTN_KPB": 8, "ATTN_DIRECT": 9,
            "DEC_FOLD": 10, "REC_COOP_REFUSE": 11, "DIAG_COLD": 12,
            "LOGMEL_Q16": 13, "KEYS_ROWS": 14, "X16_KM": 15, "DEC_KSPLIT": 16, "GEMM16_LEAN": 17,
-           "ATTN_SPLIT": 18}
+           "ATTN_SPLIT": 18, "MBR_MAP": 19}
 
 # kernel classes of casr_profile_enable / casr_profile_read (include/casr.h)
 KERNEL_CLASSES = ["features", "input_proj", "rec_step", "keys", "dec_lstm", "attention", "proj", "select"]
@@ -142,6 +143,11 @@ def load(path=None, variant=None):
         "casr_segment_host": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
         "casr_segment": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
         "casr_gather_segments": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
+        "casr_edit_distance_host": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp]),
+        "casr_edit_distance": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
+        "casr_mbr_host": (i32, [vp, vp, vp, vp, i32, i32, i32] + [ctypes.c_double] * 3 + [vp, vp]),
+        "casr_beam_mbr": (i32, [vp, ctypes.c_double, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]),
+        "casr_beam_mbr_distances": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -260,3 +266,54 @@ def pack_weights(cfg, enc_sd, dec_sd):
     out = np.empty(n, np.float32)
     check(lib.casr_pack_weights(ctypes.byref(c), ctypes.byref(w), out.ctypes.data_as(ctypes.c_void_p)))
     return out
+
+
+EDIT_MAX_LEN = 512  # include/casr.h CASR_EDIT_MAX_LEN: the longest row of the device entry
+
+
+def _i32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if shape is not None and a.shape != shape:
+        raise ValueError(f"expected an int32 array of shape {shape}, got {a.shape}")
+    return a
+
+
+def edit_distance_host(a, a_len, b, b_len, ops=False):
+    """casr_edit_distance_host: a [n, La], b [n, Lb] int32 symbols with their lengths -> dist [n] int32,
+    and with ``ops`` the (insert, delete, replace) counts [n, 3] of the script turning a into b
+    (casr.results.edit_distance / edit_ops, value for value).  Host only, no GPU."""
+    lib = load()
+    a, b = np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError("edit_distance_host: a must be [n, La] and b [n, Lb]")
+    n = a.shape[0]
+    a_len, b_len = _i32(a_len, (n,)), _i32(b_len, (n,))
+    dist = np.zeros(n, np.int32)
+    counts = np.zeros((n, 3), np.int32) if ops else None
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None and x.size else None  # noqa: E731
+    check(lib.casr_edit_distance_host(p(a), p(a_len), a.shape[1], p(b), p(b_len), b.shape[1], n, p(dist), p(counts)),
+          lib=lib)
+    return (dist, counts) if ops else dist
+
+
+def mbr_host(rec_tokens, rec_score, rec_valid, scale, rec_lm=None, lm_weight=0.0, length_weight=0.0, risk=False):
+    """casr_mbr_host on the arrays casr_beam_records writes: rec_tokens [B, L, k, L], rec_score and
+    rec_valid [B, L, k], rec_lm None or [B, L, k] -> best_index [B] (step k + rank, -1 without a
+    record), and with ``risk`` rec_risk [B, L, k] float64.  Host only, no GPU."""
+    lib = load()
+    rt = np.ascontiguousarray(rec_tokens, dtype=np.int32)
+    B, L, k = rt.shape[:3]
+    if rt.shape != (B, L, k, L):
+        raise ValueError("mbr_host: rec_tokens must be [B, L, k, L]")
+    rs = np.ascontiguousarray(rec_score, dtype=np.float32)
+    rv = np.ascontiguousarray(rec_valid, dtype=np.uint8)
+    rl = None if rec_lm is None else np.ascontiguousarray(rec_lm, dtype=np.float32)
+    for x in (rs, rv) + ((rl,) if rl is not None else ()):
+        if x.shape != (B, L, k):
+            raise ValueError("mbr_host: rec_score, rec_valid and rec_lm must be [B, L, k]")
+    best = np.full(B, -1, np.int32)
+    rr = np.zeros((B, L, k), np.float64) if risk else None
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None and x.size else None  # noqa: E731
+    check(lib.casr_mbr_host(p(rt), p(rs), p(rv), p(rl), B, L, k, float(scale), float(lm_weight), float(length_weight),
+                            p(best), p(rr)), lib=lib)
+    return (best, rr) if risk else best

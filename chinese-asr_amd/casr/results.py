@@ -76,6 +76,48 @@ def get_wer(pred, ref, normalize=True, return_tuple=False):
     return tuple(e / n for e in r) if normalize else r
 
 
+def _symbol_rows(seqs):
+    """Sequences -> (rows [n, L] int32 padded with 0, L at least 1; lens [n] int32).  A string becomes
+    its UTF-32 code points; anything else is taken as a list of int32 ids."""
+    rows = [np.frombuffer(s.encode('utf-32-le', 'surrogatepass'), dtype='<i4') if isinstance(s, str)
+            else np.asarray(s, dtype=np.int32).reshape(-1) for s in seqs]
+    lens = np.array([len(r) for r in rows], np.int32)
+    out = np.zeros((len(rows), max([1] + lens.tolist())), np.int32)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    return out, lens
+
+
+def wer_batch(preds, refs, normalize=True, return_tuple=False, engine=None):
+    """``[get_wer(p, r, normalize, return_tuple) for p, r in zip(preds, refs)]`` in one call of the HIP
+    library: the same Python values (the same integer over the same ``len(ref) * 1.``, the same
+    ZeroDivisionError for an empty reference under ``normalize``).  Strings are compared by code
+    point, id lists by id.  With an ``engine`` (casr.engine.Engine) and every row within
+    casr.lib.EDIT_MAX_LEN symbols the pairs go to the device (casr_edit_distance), else to the host
+    entry (casr_edit_distance_host)."""
+    from . import lib as _lib
+    preds, refs = list(preds), list(refs)
+    n = min(len(preds), len(refs))  # (zip's rule)
+    a, a_len = _symbol_rows(preds[:n])
+    b, b_len = _symbol_rows(refs[:n])
+    if engine is not None and n and max(a.shape[1], b.shape[1]) <= _lib.EDIT_MAX_LEN:
+        r = engine.edit_distance(a, a_len, b, b_len, ops=return_tuple)
+        dist, ops = (r[0].cpu().numpy(), r[1].cpu().numpy()) if return_tuple else (r.cpu().numpy(), None)
+    else:
+        r = _lib.edit_distance_host(a, a_len, b, b_len, ops=return_tuple)
+        dist, ops = r if return_tuple else (r, None)
+    out = []
+    for i, d in enumerate(dist.tolist()):
+        m = int(b_len[i]) * 1.
+        if not return_tuple:
+            out.append(d / m if normalize else d)
+            continue
+        ins, dele, rep = ops[i].tolist()
+        t = (ins + dele + rep, ins, dele, rep)
+        out.append(tuple(e / m for e in t) if normalize else t)
+    return out
+
+
 def greedy_outputs(tokens, out_len, finished, accum):
     """model.py:582-593.  Host numpy inputs.  Returns (token lists, scores)."""
     toks = [tokens[b, :out_len[b]].tolist() for b in range(tokens.shape[0])]

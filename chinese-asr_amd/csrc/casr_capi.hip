@@ -12,6 +12,7 @@
 
 #include "casr.h"
 #include "casr_internal.h"
+#include "edit_plan.h"
 
 namespace casr {
 
@@ -216,6 +217,8 @@ struct casr_handle {
   bool beam_lm_done = false;  // the last beam was casr_beam_lm: lmws holds its rec_lm
   DevBuf lmws;                // casr_beam_lm: term rows, LM sums, rec_lm (carve_beam_lm)
   float beam_lm_weight = 0.f, beam_length_weight = 0.f;  // the last casr_beam's (casr_beam_rescore's fallback)
+  DevBuf mbrws;           // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
+  bool mbr_done = false;  // mbrws holds the distances of the last beam's records
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
   // fallback does.  Default 2: the decode loop launches eagerly (measured faster)
@@ -584,7 +587,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist, &h->lmws})
+                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1305,6 +1308,7 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
   h->dec_k = k;
   h->beam_done = true;
   h->beam_lm_done = false;
+  h->mbr_done = false;
   h->beam_lm_weight = lm_weight;
   h->beam_length_weight = length_weight;
   if (!decode_graph_ok(h)) {
@@ -1472,6 +1476,87 @@ int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, doubl
   return CASR_OK;
 }
 
+int casr_edit_distance_host(const int32_t* a, const int32_t* a_len, int La, const int32_t* b, const int32_t* b_len,
+                            int Lb, int n, int32_t* dist, int32_t* ops) {
+  if (n < 0 || La < 0 || Lb < 0 || (n > 0 && (!a_len || !b_len || !dist || (!a && La > 0) || (!b && Lb > 0))))
+    return fail(nullptr, CASR_ERR_ARG, "casr_edit_distance_host: NULL argument, or n, La or Lb < 0");
+  for (int i = 0; i < n; ++i)
+    if (a_len[i] < 0 || a_len[i] > La || b_len[i] < 0 || b_len[i] > Lb)
+      return fail(nullptr, CASR_ERR_ARG, "casr_edit_distance_host: pair %d has lengths %d, %d outside [0, %d], [0, %d]", i,
+                  a_len[i], b_len[i], La, Lb);
+  for (int i = 0; i < n; ++i)
+    dist[i] = edit_distance_rows(a + (size_t)i * La, a_len[i], b + (size_t)i * Lb, b_len[i],
+                                 ops ? ops + (size_t)i * 3 : nullptr);
+  return CASR_OK;
+}
+
+int casr_edit_distance(casr_handle* h, const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
+                       const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops, void* stream) {
+  if (!h || n < 0 || (n > 0 && (!a || !a_len || !b || !b_len || !dist)))
+    return fail(h, CASR_ERR_ARG, "casr_edit_distance: NULL argument or n < 0");
+  if (edit_plan_pairs(La, Lb, n, ops != nullptr).form == EDIT_FORM_NONE)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_edit_distance: La = %d, Lb = %d not in [1, %d]", La, Lb, EDIT_MAX_LEN);
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_edit_distance: no guard words");
+  HIP_OK(h, launch_edit_pairs(a, a_len, La, b, b_len, Lb, n, dist, ops, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_mbr_host(const int32_t* rec_tokens, const float* rec_score, const uint8_t* rec_valid, const float* rec_lm,
+                  int B, int max_len, int k, double scale, double lm_weight, double length_weight, int32_t* best_index,
+                  double* rec_risk) {
+  if (B < 0 || max_len < 1 || k < 1 || (B > 0 && (!rec_tokens || !rec_score || !rec_valid || !best_index)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_mbr_host: NULL argument, B < 0, or max_len or k < 1");
+  if (!(scale >= 0.0) || !std::isfinite(scale))
+    return fail(nullptr, CASR_ERR_ARG, "casr_mbr_host: scale %g is negative or not finite", scale);
+  const size_t LK = (size_t)max_len * k;
+  for (int b = 0; b < B; ++b)
+    best_index[b] = mbr_utterance_host(rec_tokens + b * LK * max_len, rec_score + b * LK, rec_valid + b * LK,
+                                       rec_lm ? rec_lm + b * LK : nullptr, max_len, k, scale, lm_weight, length_weight,
+                                       rec_risk ? rec_risk + b * LK : nullptr);
+  return CASR_OK;
+}
+
+int casr_beam_mbr(casr_handle* h, double scale, const float* rec_lm, double lm_weight, double length_weight,
+                  int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* best_index, double* best_risk,
+                  double* rec_risk, void* stream) {
+  if (!h || !best_tokens || !best_len || !best_score)
+    return fail(h, CASR_ERR_ARG, "casr_beam_mbr: NULL handle, best_tokens, best_len or best_score");
+  if (!(scale >= 0.0) || !std::isfinite(scale))
+    return fail(h, CASR_ERR_ARG, "casr_beam_mbr: scale %g is negative or not finite", scale);
+  if (!h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_mbr before casr_beam");
+  if (h->beam_lm_done)
+    return fail(h, CASR_ERR_STATE, "casr_beam_mbr after casr_beam_lm: the fallback assumes the scores of a casr_beam");
+  if (!mbr_supported(h->cfg.max_len, h->dec_k))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_mbr: max_len %d x k %d: distances are bytes (max_len <= %d) and the tree must fit 64 KB of LDS",
+                h->cfg.max_len, h->dec_k, EDIT_MBR_MAX_LEN);
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  if (rc) return rc;
+  MbrBufs w{};
+  HIP_OK(h, h->mbrws.ensure(carve_mbr(nullptr, c.a.B, c.a.max_len, c.a.k, w)));
+  carve_mbr(h->mbrws.p, c.a.B, c.a.max_len, c.a.k, w);
+  h->mbr_done = true;
+  HIP_OK(h, run_beam_mbr(c.a, h->d, w, h->tune[CASR_OPT_MBR_MAP], scale, rec_lm, lm_weight, length_weight,
+                         h->beam_lm_weight, h->beam_length_weight, best_tokens, best_len, best_score, best_index,
+                         best_risk, rec_risk, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_beam_mbr_distances(casr_handle* h, uint8_t* dist, int32_t* n_rec, void* stream) {
+  if (!h || !dist) return fail(h, CASR_ERR_ARG, "casr_beam_mbr_distances: NULL handle or output");
+  if (!h->beam_done || !h->mbr_done) return fail(h, CASR_ERR_STATE, "casr_beam_mbr_distances before casr_beam_mbr");
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  if (rc) return rc;
+  MbrBufs w{};
+  carve_mbr(h->mbrws.p, c.a.B, c.a.max_len, c.a.k, w);
+  HIP_OK(h, run_mbr_distances(c.a, w, dist, n_rec, (hipStream_t)stream));
+  return CASR_OK;
+}
+
 // the refusals casr_lm_terms and casr_beam_lm share with casr_lm_score
 static int lm_on_handle(casr_handle* h, const casr_lm* lm, const char* who) {
   if (lm->device != h->device)
@@ -1529,6 +1614,7 @@ int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, floa
   h->dec_k = k;
   h->beam_done = true;
   h->beam_lm_done = true;
+  h->mbr_done = false;
   h->beam_lm_weight = lm_weight;
   h->beam_length_weight = length_weight;
   // (never a hipGraph: launched eagerly whatever casr_set_graphs says)

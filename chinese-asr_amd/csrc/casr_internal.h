@@ -525,4 +525,24 @@ hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, 
                        const NgramSuccView& sv, float lm_weight, float length_weight, int32_t* best_tokens,
                        int32_t* best_len, float* best_score, float* best_lm, int32_t* steps, hipStream_t s);
 
+// edit.hip: edit distance on the device (edit_plan.h's rule, backtrace, total order and plan).
+// n pairs a [n][La] / b [n][Lb] with their lengths; ops null or [n][3]
+hipError_t launch_edit_pairs(const int32_t* a, const int32_t* a_len, int La, const int32_t* b, const int32_t* b_len,
+                             int Lb, int n, int32_t* dist, int32_t* ops, int32_t* err, hipStream_t s);
+// casr_beam_mbr's buffers (handle-owned, beside DecodeBufs); positions are those in an utterance's list
+struct MbrBufs {
+  double* w;       // [B][L k] exp(scale (c - c_max)) of the utterance's valid records, in list order
+  int32_t* list;   // [B][L k] their flat indices step k + rank, ascending
+  int32_t* count;  // [B]
+  uint8_t* dist;   // [B][L k][L k] d(p, q) at [p][q] for q < p only
+};
+size_t carve_mbr(void* base, int B, int L, int k, MbrBufs& w);
+bool mbr_supported(int max_len, int k);
+// the MBR choice over the beam state run_beam left in d; map: CASR_OPT_MBR_MAP
+hipError_t run_beam_mbr(const DecodeArgs& a, const DecodeBufs& d, const MbrBufs& w, int map, double scale,
+                        const float* rec_lm, double lm_weight, double length_weight, float beam_lm_weight,
+                        float beam_length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
+                        int32_t* best_index, double* best_risk, double* rec_risk, hipStream_t s);
+hipError_t run_mbr_distances(const DecodeArgs& a, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s);
+
 }  // namespace casr

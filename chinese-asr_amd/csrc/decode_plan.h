@@ -50,6 +50,7 @@ constexpr OptionRow OPTIONS[] = {
     {CASR_OPT_DEC_KSPLIT, "DEC_KSPLIT", 1, 0, 1},
     {CASR_OPT_GEMM16_LEAN, "GEMM16_LEAN", 0, 0, 1},
     {CASR_OPT_ATTN_SPLIT, "ATTN_SPLIT", 0, 0, AT_SPLIT_MAX},
+    {CASR_OPT_MBR_MAP, "MBR_MAP", 0, 0, 2},
 };
 constexpr bool options_in_enum_order() {
   for (int i = 0; i < CASR_OPT_COUNT; ++i)

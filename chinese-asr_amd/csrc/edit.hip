@@ -1,0 +1,460 @@
+// Edit distance on the device (include/casr.h casr_edit_distance, casr_beam_mbr): batches of
+// independent pairs with their operation counts (the WER of an evaluation), and every pair of an
+// utterance's finished beam records for the minimum-Bayes-risk choice.  The cell rule, the direction
+// bits, the backtrace, the total order and the plan are edit_plan.h's, the text the host compiles too.
+//
+// Every workgroup here is ONE wave (64 threads): its barriers order that wave's LDS traffic only.
+#include "casr_internal.h"
+#include "edit_plan.h"
+
+namespace casr {
+
+// ------------------------------------------------------------------ the wave form
+// D[m][n] of a[0 .. m) (LDS) against b[0 .. n), lane = column, one anti-diagonal per step.  At step t
+// lane c of a strip fills row i = t - c: up is its own previous value, left its left neighbour's value of
+// the step before (one cross-lane move), diag that neighbour's value of two steps before, which is the
+// left it fetched a step ago.  Lane 0 takes left from carry, the previous strip's last column, and the
+// strip's last lane overwrites carry behind it (it writes entry i + 1 - (cols - 1) <= what lane 0 reads).
+// OPS: a lane collects the direction codes of its column, 16 rows to a word (edit_plan.h layout).
+template <bool OPS>
+__device__ __forceinline__ int edit_wave_sweep(const int32_t* sa, int m, const int32_t* b, int n, int32_t* carry,
+                                               uint32_t* bits) {
+  const int ln = threadIdx.x;
+  if (m == 0) return n;  // (uniform)
+  if (n == 0) return m;
+  const int stride = edit_bits_stride(m);
+  for (int i = ln; i <= m; i += EDIT_WAVE) carry[i] = i;  // D[i][0]
+  __syncthreads();
+  int result = 0;
+  for (int j0 = 0; j0 < n; j0 += EDIT_WAVE) {
+    const int cols = min(EDIT_WAVE, n - j0), j = j0 + ln;
+    const bool on = ln < cols;
+    const int32_t bj = on ? b[j] : 0;
+    int v = j + 1;   // D[0][j + 1]
+    int diag = j;    // D[0][j]
+    uint32_t acc = 0;
+    const int T = m + cols - 1;
+    for (int t = 0; t < T; ++t) {
+      const int i = t - ln;
+      const bool act = on && i >= 0 && i < m;
+      int left = __shfl_up(v, 1);
+      if (act) {
+        if (ln == 0) left = carry[i + 1];
+        const bool match = sa[i] == bj;
+        const int d = edit_cell(match, diag, v, left);
+        if (OPS) {
+          acc |= (uint32_t)edit_dir(match, d, diag, v) << edit_bits_shift(i);
+          if ((i & 15) == 15 || i == m - 1) {
+            bits[edit_bits_word(i, j, stride)] = acc;
+            acc = 0;
+          }
+        }
+        v = d;
+        if (ln == cols - 1) carry[i + 1] = d;
+      }
+      diag = left;
+    }
+    if (j0 + EDIT_WAVE >= n) result = __shfl(v, n - 1 - j0);
+    __syncthreads();
+  }
+  return result;
+}
+
+struct EditPairsArgs {
+  const int32_t* a;
+  const int32_t* a_len;
+  const int32_t* b;
+  const int32_t* b_len;
+  int La, Lb;
+  int32_t* dist;
+  int32_t* ops;  // or null
+  int32_t* err;
+};
+
+// One workgroup per pair.  LDS: a [La], carry [La + 1], then the direction words (OPS)
+template <bool OPS>
+__global__ __launch_bounds__(EDIT_WAVE) void edit_pairs_kernel(EditPairsArgs p) {
+  extern __shared__ __attribute__((aligned(16))) int32_t esm[];
+  const size_t pair = blockIdx.x;
+  const int ln = threadIdx.x;
+  int m = p.a_len[pair], n = p.b_len[pair];
+  bool bad = false;
+  if (m < 0 || m > p.La) {
+    bad = true;
+    m = m < 0 ? 0 : p.La;
+  }
+  if (n < 0 || n > p.Lb) {
+    bad = true;
+    n = n < 0 ? 0 : p.Lb;
+  }
+  int32_t* sa = esm;
+  int32_t* carry = sa + p.La;
+  uint32_t* bits = reinterpret_cast<uint32_t*>(carry + p.La + 1);
+  const int32_t* a = p.a + pair * p.La;
+  for (int i = ln; i < m; i += EDIT_WAVE) sa[i] = a[i];
+  __syncthreads();
+  const int d = edit_wave_sweep<OPS>(sa, m, p.b + pair * p.Lb, n, carry, bits);
+  if (OPS) __syncthreads();
+  if (ln == 0) {
+    p.dist[pair] = d;
+    if (OPS) edit_backtrace(bits, m, n, p.ops + pair * 3);
+    if (bad) atomicOr(p.err, CASR_DEV_BAD_TOKEN);
+  }
+}
+
+hipError_t launch_edit_pairs(const int32_t* a, const int32_t* a_len, int La, const int32_t* b, const int32_t* b_len,
+                             int Lb, int n, int32_t* dist, int32_t* ops, int32_t* err, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const EditPlan pl = edit_plan_pairs(La, Lb, n, ops != nullptr);
+  if (pl.form != EDIT_FORM_WAVE) return hipErrorInvalidValue;
+  const EditPairsArgs p{a, a_len, b, b_len, La, Lb, dist, ops, err};
+  if (ops) {
+    if (pl.raise_lds) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(edit_pairs_kernel<true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(edit_pairs_kernel<true>, dim3(pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, p);
+  } else {
+    hipLaunchKernelGGL(edit_pairs_kernel<false>, dim3(pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, p);
+  }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ all pairs of a beam's records
+constexpr int MBR_THREADS = 256;
+
+// executed loop steps: the step at which the cumulative count of newdone reached `total`, + 1 (else L)
+__device__ __forceinline__ int mbr_executed_steps(const int32_t* newdone, int L, int total) {
+  int cum = 0;
+  for (int s = 0; s < L; ++s) {
+    cum += newdone[s];
+    if (cum >= total) return s + 1;
+  }
+  return L;
+}
+
+struct MbrArgs {
+  int B, k, L;
+  double scale, lm_weight, length_weight;
+  float beam_lm_weight, beam_length_weight;  // casr_beam's (the unfinished fallback)
+  const float* score0;
+  const float* score1;
+  const int32_t* bp;
+  const int32_t* tk;
+  const float* rec_score;
+  const int32_t* rec_src;
+  const uint8_t* rec_valid;
+  const int32_t* newdone;
+  const float* rec_lm;  // or null
+  MbrBufs w;
+  int V;
+  int32_t* best_tokens;
+  int32_t* best_len;
+  float* best_score;
+  int32_t* best_index;  // or null
+  double* best_risk;    // or null
+  double* rec_risk;     // or null
+  int32_t* err;
+};
+
+// One workgroup per utterance: the valid records' flat indices in (step, rank) order (list, count) and
+// their weights w = exp(scale (c - c_max)).  LDS: reduction [MBR_THREADS] doubles, wave counts
+__global__ __launch_bounds__(MBR_THREADS) void mbr_prepare_kernel(MbrArgs a) {
+  __shared__ double red[MBR_THREADS];
+  __shared__ int wcount[MBR_THREADS / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, k = a.k, LK = a.L * k;
+  const int steps = mbr_executed_steps(a.newdone, a.L, a.B);
+  const int nn = steps * k;
+  int32_t* list = a.w.list + (size_t)b * LK;
+  double* w = a.w.w + (size_t)b * LK;
+  int base = 0;
+  for (int i0 = 0; i0 < LK; i0 += MBR_THREADS) {
+    const int i = i0 + tid;
+    const bool v = i < nn && a.rec_valid[(size_t)b * LK + i];
+    const unsigned long long bal = __ballot(v);
+    const int lane = tid & 63, wv = tid >> 6;
+    if (lane == 0) wcount[wv] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int u = 0; u < MBR_THREADS / 64; ++u) {
+      if (u < wv) off += wcount[u];
+      tot += wcount[u];
+    }
+    if (v) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+    base += tot;
+    __syncthreads();
+  }
+  const int n = base;
+  if (tid == 0) a.w.count[b] = n;
+  // c of every record (kept in w), c_max over the workgroup
+  double cm = NAN;
+  for (int p = tid; p < n; p += MBR_THREADS) {
+    const int i = list[p];
+    const size_t ri = (size_t)b * LK + i;
+    const double c = mbr_comb(a.rec_score[ri], a.rec_lm ? a.rec_lm[ri] : 0.f, i / k, a.lm_weight, a.length_weight);
+    w[p] = c;
+    cm = mbr_cmax(cm, c);
+  }
+  red[tid] = cm;
+  __syncthreads();
+  for (int o = MBR_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) red[tid] = mbr_cmax(red[tid], red[tid + o]);
+    __syncthreads();
+  }
+  const double cmax = red[0];
+  for (int p = tid; p < n; p += MBR_THREADS) w[p] = mbr_weight(a.scale, w[p], cmax);
+}
+
+// stage the beam tree of utterance b (beam_finalize's layout: [step][slot]); a back-pointer outside
+// [0, k) is clamped, a token outside [0, V) is an ordinary symbol here; both are reported
+__device__ __forceinline__ void mbr_stage_tree(const MbrArgs& a, int b, int nn, int32_t* sbp, int32_t* stk) {
+  const int k = a.k, R = a.B * k;
+  bool bad_tok = false, bad_bp = false;
+  for (int i = threadIdx.x; i < nn; i += blockDim.x) {
+    const int st = i / k, c = i - st * k;
+    const size_t ix = (size_t)st * R + b * k + c;
+    int p = a.bp[ix];
+    if ((unsigned)p >= (unsigned)k) {
+      if (st > 0) bad_bp = true;  // (step 0 has no predecessor node: its pointer is never followed)
+      p = 0;
+    }
+    const int t = a.tk[ix];
+    if ((unsigned)t >= (unsigned)a.V) bad_tok = true;
+    sbp[i] = p;
+    stk[i] = t;
+  }
+  if (blockIdx.y == 0) {
+    if (bad_tok) atomicOr(a.err, CASR_DEV_BAD_TOKEN);
+    if (bad_bp) atomicOr(a.err, CASR_DEV_BAD_BACKPTR);
+  }
+}
+
+// the slot a record's walk starts from (step l - 1), clamped
+__device__ __forceinline__ int mbr_record_slot(const MbrArgs& a, size_t ri, int l, int k) {
+  int slot = a.rec_src[ri];
+  if ((unsigned)slot >= (unsigned)k) {
+    if (l > 0) atomicOr(a.err, CASR_DEV_BAD_BACKPTR);
+    slot = 0;
+  }
+  return slot;
+}
+
+// Distances d(p, q), q < p, as bytes at dist[b][p][q] (p, q positions in the utterance's list).  Grid
+// (B, rows): workgroup y takes the records p = 1 + y, 1 + y + rows, ..  One wave per workgroup.
+//   FORM lane: record p's tokens, LAST FIRST, are uniform across the wave (every lane walks the tree
+//        and writes the same words: no hand-off between lanes); lane q rolls a row of D, as bytes
+//        [column][lane] in LDS, down its own record, read last token first off the back-pointers, one
+//        hop per row (the distance of two reversed rows is that of the rows).
+//   FORM wave: both records expanded in LDS, then the anti-diagonal sweep of the pairs kernel.
+template <int FORM>
+__global__ __launch_bounds__(EDIT_WAVE) void mbr_dist_kernel(MbrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t esm[];
+  const int b = blockIdx.x, ln = threadIdx.x, k = a.k, L = a.L, LK = L * k;
+  const int n = a.w.count[b];
+  if (n < 2) return;  // (uniform)
+  const int steps = mbr_executed_steps(a.newdone, L, a.B);
+  int32_t* sbp = esm;
+  int32_t* stk = sbp + LK;
+  int32_t* ua = stk + LK;  // record p's tokens [L]
+  mbr_stage_tree(a, b, steps * k, sbp, stk);
+  __syncthreads();
+  const int32_t* list = a.w.list + (size_t)b * LK;
+  uint8_t* dist = a.w.dist + (size_t)b * LK * LK;
+  for (int p = 1 + blockIdx.y; p < n; p += gridDim.y) {
+    const int fp = list[p], lp = fp / k;
+    int slot = mbr_record_slot(a, (size_t)b * LK + fp, lp, k);
+    if (FORM == EDIT_FORM_LANE) {
+      uint8_t* row = reinterpret_cast<uint8_t*>(ua + L);  // [L + 1][64]
+      for (int st = lp - 1; st >= 0; --st) {
+        ua[lp - 1 - st] = stk[st * k + slot];
+        slot = sbp[st * k + slot];
+      }
+      for (int q = ln; q < p; q += EDIT_WAVE) {
+        const int fq = list[q], lq = fq / k;
+        int sq = mbr_record_slot(a, (size_t)b * LK + fq, lq, k);
+        for (int c = 0; c <= lp; ++c) row[c * EDIT_WAVE + ln] = (uint8_t)c;
+        for (int r = 1; r <= lq; ++r) {
+          const int st = lq - r;
+          const int32_t tok = stk[st * k + sq];
+          sq = sbp[st * k + sq];
+          int diag = row[ln], left = r;
+          row[ln] = (uint8_t)r;
+          for (int c = 1; c <= lp; ++c) {
+            const int up = row[c * EDIT_WAVE + ln];
+            const int d = edit_cell(tok == ua[c - 1], diag, up, left);
+            row[c * EDIT_WAVE + ln] = (uint8_t)d;
+            diag = up;
+            left = d;
+          }
+        }
+        dist[(size_t)p * LK + q] = row[lp * EDIT_WAVE + ln];
+      }
+    } else {
+      int32_t* ub = ua + L;
+      int32_t* carry = ub + L;  // [L + 1]
+      for (int st = lp - 1; st >= 0; --st) {
+        ua[st] = stk[st * k + slot];
+        slot = sbp[st * k + slot];
+      }
+      for (int q = 0; q < p; ++q) {
+        const int fq = list[q], lq = fq / k;
+        int sq = mbr_record_slot(a, (size_t)b * LK + fq, lq, k);
+        for (int st = lq - 1; st >= 0; --st) {
+          ub[st] = stk[st * k + sq];
+          sq = sbp[st * k + sq];
+        }
+        __syncthreads();
+        const int d = edit_wave_sweep<false>(ua, lp, ub, lq, carry, nullptr);
+        if (ln == 0) dist[(size_t)p * LK + q] = (uint8_t)d;
+        __syncthreads();
+      }
+    }
+  }
+}
+
+// One workgroup per utterance: risk_p = sum_q w_q d(p, q) in ascending q, the winner by mbr_better, its
+// tokens off the tree; without a record casr_beam's unfinished fallback, as the rescore keeps it.
+__global__ __launch_bounds__(MBR_THREADS) void mbr_reduce_kernel(MbrArgs a) {
+  __shared__ double redr[MBR_THREADS];
+  __shared__ int32_t redi[MBR_THREADS];
+  const int b = blockIdx.x, tid = threadIdx.x, k = a.k, L = a.L, LK = L * k, R = a.B * k;
+  const int n = a.w.count[b];
+  const int32_t* list = a.w.list + (size_t)b * LK;
+  const double* w = a.w.w + (size_t)b * LK;
+  const uint8_t* dist = a.w.dist + (size_t)b * LK * LK;
+  if (a.rec_risk) {
+    for (int i = tid; i < LK; i += MBR_THREADS) a.rec_risk[(size_t)b * LK + i] = 0.0;
+    __syncthreads();
+  }
+  double br = 0.0;
+  int bi = -1;
+  for (int p = tid; p < n; p += MBR_THREADS) {
+    double r = 0.0;
+    for (int q = 0; q < n; ++q) {
+      const int d = q == p ? 0 : (q < p ? dist[(size_t)p * LK + q] : dist[(size_t)q * LK + p]);
+      r = mbr_risk_add(r, w[q], d);
+    }
+    if (a.rec_risk) a.rec_risk[(size_t)b * LK + list[p]] = r;
+    if (mbr_better(r, p, br, bi)) {
+      br = r;
+      bi = p;
+    }
+  }
+  redr[tid] = br;
+  redi[tid] = bi;
+  __syncthreads();
+  for (int o = MBR_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o && mbr_better(redr[tid + o], redi[tid + o], redr[tid], redi[tid])) {
+      redr[tid] = redr[tid + o];
+      redi[tid] = redi[tid + o];
+    }
+    __syncthreads();
+  }
+  const int win = redi[0];
+  __syncthreads();  // (redi[0] is rewritten below as the length)
+  int32_t* out = a.best_tokens + (size_t)b * L;
+  if (win >= 0 ? (bi == win) : (tid == 0)) {
+    int len, slot, from;
+    float bs;
+    if (win >= 0) {
+      const int fi = list[win];
+      const size_t ri = (size_t)b * LK + fi;
+      len = fi / k;
+      slot = a.rec_src[ri];
+      from = len - 1;
+      bs = a.rec_score[ri];
+      if (a.best_index) a.best_index[b] = fi;
+      if (a.best_risk) a.best_risk[b] = br;
+    } else {  // no record: casr_beam's unfinished fallback (model.py:961-972), its weights, its bits
+      const int steps = mbr_executed_steps(a.newdone, L, a.B);
+      const float* score_final = (steps & 1) ? a.score1 : a.score0;
+      const int ll = steps - 1;
+      const float lw = (float)((double)a.beam_length_weight * (double)(ll + 1));
+      int bj = 0;
+      float bsv = 0.f;
+      for (int j = 0; j < k; ++j) {
+        const float sv = (score_final[b * k + j] + a.beam_lm_weight * 0.f) + lw;
+        if (j == 0 || sv > bsv) {
+          bsv = sv;
+          bj = j;
+        }
+      }
+      bs = bsv;
+      len = ll + 1;
+      slot = bj;
+      from = ll;
+      if (a.best_index) a.best_index[b] = -1;
+      if (a.best_risk) a.best_risk[b] = 0.0;
+    }
+    bool bad_bp = false;
+    for (int st = from; st >= 0; --st) {
+      if ((unsigned)slot >= (unsigned)k) {
+        bad_bp = true;
+        slot = 0;
+      }
+      const size_t ix = (size_t)st * R + b * k + slot;
+      out[st] = a.tk[ix];
+      slot = a.bp[ix];
+    }
+    a.best_len[b] = len;
+    a.best_score[b] = bs;
+    redi[0] = len;
+    if (bad_bp) atomicOr(a.err, CASR_DEV_BAD_BACKPTR);
+  }
+  __syncthreads();
+  const int len = redi[0];
+  for (int st = len + tid; st < L; st += MBR_THREADS) out[st] = -1;
+}
+
+// the byte matrix as a full symmetric one: out [B][L k][L k], 0 on the diagonal and past the count
+__global__ __launch_bounds__(MBR_THREADS) void mbr_expand_kernel(MbrBufs w, int LK, uint8_t* out, int32_t* n_rec) {
+  const int b = blockIdx.x, n = w.count[b];
+  const uint8_t* dist = w.dist + (size_t)b * LK * LK;
+  uint8_t* o = out + (size_t)b * LK * LK;
+  for (int i = threadIdx.x; i < LK * LK; i += MBR_THREADS) {
+    const int p = i / LK, q = i - p * LK;
+    o[i] = (p < n && q < n && p != q) ? (q < p ? dist[(size_t)p * LK + q] : dist[(size_t)q * LK + p]) : 0;
+  }
+  if (threadIdx.x == 0 && n_rec) n_rec[b] = n;
+}
+
+bool mbr_supported(int max_len, int k) {
+  return edit_plan_mbr(max_len, k, EDIT_FORM_WAVE).form != EDIT_FORM_NONE &&
+         edit_plan_mbr(max_len, k, EDIT_FORM_LANE).form != EDIT_FORM_NONE;
+}
+
+size_t carve_mbr(void* base, int B, int L, int k, MbrBufs& w) {
+  Carver c(base);
+  const size_t LK = (size_t)L * k;
+  w.w = c.take<double>((size_t)B * LK);
+  w.list = c.take<int32_t>((size_t)B * LK);
+  w.count = c.take<int32_t>(B);
+  w.dist = c.take<uint8_t>((size_t)B * LK * LK);
+  return c.bytes(256);
+}
+
+hipError_t run_beam_mbr(const DecodeArgs& a, const DecodeBufs& d, const MbrBufs& w, int map, double scale,
+                        const float* rec_lm, double lm_weight, double length_weight, float beam_lm_weight,
+                        float beam_length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
+                        int32_t* best_index, double* best_risk, double* rec_risk, hipStream_t s) {
+  const EditPlan pl = edit_plan_mbr(a.max_len, a.k, map);
+  if (pl.form == EDIT_FORM_NONE) return hipErrorInvalidValue;
+  const MbrArgs m{a.B, a.k, a.max_len, scale, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
+                  d.score[0], d.score[1], d.bp, d.tk, d.rec_score, d.rec_src, d.rec_valid, d.newdone, rec_lm, w, a.V,
+                  best_tokens, best_len, best_score, best_index, best_risk, rec_risk, d.err};
+  hipLaunchKernelGGL(mbr_prepare_kernel, dim3(a.B), dim3(MBR_THREADS), 0, s, m);
+  if (pl.form == EDIT_FORM_LANE)
+    hipLaunchKernelGGL(mbr_dist_kernel<EDIT_FORM_LANE>, dim3(a.B, pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, m);
+  else
+    hipLaunchKernelGGL(mbr_dist_kernel<EDIT_FORM_WAVE>, dim3(a.B, pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, m);
+  hipLaunchKernelGGL(mbr_reduce_kernel, dim3(a.B), dim3(MBR_THREADS), 0, s, m);
+  return hipGetLastError();
+}
+
+hipError_t run_mbr_distances(const DecodeArgs& a, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s) {
+  hipLaunchKernelGGL(mbr_expand_kernel, dim3(a.B), dim3(MBR_THREADS), 0, s, w, a.max_len * a.k, dist, n_rec);
+  return hipGetLastError();
+}
+
+}  // namespace casr

@@ -15,7 +15,7 @@ from casr.engine import Engine
 from casr.lib import pack_weights
 from casr.ngram import NgramLM
 from casr.results import (EvalOutput, ScoreOutput, encode_targets, get_wer, greedy_outputs, greedy_steps,
-                          label_smoothed_loss, score_outputs, second_pass_arrays, token_times)
+                          label_smoothed_loss, score_outputs, second_pass_arrays, token_times, wer_batch)
 from casr.vocab import load_vocab
 from casr.weights import check_state_dicts, load_checkpoint, save_checkpoint, synthetic_state_dicts
 
@@ -123,20 +123,32 @@ class Model(object):
         wer = None
         if text is not None:
             text = [''.join([i2w[e] for e in ele]) for ele in text]
-            wer = np.mean([get_wer(p, r) for p, r in zip(pred_text, text)])
+            wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
         return EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=alignments,
                           audio_feat_len=lens, text_len=out['out_len'])
 
     @torch.no_grad()
     def eval_one_batch_with_beam(self, device, bmsz, data, lens, text, int2word,
                                  second_pass=gpd['second_pass'], lm_model=None,
-                                 lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight'], fusion=False):
+                                 lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight'], fusion=False,
+                                 mbr=None):
         """model.py:604-987.  ``fusion`` (this path's own addition, default off): with an NgramLM as
         ``lm_model`` the LM is fused into the first pass on the device (casr_beam_lm: every candidate
         ranked by logp + lm_weight lm + length_weight (l + 1), the ranking model.py:843-857 was designed
         for) and no second pass runs; ``score`` is the choice's acoustic log-probability.  A duck-typed
-        host scorer cannot be fused: TypeError."""
+        host scorer cannot be fused: TypeError.
+        ``mbr`` (this path's own addition, default None: off): a scale >= 0.  The result is the finished
+        hypothesis with the lowest expected edit distance to the others under the posterior
+        exp(mbr (c - c_max)) (casr_beam_mbr), c the second pass's combined score: with an NgramLM and
+        ``second_pass`` the LM enters c, without either c = logp + length_weight len.  ``score`` is the
+        choice's first-pass score.  Any other ``lm_model`` cannot be read on the device: TypeError;
+        together with ``fusion``: ValueError."""
         self.model.eval()
+        if mbr is not None:
+            if fusion:
+                raise ValueError("mbr and fusion exclude each other: the MBR choice reads the records of a plain beam")
+            if lm_model is not None and not isinstance(lm_model, NgramLM):
+                raise TypeError(f"mbr needs a casr.ngram.NgramLM as lm_model (or None), got {type(lm_model).__name__}")
         if fusion:
             if not isinstance(lm_model, NgramLM):
                 raise TypeError(f"fusion=True needs a casr.ngram.NgramLM as lm_model, got {type(lm_model).__name__}")
@@ -147,7 +159,7 @@ class Model(object):
             wer = None
             if text is not None:
                 text = [''.join([i2w[idx] for idx in ele]) for ele in text]
-                wer = np.mean([get_wer(p, t) for p, t in zip(pred_text, text)])
+                wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
             return EvalOutput(pred_text=pred_text, score=[float(s) for s in bscore], text=text, wer=wer, n=bsz,
                               alignment=None, audio_feat_len=None, text_len=None)
         # an NgramLM (casr/ngram.py) is rescored on the device from the beam tree: no record copy and
@@ -156,10 +168,12 @@ class Model(object):
 
         def decode():
             r = self.engine.beam(bmsz, lm_weight, length_weight)
+            if mbr is not None:
+                return self.engine.beam_mbr(mbr, lm_model if on_device else None, lm_weight, length_weight)
             return self.engine.beam_rescore(lm_model, lm_weight, length_weight) if on_device else r
 
         bsz, _, r = self._run(data, lens, decode)
-        second_pass = second_pass and not on_device
+        second_pass = second_pass and not on_device and mbr is None
         toks = r['tokens'].cpu().numpy()
         blen = r['length'].cpu().numpy()
         bscore = r['score'].cpu().numpy()
@@ -177,7 +191,7 @@ class Model(object):
             text = [''.join([i2w[idx] for idx in ele]) for ele in text]
         wer = None
         if text is not None:
-            wer = np.mean([get_wer(p, t) for p, t in zip(pred_text, text)])
+            wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
         return EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=None,
                           audio_feat_len=None, text_len=None)
 

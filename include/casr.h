@@ -498,6 +498,83 @@ int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, floa
                  void* stream);
 int casr_beam_record_lm(casr_handle* h, float* rec_lm, void* stream);
 
+/* Edit distance, its operation counts, and a minimum-Bayes-risk (MBR) choice among the finished
+ * hypotheses of a beam.  The reference computes a WER per utterance with python-Levenshtein
+ * (util.py:237-262) and has no MBR; like the n-gram LM, the operation is DEFINED BY THE FORMULAS BELOW.
+ * casr/results.py's edit_distance and edit_ops are the same formulas in Python (the tests' reference).
+ *   Distance  symbols are int32, equal when all 32 bits are equal (negative values are ordinary
+ *             symbols).  For a[0..m) and b[0..n): D[i][0] = i, D[0][j] = j, D[i][j] = D[i-1][j-1] where
+ *             a[i-1] == b[j-1], else 1 + min(D[i-1][j-1], D[i-1][j], D[i][j-1]); dist = D[m][n].
+ *   Ops       (insert, delete, replace) of the script turning a into b, by the backtrace from (m, n): at
+ *             (i, j) the first rule that applies: i, j > 0 and a match: diagonal; i, j > 0 and D[i][j] ==
+ *             D[i-1][j-1] + 1: replace; i > 0 and D[i][j] == D[i-1][j] + 1: delete; else insert.  The sum
+ *             is dist.  How it splits is this tie order's; parity with python-Levenshtein's split is not
+ *             pinned.  The rule a cell takes is known when it is filled: two bits per cell are kept, no D.
+ *   MBR       per utterance over its valid records r_0 .. r_{n-1} in (step, rank) order; l_i the token
+ *             count (eos not among the tokens), s_i rec_score, q_i the LM sentence score (0 without
+ *             rec_lm):
+ *               c_i    = (double(s_i) + lm_weight double(q_i)) + length_weight double(l_i)   the comb of
+ *                        casr_beam_rescore, the same uncontracted double operations
+ *               c_max  = the largest c_i that is no NaN (NaN when there is none)
+ *               w_i    = exp(scale (c_i - c_max))   double; difference and product rounded on their own
+ *               risk_i = sum_j w_j double(dist(r_i, r_j))   ascending j from 0, each product rounded
+ *                        before its add
+ *             The choice is the first record under the total order: a risk that is no NaN beats a NaN,
+ *             then the smaller risk, then the lower index.  scale = 0 gives the medoid; a large scale
+ *             gives the maximum of c wherever it is unique.  exp is the platform's (host libm, device
+ *             ocml): a risk may differ in its last bits between host and device, nothing else does.
+ * The two *_host entries take HOST pointers and need no GPU; the others DEVICE pointers.  All return
+ * after enqueueing; nothing is launched or written on an error; none is replayed as a hipGraph or
+ * counted among the timed kernel classes.
+ *   a [n][La], a_len [n], b [n][Lb], b_len [n] int32; dist [n] int32; ops NULL or [n][3] int32.
+ * casr_edit_distance_host: any La, Lb >= 0 and n >= 0.  CASR_ERR_ARG: a NULL required argument (a or b
+ * may be NULL at La or Lb = 0), or a length outside [0, L].
+ * casr_edit_distance: 1 <= La, Lb <= CASR_EDIT_MAX_LEN, else CASR_ERR_UNSUPPORTED; a length outside
+ * [0, L] is clamped and raises guard bit 1.  Needs no weights and no encode.  One wave per pair
+ * (csrc/edit.hip): lane = column, sweeping the anti-diagonals of a strip of 64 columns with one
+ * cross-lane move each; a strip's last column reaches the next through LDS; with ops the direction bits
+ * (up to 64 KB) stay in LDS and one lane walks them back. */
+#define CASR_EDIT_MAX_LEN 512
+int casr_edit_distance_host(const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
+                            const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops);
+int casr_edit_distance(casr_handle* h, const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
+                       const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops, void* stream);
+
+/* MBR on the host, on the expanded arrays casr_beam_records writes (rec_lm NULL or [B][max_len][k]):
+ *   best_index [B]  the flat index step k + rank of the choice, -1 without a record
+ *   rec_risk   NULL or [B][max_len][k] double, 0 where there is no valid record
+ * CASR_ERR_ARG: a NULL required argument, B < 0, max_len or k < 1, or a scale that is negative or not
+ * finite. */
+int casr_mbr_host(const int32_t* rec_tokens, const float* rec_score, const uint8_t* rec_valid,
+                  const float* rec_lm, int B, int max_len, int k, double scale, double lm_weight,
+                  double length_weight, int32_t* best_index, double* rec_risk);
+
+/* MBR over the finished hypotheses of the last casr_beam, on the device, from the beam tree the handle
+ * still holds (no record is expanded).  rec_lm is NULL or the device array casr_beam_rescore wrote.
+ *   best_tokens [B][max_len] (-1 past the length), best_len [B], best_score [B] = the choice's rec_score
+ *   best_index  NULL or [B] as above; best_risk NULL or [B] double (0 without a record); rec_risk NULL
+ *   or [B][max_len][k] double
+ * An utterance with no record keeps the unfinished fallback of casr_beam, bit for bit, as the rescore
+ * does.  Three launches: the records' list and weights (one workgroup per utterance); every distance of
+ * j < i once, as a byte, into a handle-owned workspace of B (max_len k)^2 bytes that grows on demand
+ * (128 workgroups of one wave per utterance; CASR_OPT_MBR_MAP picks the mapping); then per record the
+ * ascending sum and per utterance the winner by the total order above.  No float atomics: the result
+ * does not depend on scheduling or on the reduction tree.  The handle's beam state is only read: a later
+ * casr_beam_records, rescore or second MBR call gives the same bits.  A back-pointer outside [0, k) is
+ * clamped (guard bit 16); a token id outside [0, V) is an ordinary symbol and raises guard bit 1.
+ * CASR_ERR_STATE before casr_beam, and after casr_beam_lm until the next casr_beam (the limit of
+ * casr_beam_rescore: the fallback assumes the scores of casr_beam); CASR_ERR_ARG: a NULL handle,
+ * best_tokens, best_len or best_score, or a scale that is negative or not finite;
+ * CASR_ERR_UNSUPPORTED: max_len > 255 (distances are bytes) or a tree past 64 KB of LDS.
+ * casr_beam_mbr_distances copies the distances of the last casr_beam_mbr as a full symmetric matrix:
+ * dist [B][max_len k][max_len k] bytes over the positions in (step, rank) order of an utterance's valid
+ * records (0 on the diagonal and past the count), n_rec NULL or [B] the counts.  CASR_ERR_STATE unless
+ * the last beam call was followed by a casr_beam_mbr. */
+int casr_beam_mbr(casr_handle* h, double scale, const float* rec_lm, double lm_weight, double length_weight,
+                  int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* best_index,
+                  double* best_risk, double* rec_risk, void* stream);
+int casr_beam_mbr_distances(casr_handle* h, uint8_t* dist, int32_t* n_rec, void* stream);
+
 /* Guard bits raised by the device since the previous casr_device_flags call (read and clear;
  * they accumulate over every encode / decode / log-mel call in between, so one read after a
  * series of calls vouches for all of them; 0 = clean): a data-dependent index out of range (1 token, 2 predecessor row, 4 NaN logit
@@ -616,6 +693,11 @@ int casr_recurrence_mode(const casr_handle* h, int B);
  *                            images) advances its DMA sources by a stride per stage and waits on
  *                            constant vmcnt counts in its steady state (round 6); 0: 64-bit stage
  *                            addresses and the runtime wait ladder.  The same MFMAs in the same order
+ *   CASR_OPT_MBR_MAP         how casr_beam_mbr maps an utterance's pairs of records to lanes: 1 one wave
+ *                            per pair (the anti-diagonal sweep casr_edit_distance runs); 2 one lane per
+ *                            pair (a record's tokens uniform across the wave, each lane rolling a row
+ *                            of D against a record of its own); 0 (default) the plan's choice
+ *                            (csrc/edit_plan.h).  The same distances
  * Three options select numerics variants instead (the same token ids, floating-point results within
  * the stated tolerances, not bit for bit; tests/test_gpu_parity.py compares each pair):
  *   CASR_OPT_DEC_KSPLIT      1: the greedy folded GEMM at R <= 32 decode rows (BASELINE config 2)
@@ -694,7 +776,8 @@ enum {
   CASR_OPT_DEC_KSPLIT = 16,
   CASR_OPT_GEMM16_LEAN = 17,
   CASR_OPT_ATTN_SPLIT = 18,
-  CASR_OPT_COUNT = 19
+  CASR_OPT_MBR_MAP = 19,
+  CASR_OPT_COUNT = 20
 };
 int casr_set_option(casr_handle* h, int option, int value);
 int casr_get_option(const casr_handle* h, int option, int32_t* value_host);
