@@ -182,7 +182,7 @@ class BeamShardDecoder:
     position)."""
 
     def __init__(self, engine, k, lm_model=None, int2word=None, lm_weight=0.0, length_weight=0.0,
-                 keep_records=False, max_batch=256, rescorer=None, fusion=False):
+                 keep_records=False, max_batch=256, rescorer=None, fusion=False, bias=None, bias_weight=1.0):
         # engine: an Engine, or a casr.pipeline.StreamPipeline (or its limited() view), whose
         # handles then take the shard's batches in turn, several in flight
         self.engine, self.k = engine, int(k)
@@ -202,13 +202,21 @@ class BeamShardDecoder:
         if fusion and not self.device_lm:
             raise TypeError("fusion=True needs a casr.ngram.NgramLM as lm_model, no rescorer and no keep_records")
         self.fusion = bool(fusion)
+        # bias: a casr.bias.PhraseBias in the first pass (casr_beam_bias); an LM takes part only fused
+        # (Model.eval_one_batch_with_beam's rule: a second pass rescores a plain beam)
+        if bias is not None and lm_model is not None and not self.fusion:
+            raise ValueError("bias with a second pass: fuse the LM (fusion=True) or drop it")
+        self.bias, self.bias_weight = bias, float(bias_weight)
         self._slots = {}
         self._next = 0
         self.stats = {}
 
     def _batch(self, e, fbank, frames, key):
         e.encode_fbank(fbank, frames)
-        if self.fusion:
+        if self.bias is not None:
+            r = e.beam_bias(self.bias, self.k, self.bias_weight, self.lm_model if self.fusion else None, self.lm_weight,
+                            self.length_weight)
+        elif self.fusion:
             r = e.beam_lm(self.lm_model, self.k, self.lm_weight, self.length_weight)
         else:
             r = e.beam(self.k, self.lm_weight, self.length_weight)

@@ -357,6 +357,63 @@ class Engine:
         _lib.check(self.lib.casr_beam_record_lm(self.handle, _ptr(rec_lm), _stream()), self.handle)
         return rec_lm
 
+    def bias_score(self, bias, tokens, lens):
+        """(full, tail, state) int32 [n] of the rows tokens [n, L] (1 <= L <= 512) with lens [n] under a
+        casr.bias.PhraseBias, on the device (casr_bias_score): PhraseBias.score_ids' values."""
+        dev = self.device
+        tokens = torch.as_tensor(tokens).to(dev, torch.int32).contiguous()
+        lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
+        if tokens.dim() != 2 or lens.shape != (tokens.shape[0],):
+            raise ValueError("bias_score: tokens must be [n, L] and lens [n]")
+        n, L = tokens.shape
+        full, tail, state = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+        _lib.check(self.lib.casr_bias_score(self.handle, bias.on(self), _ptr(tokens), _ptr(lens), n, L, _ptr(full),
+                                            _ptr(tail), _ptr(state), _stream()), self.handle)
+        self._keep_bias = (bias, tokens, lens)  # read by the enqueued kernel
+        return full, tail, state
+
+    def bias_rows(self, bias, state, next=False):
+        """gain int32 [n, V] of automaton states [n] on the device (casr_bias_rows), and with ``next``
+        the successor states [n, V]: PhraseBias.rows' values."""
+        dev = self.device
+        state = torch.as_tensor(state).to(dev, torch.int32).contiguous().reshape(-1)
+        n = state.shape[0]
+        gain = torch.empty(n, self.cfg.vocab, dtype=torch.int32, device=dev)
+        nx = torch.empty(n, self.cfg.vocab, dtype=torch.int32, device=dev) if next else None
+        _lib.check(self.lib.casr_bias_rows(self.handle, bias.on(self), _ptr(state), n, _ptr(gain), _ptr(nx),
+                                           _stream()), self.handle)
+        self._keep_bias = (bias, state)  # read by the enqueued kernel
+        return (gain, nx) if next else gain
+
+    def beam_bias(self, bias, k, bias_weight=1.0, lm=None, lm_weight=0.0, length_weight=0.0):
+        """Beam search with the phrase bias (a casr.bias.PhraseBias) and, with ``lm`` (a
+        casr.ngram.NgramLM), the n-gram LM in the first pass (casr_beam_bias).  Returns tokens [B,
+        max_len] (-1 past the length), length [B], score [B] (the choice's acoustic log-probability),
+        lm [B] (its LM score; None without an LM), bias [B] (its bias in nats) and steps [1]."""
+        B, L = self._B, self.cfg.max_len
+        dev = self.device
+        toks = torch.empty(B, L, dtype=torch.int32, device=dev)
+        blen = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        best_lm = torch.empty(B, dtype=torch.float32, device=dev) if lm is not None else None
+        best_bias = torch.empty(B, dtype=torch.float32, device=dev)
+        steps = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.casr_beam_bias(self.handle, bias.on(self), lm.on(self) if lm is not None else None, int(k),
+                                           ctypes.c_float(bias_weight), ctypes.c_float(lm_weight),
+                                           ctypes.c_float(length_weight), _ptr(toks), _ptr(blen), _ptr(score),
+                                           _ptr(best_lm), _ptr(best_bias), _ptr(steps), _stream()), self.handle)
+        self._k = k
+        self._keep_lm = (lm, bias)
+        return dict(tokens=toks, length=blen, score=score, lm=best_lm, bias=best_bias, steps=steps)
+
+    def beam_record_bias(self):
+        """rec_bias [B, max_len, k]: bias_closed (nats) of every valid record of the last beam_bias() (0
+        elsewhere), beside beam_records()' tokens and acoustic scores."""
+        B, L, k = self._B, self.cfg.max_len, self._k
+        rec_bias = torch.empty(B, L, k, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.casr_beam_record_bias(self.handle, _ptr(rec_bias), _stream()), self.handle)
+        return rec_bias
+
     def edit_distance(self, a, a_len, b, b_len, ops=False):
         """Edit distances of n pairs on the device (casr_edit_distance): a [n, La], b [n, Lb] int32
         symbols (1 <= La, Lb <= casr.lib.EDIT_MAX_LEN), a_len and b_len [n] -> dist [n] int32, and with

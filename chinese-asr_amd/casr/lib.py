@@ -29,6 +29,8 @@ EXPORTS = [
     "casr_segment_default_params", "casr_segment_bound", "casr_segment_host", "casr_segment",
     "casr_gather_segments",
     "casr_edit_distance_host", "casr_edit_distance", "casr_mbr_host", "casr_beam_mbr", "casr_beam_mbr_distances",
+    "casr_bias_create", "casr_bias_destroy", "casr_bias_score_host", "casr_bias_score", "casr_bias_rows_host",
+    "casr_bias_rows", "casr_beam_bias", "casr_beam_record_bias",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -148,6 +150,14 @@ def load(path=None, variant=None):
         "casr_mbr_host": (i32, [vp, vp, vp, vp, i32, i32, i32] + [ctypes.c_double] * 3 + [vp, vp]),
         "casr_beam_mbr": (i32, [vp, ctypes.c_double, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]),
         "casr_beam_mbr_distances": (i32, [vp, vp, vp, vp]),
+        "casr_bias_create": (i32, [i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
+        "casr_bias_destroy": (None, [vp]),
+        "casr_bias_score_host": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+        "casr_bias_score": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "casr_bias_rows_host": (i32, [vp, vp, i32, vp, vp]),
+        "casr_bias_rows": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "casr_beam_bias": (i32, [vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+        "casr_beam_record_bias": (i32, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -269,6 +279,7 @@ def pack_weights(cfg, enc_sd, dec_sd):
 
 
 EDIT_MAX_LEN = 512  # include/casr.h CASR_EDIT_MAX_LEN: the longest row of the device entry
+BIAS_MAX_LEN = 16   # include/casr.h CASR_BIAS_MAX_LEN: the longest phrase
 
 
 def _i32(a, shape=None):

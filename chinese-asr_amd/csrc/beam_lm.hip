@@ -114,13 +114,21 @@ struct BeamLmSelLds {
 // above it are collected, and those are ranked by counting.  The rows' lists are ranked the same way into the utterance's top 2k.  The
 // bookkeeping is beam_select_block's on that ranking; the chosen candidates pass on am and lm, which
 // their lane recomputes from the same operands (the same bits).
-template <int K2, bool UNIT_T>
-__global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(BeamSelArgs a, BeamLmArgs g) {
+// LM / BIAS: which scorers take part (casr_beam_lm: LM alone; casr_beam_bias: BIAS, with or without LM).
+// With BIAS the row's gain row (bias.hip) is read beside the logits, row r carries (s_r, C_r), and
+//   bias = (float)(v == eos ? C_r : C_r + gain[v]) / 256,  val = ((am + lm_weight lm) + bias_weight bias) + len_l
+// (without LM the lm_weight lm term is left out); the bookkeeping lanes walk the automaton for the
+// chosen candidates' delta and out_sum (bias_plan.h) and pass on (delta, C_r + out_sum).
+template <int K2, bool UNIT_T, bool LM, bool BIAS>
+__global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(BeamSelArgs a, BeamLmArgs g,
+                                                                             BeamBiasArgs hb) {
   constexpr int NWV = bs_waves<K2>(), NTH = 64 * NWV;
   __shared__ BeamLmSelLds<K2, KMAX_BEAM, NWV> S;
   if (done_before(a.newdone, a.l) >= a.B) return;
   const float* __restrict__ logits = a.logits;
   const float* __restrict__ terms = g.terms;
+  const int32_t* __restrict__ gains = hb.gain;
+  const float bw = hb.bias_weight;
   const int V = a.V, B = a.B, k = a.k, l = a.l, L = a.L, eos = a.eos, b = blockIdx.x;
   const float temperature = a.temperature;
   const GreedyPart& gp = a.gp;
@@ -136,11 +144,14 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
   for (int j = wv; j < nrows; j += NWV) {
     const size_t row = (size_t)(b * k + j);
     const float* x = logits + row * V;
-    const float* t = terms + row * V;
+    const float* t = LM ? terms + row * V : x;  // (without LM: never read)
+    const int32_t* gn = BIAS ? gains + row * V : nullptr;
     const float4* x4 = reinterpret_cast<const float4*>(x);
     const float4* t4 = reinterpret_cast<const float4*>(t);
+    const int4* gn4 = reinterpret_cast<const int4*>(gn);
     const float sc = a.score_cur[row];
-    const float gc = l == 0 ? 0.f : g.g_cur[row];
+    const float gc = (!LM || l == 0) ? 0.f : g.g_cur[row];
+    const int Cc = (!BIAS || l == 0) ? 0 : hb.full_cur[row];
     float lse;
     if (UNIT_T && nbp > 0 && gp.tmx && vec) {  // beam_select_block's first form: from the partials
       float mb = -INFINITY, sb = 0.f;
@@ -177,11 +188,19 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
       lse = logf(s) + mm;
     }
     if (ln == 0) S.lse[j] = lse;
-    auto val = [&](float xv, float tv) {
-      const float am = (xt(xv) - lse) + sc;
-      const float lm = l == 0 ? tv : __fadd_rn(gc, tv);
-      return __fadd_rn(__fadd_rn(am, __fmul_rn(lmw, lm)), len_l);
+    auto val = [&](float xv, float tv, int gv, int v) {
+      float r = (xt(xv) - lse) + sc;  // am
+      if constexpr (LM) {
+        const float lm = l == 0 ? tv : __fadd_rn(gc, tv);
+        r = __fadd_rn(r, __fmul_rn(lmw, lm));
+      }
+      if constexpr (BIAS) {
+        const float bias = __int2float_rn(v == eos ? Cc : Cc + gv) * (1.f / 256.f);  // (exact)
+        r = __fadd_rn(r, __fmul_rn(bw, bias));
+      }
+      return __fadd_rn(r, len_l);
     };
+    auto val_at = [&](int v) { return val(x[v], LM ? t[v] : 0.f, BIAS ? gn[v] : 0, v); };
     // this lane's largest and second-largest candidate values (distinct elements), then tau = the
     // 2k-th largest of the lanes' values: a lower bound of the row's 2k-th best
     float lt = -INFINITY, lt2 = -INFINITY;
@@ -199,11 +218,12 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
       for (int u = 0; u < LMS_QB; ++u) {
         const int i = ln + 64 * u;
         if (i < V / 4) {
-          const float4 q = x4[i], w4 = t4[i];
-          vq[u][0] = val(q.x, w4.x);
-          vq[u][1] = val(q.y, w4.y);
-          vq[u][2] = val(q.z, w4.z);
-          vq[u][3] = val(q.w, w4.w);
+          const float4 xq = x4[i], w4 = LM ? t4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+          const int4 g4 = BIAS ? gn4[i] : make_int4(0, 0, 0, 0);
+          vq[u][0] = val(xq.x, w4.x, g4.x, 4 * i);
+          vq[u][1] = val(xq.y, w4.y, g4.y, 4 * i + 1);
+          vq[u][2] = val(xq.z, w4.z, g4.z, 4 * i + 2);
+          vq[u][3] = val(xq.w, w4.w, g4.w, 4 * i + 3);
         } else {
           vq[u][0] = vq[u][1] = vq[u][2] = vq[u][3] = -INFINITY;
         }
@@ -211,7 +231,7 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
         for (int e = 0; e < 4; ++e) top2(vq[u][e]);
       }
     } else {
-      for (int v = ln; v < V; v += 64) top2(val(x[v], t[v]));  // (a longer or unaligned row: two passes)
+      for (int v = ln; v < V; v += 64) top2(val_at(v));  // (a longer or unaligned row: two passes)
     }
     float tau = -INFINITY;
     for (int c = 0; c < n2k; ++c) {
@@ -245,7 +265,7 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
         }
       }
     } else {
-      for (int v = ln; v < V; v += 64) offer(val(x[v], t[v]), j * V + v);
+      for (int v = ln; v < V; v += 64) offer(val_at(v), j * V + v);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -271,7 +291,7 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
     } else {  // more ties at tau than the buffer holds: every element through sorted lane lists
       TopList<K2> tl;
       tl.init();
-      for (int v = ln; v < V; v += 64) tl.insert(val(x[v], t[v]), j * V + v);
+      for (int v = ln; v < V; v += 64) tl.insert(val_at(v), j * V + v);
       wave_merge<K2>(tl, n2k, S.rv[j], S.ri[j]);
     }
   }
@@ -309,17 +329,28 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
     const bool f = inr && tok == eos;
     const size_t srow = (size_t)(b * k + beam);
     float am = 0.f, lm = 0.f;
+    int bs = 0, bC = 0;  // BIAS: the candidate's successor state and its full
     if (inr) {
-      const float tv = terms[srow * V + tok];
       am = (xt(logits[srow * V + tok]) - S.lse[beam]) + a.score_cur[srow];
-      lm = l == 0 ? tv : __fadd_rn(g.g_cur[srow], tv);
+      if constexpr (LM) {
+        const float tv = terms[srow * V + tok];
+        lm = l == 0 ? tv : __fadd_rn(g.g_cur[srow], tv);
+      }
+      if constexpr (BIAS) {
+        bool sbad = false;
+        bs = l == 0 ? 0 : bias_clamp_state(hb.m, hb.st_cur[srow], &sbad);
+        bC = l == 0 ? 0 : hb.full_cur[srow];
+        if (sbad) atomicOr(a.err, CASR_DEV_BAD_TOKEN);
+        if (!f) bias_advance(hb.m, tok, &bs, &bC);  // (eos: the record keeps C_r, bias_closed)
+      }
     }
     if (c < k) {  // finished hypotheses among the first k candidates
       const size_t ri = ((size_t)b * L + l) * k + c;
       a.rec_valid[ri] = f;
       if (f) {
         a.rec_score[ri] = am;
-        g.rec_lm[ri] = lm;
+        if constexpr (LM) g.rec_lm[ri] = lm;
+        if constexpr (BIAS) hb.rec_full[ri] = bC;
         a.rec_src[ri] = beam;
       }
     }
@@ -336,40 +367,47 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
       a.tok_next[rw] = tok;
       a.src_next[rw] = b * k + beam;
       a.score_next[rw] = am;
-      g.g_next[rw] = lm;
+      if constexpr (LM) g.g_next[rw] = lm;
+      if constexpr (BIAS) {
+        hb.st_next[rw] = bs;
+        hb.full_next[rw] = bC;
+      }
       a.bp[(size_t)l * R + rw] = beam;
       a.tk[(size_t)l * R + rw] = tok;
     }
   }
 }
 
-template <int K2>
-static void launch_beam_lm_select_k(const BeamSelArgs& a, const BeamLmArgs& g, hipStream_t s) {
-  auto kern = a.temperature == 1.0f ? beam_lm_select_kernel<K2, true> : beam_lm_select_kernel<K2, false>;
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * bs_waves<K2>()), 0, s, a, g);
+template <int K2, bool LM, bool BIAS>
+static void launch_beam_lm_select_k(const BeamSelArgs& a, const BeamLmArgs& g, const BeamBiasArgs& q, hipStream_t s) {
+  auto kern = a.temperature == 1.0f ? beam_lm_select_kernel<K2, true, LM, BIAS>
+                                    : beam_lm_select_kernel<K2, false, LM, BIAS>;
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * bs_waves<K2>()), 0, s, a, g, q);
 }
 
-hipError_t launch_beam_lm_select(const BeamSelArgs& a, const BeamLmArgs& g, int K2, hipStream_t s) {
+template <bool LM, bool BIAS>
+static hipError_t launch_beam_lm_select_of(const BeamSelArgs& a, const BeamLmArgs& g, const BeamBiasArgs& q, int K2,
+                                           hipStream_t s) {
   switch (K2) {
-    case 4: launch_beam_lm_select_k<4>(a, g, s); break;
-    case 8: launch_beam_lm_select_k<8>(a, g, s); break;
-    case 16: launch_beam_lm_select_k<16>(a, g, s); break;
-    default: launch_beam_lm_select_k<32>(a, g, s);
+    case 4: launch_beam_lm_select_k<4, LM, BIAS>(a, g, q, s); break;
+    case 8: launch_beam_lm_select_k<8, LM, BIAS>(a, g, q, s); break;
+    case 16: launch_beam_lm_select_k<16, LM, BIAS>(a, g, q, s); break;
+    default: launch_beam_lm_select_k<32, LM, BIAS>(a, g, q, s);
   }
   return hipGetLastError();
 }
 
-// ------------------------------------------------------------------ the final choice
-// executed loop steps: the step at which the cumulative count of newdone reached `total`, + 1
-__device__ __forceinline__ int lmf_executed_steps(const int32_t* newdone, int L, int total) {
-  int cum = 0;
-  for (int s = 0; s < L; ++s) {
-    cum += newdone[s];
-    if (cum >= total) return s + 1;
-  }
-  return L;
+hipError_t launch_beam_lm_select(const BeamSelArgs& a, const BeamLmArgs& g, int K2, hipStream_t s) {
+  return launch_beam_lm_select_of<true, false>(a, g, BeamBiasArgs{}, K2, s);
 }
 
+hipError_t launch_beam_bias_select(const BeamSelArgs& a, const BeamLmArgs& g, const BeamBiasArgs& q, int K2,
+                                   hipStream_t s) {
+  return g.terms ? launch_beam_lm_select_of<true, true>(a, g, q, K2, s)
+                 : launch_beam_lm_select_of<false, true>(a, g, q, K2, s);
+}
+
+// ------------------------------------------------------------------ the final choice
 __device__ __forceinline__ float lmf_comb(float am, float lm, float lmw, float lenw, int l) {
   const float len_l = (float)((double)lenw * (double)(l + 1));
   return __fadd_rn(__fadd_rn(am, __fmul_rn(lmw, lm)), len_l);

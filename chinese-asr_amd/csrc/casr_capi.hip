@@ -216,6 +216,8 @@ struct casr_handle {
   bool beam_done = false;
   bool beam_lm_done = false;  // the last beam was casr_beam_lm: lmws holds its rec_lm
   DevBuf lmws;                // casr_beam_lm: term rows, LM sums, rec_lm (carve_beam_lm)
+  bool beam_bias_done = false;  // the last beam was casr_beam_bias: biasws holds its rec_full
+  DevBuf biasws;                // casr_beam_bias: gain rows, states, sums, rec_full (carve_beam_bias)
   float beam_lm_weight = 0.f, beam_length_weight = 0.f;  // the last casr_beam's (casr_beam_rescore's fallback)
   DevBuf mbrws;           // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
   bool mbr_done = false;  // mbrws holds the distances of the last beam's records
@@ -239,6 +241,14 @@ struct casr_lm {
   void* dev[11] = {};    // uni, redirect, tab[0..2]; succ: list[0..2], dir, ctab[0..1]
   NgramView dview{};
   NgramSuccView dsucc{};
+};
+
+// An immutable phrase automaton (bias_plan.h): the host tables, and for device >= 0 their copy there.
+struct casr_bias {
+  int device = -1;
+  BiasTables host;
+  void* dev[5] = {};  // node, ctok, cnext, root_next, root_gain
+  BiasView dview{};
 };
 
 static int fail(casr_handle* h, int code, const char* fmt, ...);
@@ -587,7 +597,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws})
+                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->biasws})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1308,6 +1318,7 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
   h->dec_k = k;
   h->beam_done = true;
   h->beam_lm_done = false;
+  h->beam_bias_done = false;
   h->mbr_done = false;
   h->beam_lm_weight = lm_weight;
   h->beam_length_weight = length_weight;
@@ -1457,8 +1468,8 @@ int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, doubl
   if (!h || !lm || !best_tokens || !best_len || !best_score)
     return fail(h, CASR_ERR_ARG, "casr_beam_rescore: NULL handle, LM or output");
   if (!h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_rescore before casr_beam");
-  if (h->beam_lm_done)
-    return fail(h, CASR_ERR_STATE, "casr_beam_rescore after casr_beam_lm: the second pass rescores a casr_beam");
+  if (h->beam_lm_done || h->beam_bias_done)
+    return fail(h, CASR_ERR_STATE, "casr_beam_rescore after casr_beam_lm or casr_beam_bias: the second pass rescores a casr_beam");
   if (lm->device != h->device)
     return fail(h, CASR_ERR_ARG, "casr_beam_rescore: the LM is %s, the handle on device %d",
                 lm->device < 0 ? "host-only" : "on another device", h->device);
@@ -1525,8 +1536,8 @@ int casr_beam_mbr(casr_handle* h, double scale, const float* rec_lm, double lm_w
   if (!(scale >= 0.0) || !std::isfinite(scale))
     return fail(h, CASR_ERR_ARG, "casr_beam_mbr: scale %g is negative or not finite", scale);
   if (!h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_mbr before casr_beam");
-  if (h->beam_lm_done)
-    return fail(h, CASR_ERR_STATE, "casr_beam_mbr after casr_beam_lm: the fallback assumes the scores of a casr_beam");
+  if (h->beam_lm_done || h->beam_bias_done)
+    return fail(h, CASR_ERR_STATE, "casr_beam_mbr after casr_beam_lm or casr_beam_bias: the fallback assumes the scores of a casr_beam");
   if (!mbr_supported(h->cfg.max_len, h->dec_k))
     return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_mbr: max_len %d x k %d: distances are bytes (max_len <= %d) and the tree must fit 64 KB of LDS",
                 h->cfg.max_len, h->dec_k, EDIT_MBR_MAX_LEN);
@@ -1614,6 +1625,7 @@ int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, floa
   h->dec_k = k;
   h->beam_done = true;
   h->beam_lm_done = true;
+  h->beam_bias_done = false;
   h->mbr_done = false;
   h->beam_lm_weight = lm_weight;
   h->beam_length_weight = length_weight;
@@ -1635,6 +1647,180 @@ int casr_beam_record_lm(casr_handle* h, float* rec_lm, void* stream) {
   BeamLmBufs w{};
   carve_beam_lm(h->lmws.p, c.a.B, c.a.plan.R, c.a.max_len, c.a.k, c.a.V, w);
   HIP_OK(h, run_beam_record_lm(c.a, h->d, w, rec_lm, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_bias_create(int device, int vocab, int n_phrases, const int32_t* tokens, const int32_t* lens,
+                     const int32_t* boost, casr_bias** out) {
+  if (!out) return fail(nullptr, CASR_ERR_ARG, "casr_bias_create: out is NULL");
+  *out = nullptr;
+  if (device < -1) return fail(nullptr, CASR_ERR_ARG, "casr_bias_create: device %d", device);
+  casr_bias* bo = new casr_bias();
+  std::string why;
+  const int rc = bias_build(vocab, n_phrases, tokens, lens, boost, &bo->host, &why);
+  if (rc != BIAS_OK) {
+    delete bo;
+    return fail(nullptr, rc, "casr_bias_create: %s", why.c_str());
+  }
+  bo->device = device;
+  if (device >= 0) {
+    const BiasTables& t = bo->host;
+    const void* src[5] = {t.node.data(), t.ctok.data(), t.cnext.data(), t.root_next.data(), t.root_gain.data()};
+    const size_t bytes[5] = {t.node.size() * sizeof(BiasNode), t.ctok.size() * sizeof(int32_t),
+                             t.cnext.size() * sizeof(int32_t), t.root_next.size() * sizeof(int32_t),
+                             t.root_gain.size() * sizeof(int32_t)};
+    hipError_t e = hipSetDevice(device);
+    for (int i = 0; i < 5 && e == hipSuccess; ++i) {
+      e = hipMalloc(&bo->dev[i], bytes[i] ? bytes[i] : 16);  // (no phrases: the root has no children)
+      if (e == hipSuccess && bytes[i]) e = hipMemcpy(bo->dev[i], src[i], bytes[i], hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+      casr_bias_destroy(bo);
+      return fail(nullptr, CASR_ERR_HIP, "casr_bias_create: %s", hipGetErrorString(e));
+    }
+    bo->dview = BiasView{t.V, (int)t.node.size(), static_cast<const BiasNode*>(bo->dev[0]),
+                         static_cast<const int32_t*>(bo->dev[1]), static_cast<const int32_t*>(bo->dev[2]),
+                         static_cast<const int32_t*>(bo->dev[3]), static_cast<const int32_t*>(bo->dev[4])};
+  }
+  *out = bo;
+  return CASR_OK;
+}
+
+void casr_bias_destroy(casr_bias* bias) {
+  if (!bias) return;
+  if (bias->device >= 0 && hipSetDevice(bias->device) == hipSuccess)
+    for (void* p : bias->dev)
+      if (p) (void)hipFree(p);
+  delete bias;
+}
+
+int casr_bias_score_host(const casr_bias* bias, const int32_t* tokens, const int32_t* lens, int n, int L,
+                         int32_t* full, int32_t* tail, int32_t* state) {
+  if (!bias || n < 0 || L < 0 || (n > 0 && (!lens || (!tokens && L > 0))))
+    return fail(nullptr, CASR_ERR_ARG, "casr_bias_score_host: NULL argument, n < 0 or L < 0");
+  for (int i = 0; i < n; ++i)
+    if (lens[i] < 0 || lens[i] > L)
+      return fail(nullptr, CASR_ERR_ARG, "casr_bias_score_host: lens[%d] = %d not in [0, %d]", i, lens[i], L);
+  const BiasView m = bias->host.view();
+  for (int i = 0; i < n; ++i) {
+    int32_t f, t, s;
+    bias_sentence(m, tokens + (size_t)i * L, lens[i], &f, &t, &s);
+    if (full) full[i] = f;
+    if (tail) tail[i] = t;
+    if (state) state[i] = s;
+  }
+  return CASR_OK;
+}
+
+// the refusals casr_bias_score, casr_bias_rows and casr_beam_bias share
+static int bias_on_handle(casr_handle* h, const casr_bias* bias, const char* who) {
+  if (bias->device != h->device)
+    return fail(h, CASR_ERR_ARG, "%s: the bias object is %s, the handle on device %d", who,
+                bias->device < 0 ? "host-only" : "on another device", h->device);
+  if (bias->host.V != h->cfg.vocab)
+    return fail(h, CASR_ERR_ARG, "%s: the bias object's vocab %d is not the handle's %d", who, bias->host.V,
+                h->cfg.vocab);
+  return CASR_OK;
+}
+
+int casr_bias_score(casr_handle* h, const casr_bias* bias, const int32_t* tokens, const int32_t* lens, int n,
+                    int L, int32_t* full, int32_t* tail, int32_t* state, void* stream) {
+  if (!h || !bias || n < 0 || (n > 0 && (!tokens || !lens)))
+    return fail(h, CASR_ERR_ARG, "casr_bias_score: NULL argument or n < 0");
+  int rc = bias_on_handle(h, bias, "casr_bias_score");
+  if (rc) return rc;
+  if (L < 1 || L > BIAS_MAX_SENT)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_bias_score: L = %d not in [1, %d]", L, BIAS_MAX_SENT);
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_bias_score: no guard words");
+  HIP_OK(h, launch_bias_score(bias->dview, tokens, lens, n, L, full, tail, state, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_bias_rows_host(const casr_bias* bias, const int32_t* state, int n, int32_t* gain, int32_t* next) {
+  if (!bias || n < 0 || (n > 0 && (!state || !gain)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_bias_rows_host: NULL argument or n < 0");
+  const BiasView m = bias->host.view();
+  for (int i = 0; i < n; ++i)
+    if (state[i] < 0 || state[i] >= m.n_nodes)
+      return fail(nullptr, CASR_ERR_ARG, "casr_bias_rows_host: state[%d] = %d not in [0, %d)", i, state[i], m.n_nodes);
+  for (int i = 0; i < n; ++i)
+    bias_row_host(m, state[i], gain + (size_t)i * m.V, next ? next + (size_t)i * m.V : nullptr);
+  return CASR_OK;
+}
+
+int casr_bias_rows(casr_handle* h, const casr_bias* bias, const int32_t* state, int n, int32_t* gain,
+                   int32_t* next, void* stream) {
+  if (!h || !bias || n < 0 || (n > 0 && (!state || !gain)))
+    return fail(h, CASR_ERR_ARG, "casr_bias_rows: NULL argument or n < 0");
+  int rc = bias_on_handle(h, bias, "casr_bias_rows");
+  if (rc) return rc;
+  if (!bias_rows_supported(bias->host.V))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_bias_rows: a row of %d words is past the %d KB of LDS it is assembled in",
+                bias->host.V, (int)(BIAS_ROWS_LDS_BYTES / 1024));
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_bias_rows: no guard words");
+  const BiasRowsSrc src{0, state, nullptr, 0, 1, 0};
+  HIP_OK(h, launch_bias_rows(bias->dview, src, n, gain, next, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_beam_bias(casr_handle* h, const casr_bias* bias, const casr_lm* lm, int k, float bias_weight,
+                   float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                   float* best_score, float* best_lm, float* best_bias, int32_t* steps, void* stream) {
+  if (!h || !bias || !best_tokens || !best_len || !best_score || !best_bias || !steps)
+    return fail(h, CASR_ERR_ARG, "casr_beam_bias: NULL handle, bias object or output");
+  if (!h->W) return fail(h, CASR_ERR_STATE, "casr_beam_bias before casr_bind_weights");
+  if (!h->encoded) return fail(h, CASR_ERR_STATE, "casr_beam_bias before casr_encode");
+  int rc = bias_on_handle(h, bias, "casr_beam_bias");
+  if (rc) return rc;
+  if (!bias_rows_supported(bias->host.V))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_bias: a row of %d words is past the %d KB of LDS it is assembled in",
+                bias->host.V, (int)(BIAS_ROWS_LDS_BYTES / 1024));
+  if (lm) {
+    rc = lm_on_handle(h, lm, "casr_beam_bias");
+    if (rc) return rc;
+  }
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  rc = prepare_decode(h, PLAN_BEAM_LM, k, false, c);
+  if (rc) return rc;
+  const DecodeArgs& a = c.a;
+  BeamLmBufs lw{};
+  if (lm) {
+    HIP_OK(h, h->lmws.ensure(carve_beam_lm(nullptr, a.B, a.plan.R, a.max_len, a.k, a.V, lw)));
+    carve_beam_lm(h->lmws.p, a.B, a.plan.R, a.max_len, a.k, a.V, lw);
+  }
+  BeamBiasBufs w{};
+  HIP_OK(h, h->biasws.ensure(carve_beam_bias(nullptr, a.B, a.plan.R, a.max_len, a.k, a.V, w)));
+  carve_beam_bias(h->biasws.p, a.B, a.plan.R, a.max_len, a.k, a.V, w);
+  h->dec_k = k;
+  h->beam_done = true;
+  h->beam_lm_done = lm != nullptr;  // (casr_beam_record_lm reads lmws)
+  h->beam_bias_done = true;
+  h->mbr_done = false;
+  h->beam_lm_weight = lm_weight;
+  h->beam_length_weight = length_weight;
+  // (never a hipGraph: launched eagerly whatever casr_set_graphs says)
+  dg_trace_init();  // CASR_DG_TRACE diagnostics only
+  HIP_OK(h, run_beam_bias(a, h->d, lm ? &lw : nullptr, w, bias->dview, lm ? &lm->dview : nullptr,
+                          lm ? &lm->dsucc : nullptr, bias_weight, lm_weight, length_weight, best_tokens, best_len,
+                          best_score, lm ? best_lm : nullptr, best_bias, steps, (hipStream_t)stream));
+  dg_trace_dump();
+  return CASR_OK;
+}
+
+int casr_beam_record_bias(casr_handle* h, float* rec_bias, void* stream) {
+  if (!h || !h->beam_done || !h->beam_bias_done)
+    return fail(h, CASR_ERR_STATE, "casr_beam_record_bias before casr_beam_bias");
+  if (!rec_bias) return fail(h, CASR_ERR_ARG, "casr_beam_record_bias: NULL output");
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  int rc = prepare_decode(h, PLAN_BEAM_LM, h->dec_k, false, c);
+  if (rc) return rc;
+  BeamBiasBufs w{};
+  carve_beam_bias(h->biasws.p, c.a.B, c.a.plan.R, c.a.max_len, c.a.k, c.a.V, w);
+  HIP_OK(h, run_beam_record_bias(c.a, h->d, w, rec_bias, (hipStream_t)stream));
   return CASR_OK;
 }
 

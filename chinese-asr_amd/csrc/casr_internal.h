@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "bias_plan.h"
 #include "casr.h"
 #include "encode_plan.h"
 #include "ngram_succ.h"
@@ -524,6 +525,64 @@ hipError_t run_beam_record_lm(const DecodeArgs& a, const DecodeBufs& d, const Be
 hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, const NgramView& m,
                        const NgramSuccView& sv, float lm_weight, float length_weight, int32_t* best_tokens,
                        int32_t* best_len, float* best_score, float* best_lm, int32_t* steps, hipStream_t s);
+
+// bias.hip: hotword biasing (bias_plan.h's automaton; casr_bias_score, casr_bias_rows, casr_beam_bias).
+// Where a gain row's state comes from: tree == 0 the array state [n]; tree == 1 the row's state at decode
+// step l (row i = b k + j), skipping the rows the select of step l does not read, as LmTermsSrc
+struct BiasRowsSrc {
+  int tree;
+  const int32_t* state;
+  const int32_t* newdone;
+  int l, k, B;
+};
+constexpr size_t BIAS_ROWS_LDS_BYTES = 64 * 1024;  // a gain row and its states (8 V bytes) are assembled in LDS
+bool bias_rows_supported(int V);
+// gain [n][V] and next [n][V] (or null) of n rows; m holds device pointers
+hipError_t launch_bias_rows(const BiasView& m, const BiasRowsSrc& src, int n, int32_t* gain, int32_t* next,
+                            int32_t* err, hipStream_t s);
+hipError_t launch_bias_score(const BiasView& m, const int32_t* tokens, const int32_t* lens, int n, int L,
+                             int32_t* full, int32_t* tail, int32_t* state, int32_t* err, hipStream_t s);
+// the biased beam's own buffers (handle-owned, beside DecodeBufs and BeamLmBufs)
+struct BeamBiasBufs {
+  int32_t* gain;      // [R][V] the step's gain rows
+  int32_t* st[2];     // [R] the rows' automaton states (ping-pong, as DecodeBufs::score)
+  int32_t* full[2];   // [R] ... and C_r = full(y_r)
+  int32_t* rec_full;  // [B][L][k] full of each finished record
+};
+inline size_t carve_beam_bias(void* base, int B, int R, int L, int k, int V, BeamBiasBufs& w) {
+  Carver c(base);
+  w.gain = c.take<int32_t>((size_t)R * V, 16);  // rows read 16 B at a time
+  for (int i = 0; i < 2; ++i) w.st[i] = c.take<int32_t>(R);
+  for (int i = 0; i < 2; ++i) w.full[i] = c.take<int32_t>(R);
+  w.rec_full = c.take<int32_t>((size_t)B * L * k);
+  return c.bytes(256);
+}
+// what the biased select has beyond a fused select's operands; m holds device pointers
+struct BeamBiasArgs {
+  BiasView m;
+  const int32_t* gain;
+  const int32_t* st_cur;
+  const int32_t* full_cur;
+  int32_t* st_next;
+  int32_t* full_next;
+  int32_t* rec_full;
+  float bias_weight;
+};
+// beam_lm.hip: the fused select with the bias row read beside the logits and, with g.terms, the term rows
+hipError_t launch_beam_bias_select(const BeamSelArgs& a, const BeamLmArgs& g, const BeamBiasArgs& q, int K2,
+                                   hipStream_t s);
+// lw null: no LM took part
+hipError_t launch_beam_bias_finalize(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs* lw,
+                                     const BeamBiasBufs& w, const BiasView& m, float bias_weight, float lm_weight,
+                                     float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
+                                     float* best_lm, float* best_bias, int32_t* steps, hipStream_t s);
+hipError_t run_beam_record_bias(const DecodeArgs& a, const DecodeBufs& d, const BeamBiasBufs& w, float* rec_bias,
+                                hipStream_t s);
+// decoder.hip: run_beam_lm's steps with the gain rows (and, with lw, the term rows) before the select
+hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* lw, const BeamBiasBufs& w,
+                         const BiasView& bm, const NgramView* m, const NgramSuccView* sv, float bias_weight,
+                         float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                         float* best_score, float* best_lm, float* best_bias, int32_t* steps, hipStream_t s);
 
 // edit.hip: edit distance on the device (edit_plan.h's rule, backtrace, total order and plan).
 // n pairs a [n][La] / b [n][Lb] with their lengths; ops null or [n][3]

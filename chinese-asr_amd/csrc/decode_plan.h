@@ -130,8 +130,9 @@ inline int fold_gemm_shape(bool beam, int R, bool ksplit) {
 }
 
 // ---------------------------------------------------------------- the plan
-// the API call that decodes.  PLAN_BEAM_LM (casr_beam_lm): casr_beam's steps at that shape; the select,
-// which ranks with the LM term, is always a launch of its own (it reads the whole logits row)
+// the API call that decodes.  PLAN_BEAM_LM (casr_beam_lm, casr_beam_bias): casr_beam's steps at that
+// shape; the select, which ranks with the LM term and / or the phrase bias, is always a launch of its own
+// (it reads the whole logits row)
 enum { PLAN_GREEDY = 0, PLAN_BEAM = 1, PLAN_SCORE = 2, PLAN_BEAM_LM = 3 };
 enum {
   PLAN_OK = 0,

@@ -1981,4 +1981,53 @@ hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, 
                                  s);
 }
 
+// casr_beam_bias: run_beam_lm's steps (the same plan); after each step the gain rows of the rows'
+// automaton states (bias.hip), with an LM (lw, m, sv) its term rows too, and the select with its BIAS
+// switch.  Step 0's rows are at the root with full 0, which the kernels take without reading w.st / w.full.
+hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* lw, const BeamBiasBufs& w,
+                         const BiasView& bm, const NgramView* m, const NgramSuccView* sv, float bias_weight,
+                         float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                         float* best_score, float* best_lm, float* best_bias, int32_t* steps, hipStream_t s) {
+  const int R = a.B * a.k;
+  if (a.plan.caller != PLAN_BEAM_LM || a.plan.fuse_select) return hipErrorInvalidValue;
+  if ((lw != nullptr) != (m != nullptr) || (lw != nullptr) != (sv != nullptr)) return hipErrorInvalidValue;
+  FillList fl;
+  fl.add32(d.newdone, 0, a.max_len);
+  fl.add8(d.topfin, 0, a.B);
+  hipError_t e0 = fill_multi(fl, s);
+  if (e0 != hipSuccess) return e0;
+  hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, a.k,
+                     a.sos, d.tok[0], d.src[0], d.score[0], nullptr);
+  for (int l = 0; l < a.max_len; ++l) {
+    hipError_t e;
+    if (!a.plan.fold) {
+      e = decode_step(a, d, l, a.B, nullptr, s);
+    } else if (l == 0) {
+      e = decode_step(a, d, 0, a.B, nullptr, s, nullptr, false);
+    } else {
+      e = fold_attention_step(a, d, l, a.B, nullptr, false, GreedySel{}, s, nullptr);
+    }
+    if (e == hipSuccess && a.plan.fold) e = fold_gemm_step(a, d, l, a.B, s);
+    if (e != hipSuccess) return e;
+    ProfScope ps(a.prof, CASR_K_SELECT, s);
+    const float len_l = (float)((double)length_weight * (double)(l + 1));
+    BeamLmArgs g{nullptr, nullptr, nullptr, nullptr, lm_weight, len_l};
+    if (lw) {
+      const LmTermsSrc src{1, nullptr, nullptr, d.bp, d.tk, d.newdone, l, a.k, a.B, R};
+      e = launch_lm_terms(*m, *sv, src, R, a.eos, lw->terms, d.err, s);
+      if (e != hipSuccess) return e;
+      g = BeamLmArgs{lw->terms, lw->g[l & 1], lw->g[(l + 1) & 1], lw->rec_lm, lm_weight, len_l};
+    }
+    const BiasRowsSrc bsrc{1, w.st[l & 1], d.newdone, l, a.k, a.B};
+    e = launch_bias_rows(bm, bsrc, R, w.gain, nullptr, d.err, s);
+    if (e != hipSuccess) return e;
+    const BeamBiasArgs q{bm, w.gain, w.st[l & 1], w.full[l & 1], w.st[(l + 1) & 1], w.full[(l + 1) & 1], w.rec_full,
+                         bias_weight};
+    e = launch_beam_bias_select(beam_sel_args(a, d, l), g, q, a.plan.K2, s);
+    if (e != hipSuccess) return e;
+  }
+  return launch_beam_bias_finalize(a, d, lw, w, bm, bias_weight, lm_weight, length_weight, best_tokens, best_len,
+                                   best_score, best_lm, best_bias, steps, s);
+}
+
 }  // namespace casr

@@ -69,19 +69,27 @@ def features_for(audios):
     return [feat[b, :int(lens[b])] for b in range(len(audios))], lens
 
 
-def parse(path, model, audio_base, lm_model, bw, fusion=False):
-    """main.py:27-65: one file -> predicted text.  ``fusion``: Model.eval_one_batch_with_beam's."""
+def parse(path, model, audio_base, lm_model, bw, fusion=False, bias=None, bias_weight=1.0):
+    """main.py:27-65: one file -> predicted text.  ``fusion``, ``bias`` (a casr.bias.PhraseBias) and
+    ``bias_weight``: Model.eval_one_batch_with_beam's; with a bias an LM takes part only when fused."""
     data, lens = features_for(read_audio([path]))
     text = None
     if bw is not None:
         if gpd['verbose']:
             print(f"[INFO] Beam Decode [bw={bw}]...")
         res = model.eval_one_batch_with_beam(model.device, bw, data, lens, text, audio_base.int2word,
-                                             second_pass=True if lm_model is not None else False,
-                                             lm_model=lm_model, lm_weight=1.5, length_weight=1.5, fusion=fusion)
+                                             **_beam_args(lm_model, fusion, bias, bias_weight))
     else:
         res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, text)
     return res.pred_text[0]
+
+
+def _beam_args(lm_model, fusion, bias, bias_weight):
+    """The beam's keyword arguments; with a bias the LM enters only fused, and no second pass runs."""
+    if bias is not None and not fusion:
+        lm_model = None
+    return dict(second_pass=lm_model is not None, lm_model=lm_model, lm_weight=1.5, length_weight=1.5,
+                fusion=fusion and lm_model is not None, bias=bias, bias_weight=bias_weight)
 
 
 def align(path, text, model, audio_base):
@@ -94,14 +102,13 @@ def align(path, text, model, audio_base):
     return [(ch, float(start[i]), float(res.token_logp[0][i])) for i, ch in enumerate(text)]
 
 
-def parse_batch(paths, model, audio_base, lm_model=None, bw=None, fusion=False):
+def parse_batch(paths, model, audio_base, lm_model=None, bw=None, fusion=False, bias=None, bias_weight=1.0):
     """Batched form of parse (the reference's __init__.py names it but never defines it): all
     files go through the GPU path as one batch."""
     data, lens = features_for(read_audio(paths))
     if bw is not None:
         res = model.eval_one_batch_with_beam(model.device, bw, data, lens, None, audio_base.int2word,
-                                             second_pass=lm_model is not None, lm_model=lm_model,
-                                             lm_weight=1.5, length_weight=1.5, fusion=fusion)
+                                             **_beam_args(lm_model, fusion, bias, bias_weight))
     else:
         res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, None)
     return list(res.pred_text)
@@ -110,7 +117,8 @@ def parse_batch(paths, model, audio_base, lm_model=None, bw=None, fusion=False):
 MIN_SEGMENT_FRAMES = 9  # the delta filters' 9 taps: a shorter segment is returned with empty text
 
 
-def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, batch_size=256, fusion=False):
+def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, batch_size=256, fusion=False,
+               bias=None, bias_weight=1.0):
     """Recordings of any length -> per recording a list of casr.segment.Segment (start_s, end_s, text,
     score, truncated), this path's own addition: the log-mel of every recording is cut at its pauses
     on the device (casr_segment, include/casr.h; ``params`` a casr.segment.SegmentParams) and the
@@ -153,8 +161,7 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
         data = [feat[i, :int(flen[i])] for i in range(len(idx))]
         if bw is not None:
             res = model.eval_one_batch_with_beam(model.device, bw, data, flen, None, audio_base.int2word,
-                                                 second_pass=lm_model is not None, lm_model=lm_model,
-                                                 lm_weight=1.5, length_weight=1.5, fusion=fusion)
+                                                 **_beam_args(lm_model, fusion, bias, bias_weight))
             # no finished hypothesis: the fallback ran to max_len
             cut = (~model.engine.beam_records()[2].flatten(1).bool().any(1)).cpu().tolist()
         else:
@@ -170,10 +177,14 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
 class ASR:
     """main.py:68-102."""
 
-    def __init__(self, lm_path=None, bw=None, ckpt='./pretrain-0.06328.ckpt', lm_backend="kenlm", fusion=False):
+    def __init__(self, lm_path=None, bw=None, ckpt='./pretrain-0.06328.ckpt', lm_backend="kenlm", fusion=False,
+                 hotwords=None, hotword_boost=1.0, bias_weight=1.0):
         """lm_backend "kenlm" (default: the reference's import) or "casr": the library's own ARPA
         n-gram LM (casr.ngram.NgramLM), rescored on the device; with ``fusion`` (the "casr" backend
-        only) fused into the beam's first pass instead (Model.eval_one_batch_with_beam)."""
+        only) fused into the beam's first pass instead (Model.eval_one_batch_with_beam).
+        ``hotwords``: a list of phrases, or a text file with one phrase per line and an optional boost
+        in nats per token after it (casr.bias.read_hotwords; ``hotword_boost`` serves the others): the
+        beam search favours them (needs ``bw``)."""
         self.fusion = bool(fusion)
         if lm_backend not in ("kenlm", "casr"):
             raise ValueError(f"lm_backend must be 'kenlm' or 'casr', got {lm_backend!r}")
@@ -199,14 +210,21 @@ class ASR:
         self.lm_model = lm_model
         self.model = model
         self.bw = bw
+        self.bias, self.bias_weight = None, float(bias_weight)
+        if hotwords is not None:
+            from casr.bias import PhraseBias
+            if bw is None:
+                raise ValueError("hotwords need a beam search: pass bw")
+            self.bias = PhraseBias.coerce(hotwords, self.audio_base.word2int, model.cfg.vocab, hotword_boost)
 
     def __call__(self, path):
-        return parse(path, self.model, self.audio_base, self.lm_model, self.bw, fusion=self.fusion)
+        return parse(path, self.model, self.audio_base, self.lm_model, self.bw, fusion=self.fusion, bias=self.bias,
+                     bias_weight=self.bias_weight)
 
     def transcribe(self, path, params=None):
         """A recording of any length -> its text: the segments' texts of transcribe(), joined."""
         segs = transcribe([path], self.model, self.audio_base, self.lm_model, self.bw, params=params,
-                          fusion=self.fusion)[0]
+                          fusion=self.fusion, bias=self.bias, bias_weight=self.bias_weight)[0]
         return ''.join(s.text for s in segs)
 
 

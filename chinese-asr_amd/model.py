@@ -131,7 +131,7 @@ class Model(object):
     def eval_one_batch_with_beam(self, device, bmsz, data, lens, text, int2word,
                                  second_pass=gpd['second_pass'], lm_model=None,
                                  lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight'], fusion=False,
-                                 mbr=None):
+                                 mbr=None, bias=None, bias_weight=1.0):
         """model.py:604-987.  ``fusion`` (this path's own addition, default off): with an NgramLM as
         ``lm_model`` the LM is fused into the first pass on the device (casr_beam_lm: every candidate
         ranked by logp + lm_weight lm + length_weight (l + 1), the ranking model.py:843-857 was designed
@@ -142,8 +142,28 @@ class Model(object):
         exp(mbr (c - c_max)) (casr_beam_mbr), c the second pass's combined score: with an NgramLM and
         ``second_pass`` the LM enters c, without either c = logp + length_weight len.  ``score`` is the
         choice's first-pass score.  Any other ``lm_model`` cannot be read on the device: TypeError;
-        together with ``fusion``: ValueError."""
+        together with ``fusion``: ValueError.
+        ``bias`` (this path's own addition, default None: off): a casr.bias.PhraseBias, the hotwords the
+        search favours while it searches (casr_beam_bias: a candidate's rank gains bias_weight times the
+        boost of the phrases it completes or continues); ``score`` is the choice's acoustic
+        log-probability.  With ``fusion`` and an NgramLM the LM is fused as well; otherwise no LM takes
+        part in the first pass.  Together with ``mbr``, or with a host second pass (``second_pass`` and
+        an ``lm_model`` that is not fused): ValueError.  Both read the records of a plain beam through
+        its scores alone (casr_beam_mbr's and the second pass's fallback assume them), so a biased
+        search under them would be ranked by one expression and chosen by another."""
         self.model.eval()
+        if bias is not None:
+            if mbr is not None:
+                raise ValueError("bias and mbr exclude each other: the MBR choice reads the records of a plain beam")
+            if second_pass and lm_model is not None and not fusion:
+                raise ValueError("bias with a second pass: fuse the LM (fusion=True with a casr.ngram.NgramLM) "
+                                 "or drop it; the second pass rescores a plain beam")
+            if fusion and not isinstance(lm_model, NgramLM):
+                raise TypeError(f"fusion=True needs a casr.ngram.NgramLM as lm_model, got {type(lm_model).__name__}")
+            lm = lm_model if fusion else None
+            bsz, _, r = self._run(data, lens, lambda: self.engine.beam_bias(bias, bmsz, bias_weight, lm, lm_weight,
+                                                                            length_weight))
+            return self._first_pass_output(bsz, r, text, int2word)
         if mbr is not None:
             if fusion:
                 raise ValueError("mbr and fusion exclude each other: the MBR choice reads the records of a plain beam")
@@ -153,15 +173,7 @@ class Model(object):
             if not isinstance(lm_model, NgramLM):
                 raise TypeError(f"fusion=True needs a casr.ngram.NgramLM as lm_model, got {type(lm_model).__name__}")
             bsz, _, r = self._run(data, lens, lambda: self.engine.beam_lm(lm_model, bmsz, lm_weight, length_weight))
-            toks, blen, bscore = (r[n].cpu().numpy() for n in ('tokens', 'length', 'score'))
-            i2w = self._int2word(int2word)
-            pred_text = [''.join([i2w[idx] for idx in toks[b, :blen[b]].tolist()]) for b in range(bsz)]
-            wer = None
-            if text is not None:
-                text = [''.join([i2w[idx] for idx in ele]) for ele in text]
-                wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
-            return EvalOutput(pred_text=pred_text, score=[float(s) for s in bscore], text=text, wer=wer, n=bsz,
-                              alignment=None, audio_feat_len=None, text_len=None)
+            return self._first_pass_output(bsz, r, text, int2word)
         # an NgramLM (casr/ngram.py) is rescored on the device from the beam tree: no record copy and
         # no host pass; any other lm_model keeps the host second pass below
         on_device = bool(second_pass) and isinstance(lm_model, NgramLM)
@@ -194,6 +206,18 @@ class Model(object):
             wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
         return EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=None,
                           audio_feat_len=None, text_len=None)
+
+    def _first_pass_output(self, bsz, r, text, int2word):
+        """The EvalOutput of a beam whose first pass made the choice (beam_lm, beam_bias)."""
+        toks, blen, bscore = (r[n].cpu().numpy() for n in ('tokens', 'length', 'score'))
+        i2w = self._int2word(int2word)
+        pred_text = [''.join([i2w[idx] for idx in toks[b, :blen[b]].tolist()]) for b in range(bsz)]
+        wer = None
+        if text is not None:
+            text = [''.join([i2w[idx] for idx in ele]) for ele in text]
+            wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
+        return EvalOutput(pred_text=pred_text, score=[float(s) for s in bscore], text=text, wer=wer, n=bsz,
+                          alignment=None, audio_feat_len=None, text_len=None)
 
     @torch.no_grad()
     def score_one_batch(self, device, data, lens, text, word2int=None, int2word=None, eos=True):

@@ -498,6 +498,98 @@ int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, floa
                  void* stream);
 int casr_beam_record_lm(casr_handle* h, float* rec_lm, void* stream);
 
+/* Hotword (contextual) biasing: the caller lists phrases (names, product terms, addresses) and the beam
+ * search favours hypotheses that spell them WHILE it searches.  An n-gram LM cannot do this: the words
+ * that need the help are the ones its training text never saw.  The reference has no such pass; like
+ * the n-gram LM and the edit distance, the operation is DEFINED BY THE FORMULAS BELOW.  All bias
+ * arithmetic is int32, so the incremental device form, the host entries and a brute-force restatement
+ * (tests/bias_ref.py) agree exactly, in any order of evaluation.
+ *   Phrases   P >= 0 phrases; phrase p is a token sequence p[0..n_p), 1 <= n_p <= CASR_BIAS_MAX_LEN, ids
+ *             in [0, V), with an int32 boost b_p in [1, 4096] in units of 1/256 nat PER TOKEN.
+ *   Sequence  y[0..l) of plain int32 symbols; an id outside [0, V) matches nothing.
+ *   full(y)   the sum over every phrase p and every j with y[j - n_p .. j) == p of n_p b_p.  EVERY
+ *             occurrence of EVERY phrase counts, overlapping and nested ones included: listing both
+ *             北京 and 北京大学 boosts the longer one by both.
+ *   tail(y)   the maximum of m b_p over phrases p and 1 <= m < n_p, m <= l, with y[l - m .. l) ==
+ *             p[0..m); 0 when there is none.  The credit of a match in progress; it is withdrawn when the
+ *             match fails (the next step's tail no longer holds it).
+ *   bias_open(y) = (float)(full(y) + tail(y)) / 256, bias_closed(y) = (float)full(y) / 256: a finished
+ *             hypothesis keeps no partial credit.  The conversion is correctly rounded, the division exact.
+ * Boosts <= 4096 and lengths <= 16 keep every sum below 2^31 for sequences of up to 512 tokens (a
+ * position adds at most 4096 (1 + 2 + ... + 16) = 557,056; 512 of them 2.9e8).
+ * casr_bias_create builds, on the host, an Aho-Corasick automaton over the phrases (csrc/bias_plan.h):
+ * per node its fail link and depth, out_sum (the sum of n_p b_p over the phrases ending at the node or on
+ * its fail chain), tail (the maximum over the node and its fail chain of depth x the largest b_p among
+ * the phrases passing properly through) and its children ascending in token; the root's children are
+ * dense arrays [V].  State 0 is the root.  tokens holds the phrases back to back, lens [n_phrases],
+ * boost [n_phrases], all HOST arrays.  device >= 0 also uploads the automaton to that device
+ * (synchronously); device = -1 makes a host-only object.  The object is immutable: any number of handles
+ * on its device may share it, from any thread.  It must outlive the work enqueued with it.
+ * CASR_ERR_ARG: a NULL array, a length, id or boost out of range, a duplicate phrase
+ * (casr_last_error(NULL) says which); CASR_ERR_UNSUPPORTED: more than 2^20 tokens in total. */
+#define CASR_BIAS_MAX_LEN 16
+typedef struct casr_bias casr_bias;
+int casr_bias_create(int device, int vocab, int n_phrases, const int32_t* tokens, const int32_t* lens,
+                     const int32_t* boost, casr_bias** out);
+void casr_bias_destroy(casr_bias* bias);
+
+/* full [n], tail [n] and the final automaton state [n] (each may be NULL) of the sentences tokens
+ * [n][L] with lens [n].
+ * casr_bias_score_host: HOST pointers, any object, no GPU, any L >= 0; CASR_ERR_ARG for a NULL argument
+ * or a length outside [0, L].
+ * casr_bias_score: DEVICE pointers, one work item per sentence; a length outside [0, L] is clamped and
+ * raises guard bit 1; 1 <= L <= 512, else CASR_ERR_UNSUPPORTED.  Needs no weights and no encode. */
+int casr_bias_score_host(const casr_bias* bias, const int32_t* tokens, const int32_t* lens, int n, int L,
+                         int32_t* full, int32_t* tail, int32_t* state);
+int casr_bias_score(casr_handle* h, const casr_bias* bias, const int32_t* tokens, const int32_t* lens, int n,
+                    int L, int32_t* full, int32_t* tail, int32_t* state, void* stream);
+
+/* The dense rows of automaton states (the analogue of casr_lm_terms): for state [n], gain [n][V] int32,
+ * gain[i][v] = out_sum(d) + tail(d) with d = delta(state[i], v) (what candidate v adds to the row's full
+ * under bias_open), and next [n][V] (NULL or the d themselves).  delta(s, v) is the first node on s,
+ * fail(s), ... (root excluded) that has child v, else the root's child; the chain has at most 16 nodes.
+ * casr_bias_rows_host: HOST pointers; a state outside the automaton is CASR_ERR_ARG.
+ * casr_bias_rows: DEVICE pointers, one workgroup per row: the row is assembled in LDS from the root's
+ * dense arrays, the chain's children are scattered over it from the node nearest the root to the state
+ * itself with a barrier between nodes, so the deepest wins, and the row is written once, coalesced.  A
+ * state outside the automaton is clamped to the root and raises guard bit 1.  CASR_ERR_UNSUPPORTED: a row
+ * past the LDS it is assembled in (8 V bytes > 64 KB).  CASR_ERR_ARG: a NULL argument, n < 0, an object
+ * that is host-only or on another device, or whose vocab is not the handle's. */
+int casr_bias_rows_host(const casr_bias* bias, const int32_t* state, int n, int32_t* gain, int32_t* next);
+int casr_bias_rows(casr_handle* h, const casr_bias* bias, const int32_t* state, int n, int32_t* gain,
+                   int32_t* next, void* stream);
+
+/* Beam search with the phrase bias, and optionally the n-gram LM, in the first pass.  am, lm, len_l, the
+ * top 2k, the tie rule, ranking beam 0 only at step 0, and the record, early-stop and active-set
+ * bookkeeping are exactly casr_beam_lm's.  At step l, row r with tokens y_r ranks candidate v by
+ *     bias = v == eos ? bias_closed(y_r) : bias_open(y_r . v)
+ *     val  = ((am + lm_weight lm) + bias_weight bias) + len_l
+ * each operation an f32 operation rounded on its own; with lm == NULL the lm_weight lm term is left out.
+ * A row carries the integer pair (s_r, C_r), its automaton state and C_r = full(y_r): the candidate's
+ * integer is C_r + gain(s_r, v) (C_r for eos), and the successor carries (delta, C_r + out_sum(delta)).
+ * The chosen candidates pass on am, lm and the integer state, not val.  A record stores am, lm and
+ * rec_bias = bias_closed of its tokens (casr_beam_record_bias: rec_bias [B][max_len][k] float, 0 where
+ * there is no valid record).  The best hypothesis is the first maximum of the same expression over the
+ * valid records in (step, rank) order; without a record, over the k live rows of the last executed step,
+ * which use bias_open.  best_score is the choice's am, best_lm (NULL without an LM, else optional) its lm,
+ * best_bias its bias.  With bias_weight = 0, or P = 0, every output equals casr_beam_lm's bit for bit (an
+ * added +0 changes no bits that are carried); with lm == NULL as well and length_weight = 0, casr_beam's.
+ * Per step the dense gain rows of the rows' states go through a handle-owned workspace of R V int32
+ * (casr_bias_rows' kernel), read by the select beside the logits and the optional term rows; the
+ * select's bookkeeping lanes recompute delta and out_sum of the chosen candidates from the automaton (at
+ * most 32 walks per utterance).  It counts under CASR_K_SELECT.  Never replayed as a hipGraph; no float
+ * atomics; results do not depend on scheduling.  Returns after enqueueing.
+ * Errors and state as casr_beam_lm: CASR_ERR_STATE before an encode or before weights are bound;
+ * CASR_ERR_ARG: a NULL handle, bias or required output, a bias or LM that is host-only, on another
+ * device or of another vocab, k outside 1..16; CASR_ERR_UNSUPPORTED: V > 8,192 (the gain row with its
+ * states is assembled in 64 KB of LDS).  After it casr_beam_rescore and casr_beam_mbr return
+ * CASR_ERR_STATE until the next casr_beam; casr_beam_records works; casr_beam_record_lm works only if an
+ * LM was given; casr_beam_record_bias returns CASR_ERR_STATE unless the last beam was a casr_beam_bias. */
+int casr_beam_bias(casr_handle* h, const casr_bias* bias, const casr_lm* lm_or_null, int k, float bias_weight,
+                   float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                   float* best_score, float* best_lm_or_null, float* best_bias, int32_t* steps, void* stream);
+int casr_beam_record_bias(casr_handle* h, float* rec_bias, void* stream);
+
 /* Edit distance, its operation counts, and a minimum-Bayes-risk (MBR) choice among the finished
  * hypotheses of a beam.  The reference computes a WER per utterance with python-Levenshtein
  * (util.py:237-262) and has no MBR; like the n-gram LM, the operation is DEFINED BY THE FORMULAS BELOW.
