@@ -495,6 +495,28 @@ class Engine:
         return dict(token_logp=token_logp, total_logp=total, best_token=best_token, best_logp=best_logp,
                     mean_logp=mean_logp, alignment=align, tgt_len=tgt_len)
 
+    def align_path(self, align, enc_len, tgt_len):
+        """The best monotone path through attention weights on the device (casr_align_path): align
+        [L, Tp, B] float32 as greedy(alignment=True) and score(alignment=True) return it (Tp at most
+        casr.lib.ALIGN_MAX_TP), enc_len [B] encoder frames and tgt_len [B] scored positions -> dict of
+        device tensors first, last, peak [B, L] int32 (-1 past tgt_len) and path_score [B] int32: the
+        values casr.lib.align_path_host gives.  Needs no weights and no encode; returns after enqueueing."""
+        dev = self.device
+        align = torch.as_tensor(align).to(dev, torch.float32).contiguous()
+        if align.dim() != 3:
+            raise ValueError("align_path: align must be [L, Tp, B]")
+        L, Tp, B = align.shape
+        enc_len = torch.as_tensor(enc_len).to(dev, torch.int32).contiguous()
+        tgt_len = torch.as_tensor(tgt_len).to(dev, torch.int32).contiguous()
+        if enc_len.shape != (B,) or tgt_len.shape != (B,):
+            raise ValueError(f"align_path: enc_len and tgt_len must be [B={B}]")
+        first, last, peak = (torch.empty(B, L, dtype=torch.int32, device=dev) for _ in range(3))
+        score = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.casr_align_path(self.handle, _ptr(align), _ptr(enc_len), _ptr(tgt_len), B, Tp, L,
+                                            _ptr(first), _ptr(last), _ptr(peak), _ptr(score), _stream()), self.handle)
+        self._keep_align = (align, enc_len, tgt_len)  # read by the enqueued kernel
+        return dict(first=first, last=last, peak=peak, path_score=score)
+
     def device_flags(self):
         """Guard bits raised since the previous read (read and clear: every encode / decode in
         between is covered; 0 = clean); synchronises the stream."""

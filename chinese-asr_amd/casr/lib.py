@@ -31,6 +31,7 @@ EXPORTS = [
     "casr_edit_distance_host", "casr_edit_distance", "casr_mbr_host", "casr_beam_mbr", "casr_beam_mbr_distances",
     "casr_bias_create", "casr_bias_destroy", "casr_bias_score_host", "casr_bias_score", "casr_bias_rows_host",
     "casr_bias_rows", "casr_beam_bias", "casr_beam_record_bias",
+    "casr_align_path_host", "casr_align_path",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -47,7 +48,7 @@ OPTIONS = {"FUSE_SELECT": 0, "REC_LAYOUT": 1, "REC_STORE_PLAIN": 2, "REC_SLEEP":
            "REC_COOP": 5, "GEMM16_PERSIST": 6, "GEMM16_TAIL": 7, "ATTN_KPB": 8, "ATTN_DIRECT": 9,
            "DEC_FOLD": 10, "REC_COOP_REFUSE": 11, "DIAG_COLD": 12,
            "LOGMEL_Q16": 13, "KEYS_ROWS": 14, "X16_KM": 15, "DEC_KSPLIT": 16, "GEMM16_LEAN": 17,
-           "ATTN_SPLIT": 18, "MBR_MAP": 19}
+           "ATTN_SPLIT": 18, "MBR_MAP": 19, "ALIGN_GROUP": 20}
 
 # kernel classes of casr_profile_enable / casr_profile_read (include/casr.h)
 KERNEL_CLASSES = ["features", "input_proj", "rec_step", "keys", "dec_lstm", "attention", "proj", "select"]
@@ -158,6 +159,8 @@ def load(path=None, variant=None):
         "casr_bias_rows": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "casr_beam_bias": (i32, [vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
         "casr_beam_record_bias": (i32, [vp, vp, vp]),
+        "casr_align_path_host": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "casr_align_path": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -280,6 +283,7 @@ def pack_weights(cfg, enc_sd, dec_sd):
 
 EDIT_MAX_LEN = 512  # include/casr.h CASR_EDIT_MAX_LEN: the longest row of the device entry
 BIAS_MAX_LEN = 16   # include/casr.h CASR_BIAS_MAX_LEN: the longest phrase
+ALIGN_MAX_TP = 1024  # include/casr.h CASR_ALIGN_MAX_TP: the longest row of casr_align_path
 
 
 def _i32(a, shape=None):
@@ -328,3 +332,22 @@ def mbr_host(rec_tokens, rec_score, rec_valid, scale, rec_lm=None, lm_weight=0.0
     check(lib.casr_mbr_host(p(rt), p(rs), p(rv), p(rl), B, L, k, float(scale), float(lm_weight), float(length_weight),
                             p(best), p(rr)), lib=lib)
     return (best, rr) if risk else best
+
+
+def align_path_host(align, enc_len, tgt_len):
+    """casr_align_path_host: the best monotone path through attention weights align [L, Tp, B] float32
+    (the layout Engine.greedy and Engine.score write), enc_len [B] encoder frames and tgt_len [B] scored
+    positions per utterance -> dict of first, last, peak [B, L] int32 (-1 past tgt_len) and path_score
+    [B] int32 (include/casr.h has the formulas).  Host only, no GPU."""
+    lib = load()
+    align = np.ascontiguousarray(align, dtype=np.float32)
+    if align.ndim != 3:
+        raise ValueError("align_path_host: align must be [L, Tp, B]")
+    L, Tp, B = align.shape
+    enc_len, tgt_len = _i32(enc_len, (B,)), _i32(tgt_len, (B,))
+    first, last, peak = (np.full((B, L), -1, np.int32) for _ in range(3))
+    score = np.zeros(B, np.int32)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x.size else None  # noqa: E731
+    check(lib.casr_align_path_host(p(align), p(enc_len), p(tgt_len), B, Tp, L, p(first), p(last), p(peak), p(score)),
+          lib=lib)
+    return dict(first=first, last=last, peak=peak, path_score=score)

@@ -8,8 +8,10 @@ from collections import namedtuple
 
 import numpy as np
 
+# timing (this path's own addition, None unless a decode is asked for timestamps): per utterance one
+# (start_s, end_s, peak_s, confidence) per character of pred_text (token_spans)
 EvalOutput = namedtuple('EvalOutput', ('pred_text', 'score', 'text', 'wer', 'n', 'alignment',
-                                       'audio_feat_len', 'text_len'))
+                                       'audio_feat_len', 'text_len', 'timing'), defaults=(None,))
 EncoderOutput = namedtuple('EncoderOutput', ('out', 'out_lens', 'state'))
 DecoderOutput = namedtuple('DecoderOutput', ('logit', 'attn_hidden_state', 'alignment', 'cell_state'))
 # Model.score_one_batch (teacher-forced scoring; no reference counterpart)
@@ -299,3 +301,26 @@ def token_times(align, enc_lens, tgt_len, sample_rate=16000):
         expect[b, :n] = a @ np.arange(T, dtype=np.float64)
     sec = 3 * 160 / float(sample_rate)
     return dict(frame=frame, expect=expect, frame_s=np.where(frame >= 0, frame * sec, 0.0), expect_s=expect * sec)
+
+
+def token_spans(first, last, peak, token_logp, tgt_len, sample_rate=16000, n_tokens=None):
+    """Per-token times and confidences from the monotone attention path (Engine.align_path /
+    casr.lib.align_path_host: first, last, peak [B, L] encoder frames) and the teacher-forced
+    log-probabilities of the same pass (token_logp [B, L]); tgt_len [B] the scored positions.  Per
+    utterance a list of (start_s, end_s, peak_s, confidence): start_s = first x 0.03, end_s = (last + 1)
+    x 0.03, peak_s = peak x 0.03 (one encoder frame = 3 stacked frames x 160 samples = 30 ms at 16 kHz),
+    confidence = exp(token_logp).  ``n_tokens`` [B] (default tgt_len) is how many positions are listed:
+    a closing eos is scored and takes part in the path, where it absorbs the trailing quiet, but is not
+    listed.  The spans tile the utterance, so token 0's span absorbs the leading quiet the same way:
+    start_s / end_s say which stretch of audio a token owns, peak_s (the frame of its span the
+    attention weighs most) is the robust instant of the token itself."""
+    first, last, peak = (np.asarray(x) for x in (first, last, peak))
+    token_logp = np.asarray(token_logp, np.float64)
+    sec = 3 * 160 / float(sample_rate)
+    n_tokens = tgt_len if n_tokens is None else n_tokens
+    out = []
+    for b in range(first.shape[0]):
+        n = min(int(n_tokens[b]), int(tgt_len[b]), first.shape[1])
+        out.append([(float(first[b, l] * sec), float((last[b, l] + 1) * sec), float(peak[b, l] * sec),
+                     float(np.exp(token_logp[b, l]))) for l in range(n) if first[b, l] >= 0])
+    return out

@@ -100,6 +100,7 @@ class Segment:
     text: str
     score: float
     truncated: bool  # the decode used all max_len steps without an EOS: lower max_frames
+    chars: list = None  # transcribe(timestamps=True): [(char, start_s, end_s, confidence)] in recording time
 
 
 def frame_time(frame):

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "casr.h"
+#include "align_plan.h"
 #include "casr_internal.h"
 #include "edit_plan.h"
 
@@ -1510,6 +1511,35 @@ int casr_edit_distance(casr_handle* h, const int32_t* a, const int32_t* a_len, i
   HIP_OK(h, hipSetDevice(h->device));
   if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_edit_distance: no guard words");
   HIP_OK(h, launch_edit_pairs(a, a_len, La, b, b_len, Lb, n, dist, ops, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_align_path_host(const float* align, const int32_t* enc_len, const int32_t* tgt_len, int B, int Tp, int L,
+                         int32_t* first, int32_t* last, int32_t* peak, int32_t* path_score) {
+  if (!align || !enc_len || !tgt_len || !first || !last || !peak || B < 1 || Tp < 1 || L < 1 || L > ALIGN_MAX_L)
+    return fail(nullptr, CASR_ERR_ARG, "casr_align_path_host: NULL argument, B or Tp < 1, or L outside [1, %d]",
+                ALIGN_MAX_L);
+  for (int b = 0; b < B; ++b) {
+    int T = enc_len[b], n = tgt_len[b];
+    align_clamp(T, Tp);
+    align_clamp(n, L);
+    const int32_t s = align_path_utterance(align + b, (size_t)Tp * B, (size_t)B, T, n, L, first + (size_t)b * L,
+                                           last + (size_t)b * L, peak + (size_t)b * L);
+    if (path_score) path_score[b] = s;
+  }
+  return CASR_OK;
+}
+
+int casr_align_path(casr_handle* h, const float* align, const int32_t* enc_len, const int32_t* tgt_len, int B, int Tp,
+                    int L, int32_t* first, int32_t* last, int32_t* peak, int32_t* path_score, void* stream) {
+  if (!h || !align || !enc_len || !tgt_len || !first || !last || !peak || B < 1 || Tp < 1 || L < 1 || L > ALIGN_MAX_L)
+    return fail(h, CASR_ERR_ARG, "casr_align_path: NULL argument, B or Tp < 1, or L outside [1, %d]", ALIGN_MAX_L);
+  if (Tp > ALIGN_MAX_TP)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_align_path: Tp = %d > %d (the move bits stay in LDS)", Tp, ALIGN_MAX_TP);
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_align_path: no guard words");
+  HIP_OK(h, launch_align_path(align, enc_len, tgt_len, B, Tp, L, h->tune[CASR_OPT_ALIGN_GROUP], first, last, peak,
+                              path_score, GUARD(h, 0), (hipStream_t)stream));
   return CASR_OK;
 }
 

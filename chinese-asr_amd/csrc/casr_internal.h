@@ -604,4 +604,9 @@ hipError_t run_beam_mbr(const DecodeArgs& a, const DecodeBufs& d, const MbrBufs&
                         int32_t* best_index, double* best_risk, double* rec_risk, hipStream_t s);
 hipError_t run_mbr_distances(const DecodeArgs& a, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s);
 
+// ---- align.hip: the monotone path through align [L][Tp][B] (align_plan.h); group: CASR_OPT_ALIGN_GROUP
+hipError_t launch_align_path(const float* align, const int32_t* enc_len, const int32_t* tgt_len, int B, int Tp, int L,
+                             int group, int32_t* first, int32_t* last, int32_t* peak, int32_t* path_score,
+                             int32_t* err, hipStream_t s);
+
 }  // namespace casr

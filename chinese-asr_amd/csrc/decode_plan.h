@@ -51,6 +51,7 @@ constexpr OptionRow OPTIONS[] = {
     {CASR_OPT_GEMM16_LEAN, "GEMM16_LEAN", 0, 0, 1},
     {CASR_OPT_ATTN_SPLIT, "ATTN_SPLIT", 0, 0, AT_SPLIT_MAX},
     {CASR_OPT_MBR_MAP, "MBR_MAP", 0, 0, 2},
+    {CASR_OPT_ALIGN_GROUP, "ALIGN_GROUP", 0, 0, 16},  // (0 or a power of two: option_value_ok)
 };
 constexpr bool options_in_enum_order() {
   for (int i = 0; i < CASR_OPT_COUNT; ++i)
@@ -63,6 +64,7 @@ static_assert(sizeof(OPTIONS) / sizeof(OPTIONS[0]) == CASR_OPT_COUNT && options_
 inline bool option_value_ok(int option, int value) {
   if (option < 0 || option >= CASR_OPT_COUNT) return false;
   if (option == CASR_OPT_ATTN_KPB && value != 0 && value != 4 && value != 8) return false;
+  if (option == CASR_OPT_ALIGN_GROUP && (value & (value - 1))) return false;
   return value >= OPTIONS[option].lo && value <= OPTIONS[option].hi;
 }
 

@@ -3,8 +3,9 @@
 
 ``parse(path, model, audio_base, lm_model, bw)`` and ``ASR(lm_path=None, bw=None)(path)`` keep
 the reference signatures and results; ``align(path, text, model, audio_base)`` is this path's own
-addition (forced alignment of a given transcript), and so is ``transcribe(paths, model, audio_base)``
-(recordings of any length, cut at their pauses on the device: casr_segment).  The chain wav ->
+addition (forced alignment of a given transcript), and so are ``transcribe(paths, model, audio_base)``
+(recordings of any length, cut at their pauses on the device: casr_segment), ``parse_timed`` and
+``ASR.subtitles`` (a start, an end and a confidence per decoded character: casr_align_path).  The chain wav ->
 log-mel -> delta/stack -> CMVN (eps 1e-6, main.py:37) -> encoder -> greedy / beam (+ second pass with a KenLM-like
 ``lm_model.score(s, bos=True)``) runs on the GPU through the casr C ABI.  Format conversion
 (``convert_audio``: ffmpeg + sox, main.py:19-24) uses the external tools where both are present;
@@ -84,6 +85,19 @@ def parse(path, model, audio_base, lm_model, bw, fusion=False, bias=None, bias_w
     return res.pred_text[0]
 
 
+def parse_timed(path, model, audio_base, lm_model=None, bw=None, fusion=False, bias=None, bias_weight=1.0):
+    """parse with times: one file -> [(char, start_s, end_s, confidence)], one tuple per character of
+    the text parse returns (Model.eval_one_batch_*'s ``timestamps``; casr.results.token_spans says what
+    the times mean)."""
+    data, lens = features_for(read_audio([path]))
+    if bw is not None:
+        res = model.eval_one_batch_with_beam(model.device, bw, data, lens, None, audio_base.int2word, timestamps=True,
+                                             **_beam_args(lm_model, fusion, bias, bias_weight))
+    else:
+        res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, None, timestamps=True)
+    return [(ch, t[0], t[1], t[3]) for ch, t in zip(res.pred_text[0], res.timing[0])]
+
+
 def _beam_args(lm_model, fusion, bias, bias_weight):
     """The beam's keyword arguments; with a bias the LM enters only fused, and no second pass runs."""
     if bias is not None and not fusion:
@@ -118,13 +132,15 @@ MIN_SEGMENT_FRAMES = 9  # the delta filters' 9 taps: a shorter segment is return
 
 
 def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, batch_size=256, fusion=False,
-               bias=None, bias_weight=1.0):
+               bias=None, bias_weight=1.0, timestamps=False):
     """Recordings of any length -> per recording a list of casr.segment.Segment (start_s, end_s, text,
     score, truncated), this path's own addition: the log-mel of every recording is cut at its pauses
     on the device (casr_segment, include/casr.h; ``params`` a casr.segment.SegmentParams) and the
     segments are decoded as parse decodes an utterance, ``batch_size`` at a time in (recording, time)
     order.  ``truncated`` marks a segment whose decode used all max_len steps without an EOS (lower
-    ``params.max_frames`` then).  A recording with no speech returns []."""
+    ``params.max_frames`` then).  A recording with no speech returns [].  With ``timestamps`` every
+    decoded segment's ``chars`` holds [(char, start_s, end_s, confidence)], one per character of its
+    text, in the recording's time (parse_timed's tuples, offset by the segment's start)."""
     import numpy as np
     import torch
     from data import _engine
@@ -161,14 +177,21 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
         data = [feat[i, :int(flen[i])] for i in range(len(idx))]
         if bw is not None:
             res = model.eval_one_batch_with_beam(model.device, bw, data, flen, None, audio_base.int2word,
+                                                 timestamps=timestamps,
                                                  **_beam_args(lm_model, fusion, bias, bias_weight))
-            # no finished hypothesis: the fallback ran to max_len
-            cut = (~model.engine.beam_records()[2].flatten(1).bool().any(1)).cpu().tolist()
+            # no finished hypothesis: the fallback ran to max_len (with timestamps the model took the
+            # flags before its scoring pass reused the beam's workspace)
+            cut = (model.beam_unfinished if timestamps else
+                   ~model.engine.beam_records()[2].flatten(1).bool().any(1)).cpu().tolist()
         else:
-            res = model.eval_one_batch_with_greedy(model.device, data, flen, audio_base.int2word, None)
+            res = model.eval_one_batch_with_greedy(model.device, data, flen, audio_base.int2word, None,
+                                                   timestamps=timestamps)
             cut = (res.text_len >= model.cfg.max_len).cpu().tolist()
         for j, i in enumerate(idx):
             segs[i].text, segs[i].score, segs[i].truncated = res.pred_text[j], float(res.score[j]), bool(cut[j])
+            if timestamps:
+                t0 = segs[i].start_s
+                segs[i].chars = [(ch, t0 + t[0], t0 + t[1], t[3]) for ch, t in zip(res.pred_text[j], res.timing[j])]
     for b, s in zip(src_h, segs):
         out[b].append(s)
     return out
@@ -226,6 +249,18 @@ class ASR:
         segs = transcribe([path], self.model, self.audio_base, self.lm_model, self.bw, params=params,
                           fusion=self.fusion, bias=self.bias, bias_weight=self.bias_weight)[0]
         return ''.join(s.text for s in segs)
+
+    def subtitles(self, path, fmt="srt", params=None):
+        """A recording of any length -> its subtitles as SubRip ("srt") or WebVTT ("vtt") text: the
+        segments of transcribe(timestamps=True), one cue each, split between characters while a cue
+        is too long (casr.subtitles.cues)."""
+        from casr import subtitles
+        if fmt not in ("srt", "vtt"):
+            raise ValueError(f"fmt must be 'srt' or 'vtt', got {fmt!r}")
+        segs = transcribe([path], self.model, self.audio_base, self.lm_model, self.bw, params=params,
+                          fusion=self.fusion, bias=self.bias, bias_weight=self.bias_weight, timestamps=True)[0]
+        cue_list = subtitles.cues(segs)
+        return subtitles.to_srt(cue_list) if fmt == "srt" else subtitles.to_vtt(cue_list)
 
 
 if __name__ == '__main__':

@@ -15,7 +15,7 @@ from casr.engine import Engine
 from casr.lib import pack_weights
 from casr.ngram import NgramLM
 from casr.results import (EvalOutput, ScoreOutput, encode_targets, get_wer, greedy_outputs, greedy_steps,
-                          label_smoothed_loss, score_outputs, second_pass_arrays, token_times, wer_batch)
+                          label_smoothed_loss, score_outputs, second_pass_arrays, token_spans, token_times, wer_batch)
 from casr.vocab import load_vocab
 from casr.weights import check_state_dicts, load_checkpoint, save_checkpoint, synthetic_state_dicts
 
@@ -60,6 +60,9 @@ class Model(object):
         self.decoder = _DecoderInfo(self.cfg)
         self.model = _ModuleList()
         self.optimizer = None
+        # eval_one_batch_with_beam(timestamps=True): [B] bool, the utterances whose beam finished no
+        # hypothesis (the handle's beam state cannot be asked afterwards); None after any other decode
+        self.beam_unfinished = None
         self._default_int2word = None
 
     # ------------------------------------------------------------------ weights
@@ -105,12 +108,53 @@ class Model(object):
         out, _ = self.engine.run_checked(lambda: self.engine.encode(feat, lens_d), decode)
         return feat.shape[0], lens, out
 
+    # ------------------------------------------------------------------ character timestamps
+    def _timed(self, tokens, length):
+        """Times of a decode's chosen tokens, on the encode the handle still holds: the tokens
+        [B, max_len] with their lengths [B] are scored teacher-forced (casr_score; an eos appended
+        where length < max_len, so the path has a row for the trailing quiet) and the monotone path
+        runs through that pass's attention (casr_align_path).  Device tensors; nothing is read back."""
+        L, dev = self.cfg.max_len, self.engine.device
+        tokens = torch.as_tensor(tokens).to(dev, torch.int32)
+        n = torch.as_tensor(length).to(dev, torch.int32)
+        pos = torch.arange(L, device=dev, dtype=torch.int32)[None, :]
+        tgt = torch.where(pos == n[:, None], torch.full_like(tokens, self.cfg.eos), tokens)
+        tgt_len = torch.clamp(n + 1, max=L)
+        sc = self.engine.score(tgt, tgt_len, alignment=True)
+        ap = self.engine.align_path(sc['alignment'], self.engine._lens, tgt_len)
+        return dict(ap, token_logp=sc['token_logp'], tgt_len=tgt_len, n_tokens=n)
+
+    def _with_timing(self, r, timestamps):
+        """r (a decode's dict with tokens and length / out_len) plus, when asked, its 'timing'.  The
+        scoring pass reuses the decode workspace, so a beam's state is spent after it (beam_records,
+        a rescore or an MBR choice would read a cleared step count): what main.transcribe wants from
+        it, which utterances finished no hypothesis, is taken first ('unfinished', [B] bool)."""
+        if not timestamps:
+            return r
+        if 'length' in r:
+            r = dict(r, unfinished=~self.engine.beam_records()[2].flatten(1).bool().any(1))
+        return dict(r, timing=self._timed(r['tokens'], r['length'] if 'length' in r else r['out_len']))
+
+    def _spans(self, timed, toks, i2w):
+        """_timed's tensors -> per utterance one token_spans tuple per character of the predicted text
+        (a token whose word has several characters lends each of them its span)."""
+        if timed is None:
+            return None
+        h = {k: v.cpu().numpy() for k, v in timed.items()}
+        spans = token_spans(h['first'], h['last'], h['peak'], h['token_logp'], h['tgt_len'],
+                            gpd.get('sample_rate', 16000), n_tokens=h['n_tokens'])
+        return [[sp for e, sp in zip(t, row) for _ in i2w[e]] for t, row in zip(toks, spans)]
+
     # ------------------------------------------------------------------ decode
     @torch.no_grad()
-    def eval_one_batch_with_greedy(self, device, data, lens, int2word=None, text=None):
-        """model.py:503-602."""
+    def eval_one_batch_with_greedy(self, device, data, lens, int2word=None, text=None, timestamps=False):
+        """model.py:503-602.  ``timestamps`` (this path's own addition, default off: nothing else is
+        launched): the result's ``timing`` holds per utterance one (start_s, end_s, peak_s, confidence)
+        per character of pred_text (casr.results.token_spans), from the monotone path through the
+        attention of a teacher-forced pass over the decoded tokens."""
         self.model.eval()
-        bsz, lens, out = self._run(data, lens, lambda: self.engine.greedy(alignment=True))
+        bsz, lens, out = self._run(data, lens,
+                                   lambda: self._with_timing(self.engine.greedy(alignment=True), timestamps))
         tokens = out['tokens'].cpu().numpy()
         out_len = out['out_len'].cpu().numpy()
         fin = out['finished'].cpu().numpy().astype(bool)
@@ -125,13 +169,13 @@ class Model(object):
             text = [''.join([i2w[e] for e in ele]) for ele in text]
             wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
         return EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=alignments,
-                          audio_feat_len=lens, text_len=out['out_len'])
+                          audio_feat_len=lens, text_len=out['out_len'], timing=self._spans(out.get('timing'), toks, i2w))
 
     @torch.no_grad()
     def eval_one_batch_with_beam(self, device, bmsz, data, lens, text, int2word,
                                  second_pass=gpd['second_pass'], lm_model=None,
                                  lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight'], fusion=False,
-                                 mbr=None, bias=None, bias_weight=1.0):
+                                 mbr=None, bias=None, bias_weight=1.0, timestamps=False):
         """model.py:604-987.  ``fusion`` (this path's own addition, default off): with an NgramLM as
         ``lm_model`` the LM is fused into the first pass on the device (casr_beam_lm: every candidate
         ranked by logp + lm_weight lm + length_weight (l + 1), the ranking model.py:843-857 was designed
@@ -150,7 +194,11 @@ class Model(object):
         part in the first pass.  Together with ``mbr``, or with a host second pass (``second_pass`` and
         an ``lm_model`` that is not fused): ValueError.  Both read the records of a plain beam through
         its scores alone (casr_beam_mbr's and the second pass's fallback assume them), so a biased
-        search under them would be ranked by one expression and chosen by another."""
+        search under them would be ranked by one expression and chosen by another.
+        ``timestamps`` (this path's own addition, default off: nothing else is launched): ``timing`` as
+        eval_one_batch_with_greedy fills it, for the hypothesis that was chosen, whatever chose it.  The
+        device-only modes score it inside the guarded decode; after a host second pass the scoring runs
+        once the host has chosen, on the encode the handle still holds, and the guard bits are read again."""
         self.model.eval()
         if bias is not None:
             if mbr is not None:
@@ -161,8 +209,8 @@ class Model(object):
             if fusion and not isinstance(lm_model, NgramLM):
                 raise TypeError(f"fusion=True needs a casr.ngram.NgramLM as lm_model, got {type(lm_model).__name__}")
             lm = lm_model if fusion else None
-            bsz, _, r = self._run(data, lens, lambda: self.engine.beam_bias(bias, bmsz, bias_weight, lm, lm_weight,
-                                                                            length_weight))
+            bsz, _, r = self._run(data, lens, lambda: self._with_timing(
+                self.engine.beam_bias(bias, bmsz, bias_weight, lm, lm_weight, length_weight), timestamps))
             return self._first_pass_output(bsz, r, text, int2word)
         if mbr is not None:
             if fusion:
@@ -172,20 +220,25 @@ class Model(object):
         if fusion:
             if not isinstance(lm_model, NgramLM):
                 raise TypeError(f"fusion=True needs a casr.ngram.NgramLM as lm_model, got {type(lm_model).__name__}")
-            bsz, _, r = self._run(data, lens, lambda: self.engine.beam_lm(lm_model, bmsz, lm_weight, length_weight))
+            bsz, _, r = self._run(data, lens, lambda: self._with_timing(
+                self.engine.beam_lm(lm_model, bmsz, lm_weight, length_weight), timestamps))
             return self._first_pass_output(bsz, r, text, int2word)
         # an NgramLM (casr/ngram.py) is rescored on the device from the beam tree: no record copy and
         # no host pass; any other lm_model keeps the host second pass below
         on_device = bool(second_pass) and isinstance(lm_model, NgramLM)
+        host_pass = bool(second_pass) and not on_device and mbr is None
 
         def decode():
             r = self.engine.beam(bmsz, lm_weight, length_weight)
             if mbr is not None:
-                return self.engine.beam_mbr(mbr, lm_model if on_device else None, lm_weight, length_weight)
-            return self.engine.beam_rescore(lm_model, lm_weight, length_weight) if on_device else r
+                r = self.engine.beam_mbr(mbr, lm_model if on_device else None, lm_weight, length_weight)
+            elif on_device:
+                r = self.engine.beam_rescore(lm_model, lm_weight, length_weight)
+            return self._with_timing(r, timestamps and not host_pass)
 
         bsz, _, r = self._run(data, lens, decode)
-        second_pass = second_pass and not on_device and mbr is None
+        self.beam_unfinished = r.get('unfinished')
+        second_pass = host_pass
         toks = r['tokens'].cpu().numpy()
         blen = r['length'].cpu().numpy()
         bscore = r['score'].cpu().numpy()
@@ -199,25 +252,36 @@ class Model(object):
             best.update(second_pass_arrays(rt, rs, rv, i2w, lm_model, lm_weight, length_weight))
         pred_text = [''.join([i2w[idx] for idx in best[b][0]]) for b in range(bsz)]
         score = [best[b][1] for b in range(bsz)]
+        timed = r.get('timing')
+        if timestamps and host_pass:
+            rows = np.full((bsz, self.cfg.max_len), -1, np.int32)
+            for b in range(bsz):
+                rows[b, :len(best[b][0])] = best[b][0]
+            self.beam_unfinished = torch.from_numpy(~rv.reshape(bsz, -1).astype(bool).any(axis=1))
+            timed = self._timed(torch.from_numpy(rows), torch.tensor([len(best[b][0]) for b in range(bsz)]))
+            self.engine.check_flags()
+        timing = self._spans(timed, [best[b][0] for b in range(bsz)], i2w)
         if text is not None:
             text = [''.join([i2w[idx] for idx in ele]) for ele in text]
         wer = None
         if text is not None:
             wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
         return EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=None,
-                          audio_feat_len=None, text_len=None)
+                          audio_feat_len=None, text_len=None, timing=timing)
 
     def _first_pass_output(self, bsz, r, text, int2word):
         """The EvalOutput of a beam whose first pass made the choice (beam_lm, beam_bias)."""
         toks, blen, bscore = (r[n].cpu().numpy() for n in ('tokens', 'length', 'score'))
+        self.beam_unfinished = r.get('unfinished')
         i2w = self._int2word(int2word)
         pred_text = [''.join([i2w[idx] for idx in toks[b, :blen[b]].tolist()]) for b in range(bsz)]
+        timing = self._spans(r.get('timing'), [toks[b, :blen[b]].tolist() for b in range(bsz)], i2w)
         wer = None
         if text is not None:
             text = [''.join([i2w[idx] for idx in ele]) for ele in text]
             wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
         return EvalOutput(pred_text=pred_text, score=[float(s) for s in bscore], text=text, wer=wer, n=bsz,
-                          alignment=None, audio_feat_len=None, text_len=None)
+                          alignment=None, audio_feat_len=None, text_len=None, timing=timing)
 
     @torch.no_grad()
     def score_one_batch(self, device, data, lens, text, word2int=None, int2word=None, eos=True):

@@ -667,6 +667,56 @@ int casr_beam_mbr(casr_handle* h, double scale, const float* rec_lm, double lm_w
                   double* best_risk, double* rec_risk, void* stream);
 int casr_beam_mbr_distances(casr_handle* h, uint8_t* dist, int32_t* n_rec, void* stream);
 
+/* Character timestamps: the best monotone path through the attention weights of a decode (the align
+ * that casr_greedy and casr_score write), per token its first, last and peak encoder frame.  The
+ * reference has no counterpart; like the edit distance the operation is DEFINED BY THE FORMULAS BELOW,
+ * in integers after the first, so the host entry and the kernel agree bit for bit and nothing depends
+ * on scheduling (no float atomics, no libm).
+ *   Inputs    align [L][Tp][B] f32; per utterance b: T = enc_len[b] frames and n = tgt_len[b] scored
+ *             positions (the closing eos among them when it was scored).  x = align[l][t][b].
+ *   Weight    q[l][t] = -3072 where !(x > 0) (zero, negative, NaN), else
+ *             clamp((int32)(bits(x) >> 16) - (127 << 7), -3072, 0), bits the f32's pattern: a
+ *             piecewise-linear log2 in 1/128 octave with the floor 2^-24; x >= 1 gives 0.
+ *   Path      cells (l, t), 0 <= l < n, 0 <= t < T, from (0, 0) to (n - 1, T - 1); a cell is entered by
+ *             the diagonal (l - 1, t - 1), by staying (l, t - 1) or vertically (l - 1, t).
+ *             D[0][0] = q[0][0]; D[l][t] = q[l][t] + max over the predecessors that exist; on equal
+ *             values the diagonal, then the vertical, then the stay.  int32: |D| <= 3072 (L + Tp).
+ *             The vertical move is what makes T < n well defined (tokens then share frames).
+ *   Backtrack from (n - 1, T - 1) through the moves the cells took: first[b][l] and last[b][l] the
+ *             smallest and largest t of token l's cells, peak[b][l] the smallest t in [first, last]
+ *             with the largest q[l][t]; path_score[b] = D[n - 1][T - 1].
+ *   Edges     n = 0 or T = 0: every output of the utterance -1 and path_score 0; positions l >= n get
+ *             -1.  A tgt_len outside [0, L] or an enc_len outside [0, Tp] is clamped (the device entry
+ *             raises guard bit 1; the host entry has no guard word and clamps silently).  Values of
+ *             align at t >= T or l >= n are never read as data.
+ *   first, last, peak [B][L] int32; path_score NULL or [B] int32.
+ * casr_align_path_host: every pointer a HOST pointer; no GPU, no handle, any Tp (64-bit sums: the same
+ * values wherever 3072 (L + Tp) fits an int32).
+ * casr_align_path: every pointer a DEVICE pointer; needs no weights and no encode; returns after
+ * enqueueing; not among the timed kernel classes and never replayed as a hipGraph.  One launch
+ * (csrc/align.hip): a workgroup takes 4 adjacent utterances (16 contiguous bytes of a cell; 16 utterances,
+ * the whole 64-byte run, measured 0.143 against 0.126 ms at B = 256: DESIGN.md 3.9), one wave each; per row it loads
+ * the [T][4] tile, quantises and transposes it into LDS as int16, and each
+ * wave scans its row in chunks of 64 frames with a prefix sum and a prefix maximum across lanes (the
+ * stay move is a scan along t: with E the best of diagonal and vertical and P the row's prefix sum of
+ * q, D[l][t] = P[t] + max_{s <= t} (E[s] - P[s - 1]); integers make both scans associative).  Two D
+ * rows and the 2-bit moves of all L x Tp cells stay in LDS (no workspace in memory): 16 Tp/64 bytes per
+ * row, 3.3 KB per utterance at L = 41, Tp = 266; one lane walks them back.  Where the utterances of a
+ * workgroup do not fit the 160 KB of a CU it takes half as many, down to 1 (CASR_OPT_ALIGN_GROUP asks
+ * for 1, 2, 4, 8 or 16).
+ * CASR_ALIGN_MAX_TP: at L = 512 and one utterance per workgroup the move bits (128 Tp bytes), the D
+ * rows (8 Tp) and the tiles (4 Tp) fit 160 KB up to Tp = 1152; 1024 is the power of two below it (30.7 s
+ * of audio).  The int32 bound is far: 3072 (512 + 2 x 1024) = 7.9 million, against the sentinel 2^30.
+ * CASR_ERR_ARG: a NULL required pointer (or handle), B < 1, Tp < 1, L outside [1, 512];
+ * CASR_ERR_UNSUPPORTED (device entry): Tp > CASR_ALIGN_MAX_TP.  Nothing is launched or written on an
+ * error. */
+#define CASR_ALIGN_MAX_TP 1024
+int casr_align_path_host(const float* align, const int32_t* enc_len, const int32_t* tgt_len, int B, int Tp,
+                         int L, int32_t* first, int32_t* last, int32_t* peak, int32_t* path_score);
+int casr_align_path(casr_handle* h, const float* align, const int32_t* enc_len, const int32_t* tgt_len, int B,
+                    int Tp, int L, int32_t* first, int32_t* last, int32_t* peak, int32_t* path_score,
+                    void* stream);
+
 /* Guard bits raised by the device since the previous casr_device_flags call (read and clear;
  * they accumulate over every encode / decode / log-mel call in between, so one read after a
  * series of calls vouches for all of them; 0 = clean): a data-dependent index out of range (1 token, 2 predecessor row, 4 NaN logit
@@ -790,6 +840,9 @@ int casr_recurrence_mode(const casr_handle* h, int B);
  *                            pair (a record's tokens uniform across the wave, each lane rolling a row
  *                            of D against a record of its own); 0 (default) the plan's choice
  *                            (csrc/edit_plan.h).  The same distances
+ *   CASR_OPT_ALIGN_GROUP     utterances (waves) per workgroup of casr_align_path: 1, 2, 4, 8 or 16; 0
+ *                            (default) the plan's choice (csrc/align_plan.h).  Either
+ *                            is halved until the workgroup's LDS fits a CU.  The same paths
  * Three options select numerics variants instead (the same token ids, floating-point results within
  * the stated tolerances, not bit for bit; tests/test_gpu_parity.py compares each pair):
  *   CASR_OPT_DEC_KSPLIT      1: the greedy folded GEMM at R <= 32 decode rows (BASELINE config 2)
@@ -869,7 +922,8 @@ enum {
   CASR_OPT_GEMM16_LEAN = 17,
   CASR_OPT_ATTN_SPLIT = 18,
   CASR_OPT_MBR_MAP = 19,
-  CASR_OPT_COUNT = 20
+  CASR_OPT_ALIGN_GROUP = 20,
+  CASR_OPT_COUNT = 21
 };
 int casr_set_option(casr_handle* h, int option, int value);
 int casr_get_option(const casr_handle* h, int option, int32_t* value_host);
