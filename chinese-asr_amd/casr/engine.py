@@ -470,6 +470,85 @@ class Engine:
         _lib.check(self.lib.casr_beam_mbr_distances(self.handle, _ptr(dist), _ptr(n_rec), _stream()), self.handle)
         return dist, n_rec
 
+    def beam_nbest(self, N, lm=None, lm_weight=0.0, length_weight=0.0, rec_lm=None):
+        """The N best finished hypotheses of the last beam() by the second pass's combined score c, on the
+        device (casr_beam_nbest).  With ``lm`` (a casr.ngram.NgramLM) the rescore runs first for the records'
+        LM scores; ``rec_lm`` hands in the array an earlier rescore returned instead.  Returns index [B, N]
+        (step k + rank, -1 past the record count), tokens [B, N, max_len] (-1 past each length), length
+        [B, N] and comb [B, N] float64."""
+        B, L = self._B, self.cfg.max_len
+        dev = self.device
+        if lm is not None and rec_lm is None:
+            rec_lm = self.beam_rescore(lm, lm_weight, length_weight, records=True)["rec_lm"]
+        N = int(N)
+        index = torch.empty(B, max(N, 0), dtype=torch.int32, device=dev)
+        toks = torch.empty(B, max(N, 0), L, dtype=torch.int32, device=dev)
+        ln = torch.empty(B, max(N, 0), dtype=torch.int32, device=dev)
+        comb = torch.empty(B, max(N, 0), dtype=torch.float64, device=dev)
+        _lib.check(self.lib.casr_beam_nbest(self.handle, N, _ptr(rec_lm), float(lm_weight if rec_lm is not None else 0.0),
+                                            float(length_weight), _ptr(index), _ptr(toks), _ptr(ln), _ptr(comb),
+                                            _stream()), self.handle)
+        self._keep_nbest = (rec_lm,)  # read by the enqueued kernel
+        return dict(index=index, tokens=toks, length=ln, comb=comb, rec_lm=rec_lm)
+
+    def beam_confusion(self, M=4, scale=1.0, lm=None, lm_weight=0.0, length_weight=0.0, pivot=None, rec_lm=None,
+                       units=False):
+        """The confusion network of the last beam()'s finished hypotheses around a pivot, on the device
+        (casr_beam_confusion): per slot of the pivot (odd: its characters, even: the gaps) the M tokens with
+        the largest posterior mass under exp(scale (c - c_max)) in units of 2^-32.  ``pivot`` [B] flat
+        indices step k + rank (None: the record with the largest c; -1: none).  LM arguments as
+        beam_nbest.  Returns n_slots [B], slot_token [B, 2 max_len + 1, M] (casr.lib.CN_EPS = -1 nothing,
+        CN_NONE = -2 unused), slot_mass of the same shape int64, pivot_mass [B, max_len] int64, total [B]
+        int64, and with ``units`` rec_unit [B, max_len, k] int64."""
+        B, L, k = self._B, self.cfg.max_len, self._k
+        dev = self.device
+        if lm is not None and rec_lm is None:
+            rec_lm = self.beam_rescore(lm, lm_weight, length_weight, records=True)["rec_lm"]
+        if pivot is not None:
+            pivot = torch.as_tensor(pivot).to(dev, torch.int32).contiguous()
+            if pivot.shape != (B,):
+                raise ValueError(f"beam_confusion: pivot must be [B={B}]")
+        M = int(M)
+        n_slots = torch.empty(B, dtype=torch.int32, device=dev)
+        st = torch.empty(B, 2 * L + 1, max(M, 0), dtype=torch.int32, device=dev)
+        sm = torch.empty(B, 2 * L + 1, max(M, 0), dtype=torch.int64, device=dev)
+        pm = torch.empty(B, L, dtype=torch.int64, device=dev)
+        total = torch.empty(B, dtype=torch.int64, device=dev)
+        ru = torch.empty(B, L, k, dtype=torch.int64, device=dev) if units else None
+        _lib.check(self.lib.casr_beam_confusion(self.handle, M, float(scale), _ptr(rec_lm),
+                                                float(lm_weight if rec_lm is not None else 0.0), float(length_weight),
+                                                _ptr(pivot), _ptr(n_slots), _ptr(st), _ptr(sm), _ptr(pm), _ptr(total),
+                                                _ptr(ru), _stream()), self.handle)
+        self._keep_cn = (rec_lm, pivot)  # read by the enqueued kernels
+        return dict(n_slots=n_slots, slot_token=st, slot_mass=sm, pivot_mass=pm, total=total, rec_unit=ru,
+                    rec_lm=rec_lm)
+
+    def confusion(self, rec_tokens, rec_valid, rec_unit, pivot, vocab, M=4):
+        """casr.lib.confusion_host's operation on the device (casr_confusion): rec_tokens [B, L, k, L]
+        int32, rec_valid [B, L, k], rec_unit [B, L, k] int64, pivot [B] -> the same dict, of device tensors,
+        value for value.  L <= 255, k <= 16.  Needs no weights and no encode; returns after enqueueing."""
+        dev = self.device
+        rt = torch.as_tensor(rec_tokens).to(dev, torch.int32).contiguous()
+        if rt.dim() != 4 or rt.shape[1] != rt.shape[3]:
+            raise ValueError("confusion: rec_tokens must be [B, L, k, L]")
+        B, L, k = rt.shape[:3]
+        rv = torch.as_tensor(rec_valid).to(dev, torch.uint8).contiguous()
+        ru = torch.as_tensor(rec_unit).to(dev, torch.int64).contiguous()
+        pv = torch.as_tensor(pivot).to(dev, torch.int32).contiguous()
+        if rv.shape != (B, L, k) or ru.shape != (B, L, k) or pv.shape != (B,):
+            raise ValueError("confusion: rec_valid and rec_unit must be [B, L, k] and pivot [B]")
+        M = int(M)
+        n_slots = torch.empty(B, dtype=torch.int32, device=dev)
+        st = torch.empty(B, 2 * L + 1, max(M, 0), dtype=torch.int32, device=dev)
+        sm = torch.empty(B, 2 * L + 1, max(M, 0), dtype=torch.int64, device=dev)
+        pm = torch.empty(B, L, dtype=torch.int64, device=dev)
+        total = torch.empty(B, dtype=torch.int64, device=dev)
+        _lib.check(self.lib.casr_confusion(self.handle, _ptr(rt), _ptr(rv), _ptr(ru), _ptr(pv), B, L, k, int(vocab), M,
+                                           _ptr(n_slots), _ptr(st), _ptr(sm), _ptr(pm), _ptr(total), _stream()),
+                   self.handle)
+        self._keep_cn = (rt, rv, ru, pv)  # read by the enqueued kernels
+        return dict(n_slots=n_slots, slot_token=st, slot_mass=sm, pivot_mass=pm, total=total)
+
     def score(self, targets, tgt_len, alignment=False, best=False, mean=False):
         """Teacher-forced pass over the last encode (casr_score): targets [B, L] int (1 <= L <=
         max_len), tgt_len [B] scored positions per utterance.  Returns token_logp [B, L] (0 past

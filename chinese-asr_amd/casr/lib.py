@@ -32,6 +32,8 @@ EXPORTS = [
     "casr_bias_create", "casr_bias_destroy", "casr_bias_score_host", "casr_bias_score", "casr_bias_rows_host",
     "casr_bias_rows", "casr_beam_bias", "casr_beam_record_bias",
     "casr_align_path_host", "casr_align_path",
+    "casr_posterior_units_host", "casr_nbest_host", "casr_confusion_host", "casr_confusion", "casr_beam_nbest",
+    "casr_beam_confusion",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -161,6 +163,13 @@ def load(path=None, variant=None):
         "casr_beam_record_bias": (i32, [vp, vp, vp]),
         "casr_align_path_host": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "casr_align_path": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "casr_posterior_units_host": (i32, [vp, vp, vp, i32, i32, i32] + [ctypes.c_double] * 3 + [vp, vp]),
+        "casr_nbest_host": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp]),
+        "casr_confusion_host": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "casr_confusion": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "casr_beam_nbest": (i32, [vp, i32, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp]),
+        "casr_beam_confusion": (i32, [vp, i32, ctypes.c_double, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp,
+                                      vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -284,6 +293,8 @@ def pack_weights(cfg, enc_sd, dec_sd):
 EDIT_MAX_LEN = 512  # include/casr.h CASR_EDIT_MAX_LEN: the longest row of the device entry
 BIAS_MAX_LEN = 16   # include/casr.h CASR_BIAS_MAX_LEN: the longest phrase
 ALIGN_MAX_TP = 1024  # include/casr.h CASR_ALIGN_MAX_TP: the longest row of casr_align_path
+CN_EPS, CN_NONE = -1, -2  # include/casr.h CASR_CN_EPS, CASR_CN_NONE: "nothing here", an unused entry
+CN_MAX_M, NBEST_MAX_N = 8, 64  # include/casr.h CASR_CN_MAX_M, CASR_NBEST_MAX_N
 
 
 def _i32(a, shape=None):
@@ -351,3 +362,75 @@ def align_path_host(align, enc_len, tgt_len):
     check(lib.casr_align_path_host(p(align), p(enc_len), p(tgt_len), B, Tp, L, p(first), p(last), p(peak), p(score)),
           lib=lib)
     return dict(first=first, last=last, peak=peak, path_score=score)
+
+
+def _records(who, rec_tokens, rec_valid, *others):
+    """rec_tokens [B, L, k, L] int32, rec_valid and every other given array [B, L, k]."""
+    rt = np.ascontiguousarray(rec_tokens, dtype=np.int32)
+    B, L, k = rt.shape[:3]
+    if rt.shape != (B, L, k, L):
+        raise ValueError(f"{who}: rec_tokens must be [B, L, k, L]")
+    out = [rt, np.ascontiguousarray(rec_valid, dtype=np.uint8)]
+    out += [None if x is None else np.ascontiguousarray(x, dtype=dt) for x, dt in others]
+    for x in out[1:]:
+        if x is not None and x.shape != (B, L, k):
+            raise ValueError(f"{who}: rec_valid and the other record arrays must be [B, L, k]")
+    return (B, L, k), out
+
+
+def _p(x):
+    return x.ctypes.data_as(ctypes.c_void_p) if x is not None and x.size else None
+
+
+def posterior_units_host(rec_score, rec_valid, scale, rec_lm=None, lm_weight=0.0, length_weight=0.0):
+    """casr_posterior_units_host on the arrays casr_beam_records writes: rec_score, rec_valid and rec_lm
+    (or None) [B, L, k] -> (rec_unit [B, L, k] int64 = floor(exp(scale (c - c_max)) 2^32), 0 where there is
+    no record, total [B] int64).  Host only, no GPU."""
+    lib = load()
+    rs = np.ascontiguousarray(rec_score, dtype=np.float32)
+    rv = np.ascontiguousarray(rec_valid, dtype=np.uint8)
+    rl = None if rec_lm is None else np.ascontiguousarray(rec_lm, dtype=np.float32)
+    if rs.ndim != 3 or rv.shape != rs.shape or (rl is not None and rl.shape != rs.shape):
+        raise ValueError("posterior_units_host: rec_score, rec_valid and rec_lm must be [B, L, k]")
+    B, L, k = rs.shape
+    unit = np.zeros((B, L, k), np.int64)
+    total = np.zeros(B, np.int64)
+    check(lib.casr_posterior_units_host(_p(rs), _p(rv), _p(rl), B, L, k, float(scale), float(lm_weight),
+                                        float(length_weight), _p(unit), _p(total)), lib=lib)
+    return unit, total
+
+
+def nbest_host(rec_tokens, rec_score, rec_valid, N, rec_lm=None, lm_weight=0.0, length_weight=0.0):
+    """casr_nbest_host: the N records with the largest c per utterance -> dict of index [B, N] (step k +
+    rank, -1 past the record count), tokens [B, N, L] (-1 past each length), length [B, N] and comb
+    [B, N] float64.  Host only, no GPU."""
+    lib = load()
+    (B, L, k), (rt, rv, rs, rl) = _records("nbest_host", rec_tokens, rec_valid, (rec_score, np.float32),
+                                           (rec_lm, np.float32))
+    N = int(N)
+    index = np.full((B, N), -1, np.int32)
+    toks = np.full((B, N, L), -1, np.int32)
+    ln = np.zeros((B, N), np.int32)
+    comb = np.zeros((B, N), np.float64)
+    check(lib.casr_nbest_host(_p(rt), _p(rs), _p(rv), _p(rl), B, L, k, N, float(lm_weight), float(length_weight),
+                              _p(index), _p(toks), _p(ln), _p(comb)), lib=lib)
+    return dict(index=index, tokens=toks, length=ln, comb=comb)
+
+
+def confusion_host(rec_tokens, rec_valid, rec_unit, pivot, vocab, M=4):
+    """casr_confusion_host: the confusion network of every utterance's records around its pivot (a flat
+    index step k + rank, [B]) under the given units rec_unit [B, L, k] int64 -> dict of n_slots [B],
+    slot_token [B, 2 L + 1, M] int32 (CN_EPS = -1: nothing, CN_NONE = -2: unused), slot_mass of the same
+    shape int64, pivot_mass [B, L] int64 and total [B] int64.  Host only, no GPU."""
+    lib = load()
+    (B, L, k), (rt, rv, ru) = _records("confusion_host", rec_tokens, rec_valid, (rec_unit, np.int64))
+    pv = _i32(pivot, (B,))
+    M = int(M)
+    n_slots = np.zeros(B, np.int32)
+    st = np.full((B, 2 * L + 1, max(M, 0)), CN_NONE, np.int32)
+    sm = np.zeros((B, 2 * L + 1, max(M, 0)), np.int64)
+    pm = np.zeros((B, L), np.int64)
+    total = np.zeros(B, np.int64)
+    check(lib.casr_confusion_host(_p(rt), _p(rv), _p(ru), _p(pv), B, L, k, int(vocab), M, _p(n_slots), _p(st), _p(sm),
+                                  _p(pm), _p(total)), lib=lib)
+    return dict(n_slots=n_slots, slot_token=st, slot_mass=sm, pivot_mass=pm, total=total)

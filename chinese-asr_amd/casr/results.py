@@ -13,6 +13,36 @@ import numpy as np
 EvalOutput = namedtuple('EvalOutput', ('pred_text', 'score', 'text', 'wer', 'n', 'alignment',
                                        'audio_feat_len', 'text_len', 'timing'), defaults=(None,))
 EncoderOutput = namedtuple('EncoderOutput', ('out', 'out_lens', 'state'))
+
+
+class BeamEvalOutput(EvalOutput):
+    """An EvalOutput (the same nine fields, unpacking the same) of eval_one_batch_with_beam called with
+    ``nbest`` or ``alternatives``, carrying two attributes more: ``nbest``, per utterance [(text, comb)]
+    best first, and ``alternatives``, per utterance confusion_slots' list of slots (each None when it was
+    not asked for).  An utterance that finished no hypothesis has [] in both.  Built like an EvalOutput,
+    the two attributes by keyword; pickle, copy and _replace keep them."""
+    nbest = None
+    alternatives = None
+
+    def __new__(cls, *fields, nbest=None, alternatives=None, **named):
+        self = super().__new__(cls, *fields, **named)
+        self.nbest = nbest
+        self.alternatives = alternatives
+        return self
+
+    def __reduce__(self):
+        return _beam_eval_output, (tuple(self), self.nbest, self.alternatives)
+
+    def _replace(self, **kwds):
+        nbest = kwds.pop('nbest', self.nbest)
+        alternatives = kwds.pop('alternatives', self.alternatives)
+        return type(self)(*EvalOutput._replace(EvalOutput._make(self), **kwds), nbest=nbest, alternatives=alternatives)
+
+
+def _beam_eval_output(fields, nbest, alternatives):
+    return BeamEvalOutput(*fields, nbest=nbest, alternatives=alternatives)
+
+
 DecoderOutput = namedtuple('DecoderOutput', ('logit', 'attn_hidden_state', 'alignment', 'cell_state'))
 # Model.score_one_batch (teacher-forced scoring; no reference counterpart)
 ScoreOutput = namedtuple('ScoreOutput', ('token_logp', 'score', 'loss', 'best_text', 'times', 'token_loss', 'ids',
@@ -323,4 +353,29 @@ def token_spans(first, last, peak, token_logp, tgt_len, sample_rate=16000, n_tok
         n = min(int(n_tokens[b]), int(tgt_len[b]), first.shape[1])
         out.append([(float(first[b, l] * sec), float((last[b, l] + 1) * sec), float(peak[b, l] * sec),
                      float(np.exp(token_logp[b, l]))) for l in range(n) if first[b, l] >= 0])
+    return out
+
+
+def confusion_slots(slot_token, slot_mass, n_slots, total, int2word, min_gap=0.05):
+    """The confusion network of Engine.beam_confusion / casr.lib.confusion_host (host numpy arrays) as
+    lists: per utterance a list of slots in the pivot's order, each slot [(char, prob)] by falling
+    posterior, prob = mass / U and '' for "nothing here" (EPS).  Every slot of a pivot character is kept;
+    a gap slot only where the mass of its tokens other than EPS is at least ``min_gap`` U.  That mass is
+    exact where EPS is among the M listed entries or fewer than M are listed.  Else EPS weighs at most the
+    last listed entry, and the larger of the listed sum and U less that entry stands for it, a lower bound:
+    such a gap (M or more distinct inserts, each outweighing EPS) can be dropped though its tokens together
+    reach ``min_gap`` U; a larger M lists EPS.  An utterance without a pivot gives []."""
+    out = []
+    for b in range(len(n_slots)):
+        U = int(total[b])
+        slots = []
+        for s in range(int(n_slots[b])):
+            ent = [(int(t), int(w)) for t, w in zip(slot_token[b, s], slot_mass[b, s]) if t != -2 and w > 0]
+            if s % 2 == 0:
+                eps = [w for t, w in ent if t == -1]
+                other = U - eps[0] if eps else max(sum(w for _, w in ent), U - ent[-1][1]) if ent else 0
+                if not ent or other <= 0 or other < min_gap * U:
+                    continue
+            slots.append([('' if t == -1 else int2word[t], w / U) for t, w in ent])
+        out.append(slots)
     return out

@@ -13,6 +13,7 @@
 #include "casr.h"
 #include "align_plan.h"
 #include "casr_internal.h"
+#include "confusion_plan.h"
 #include "edit_plan.h"
 
 namespace casr {
@@ -222,6 +223,7 @@ struct casr_handle {
   float beam_lm_weight = 0.f, beam_length_weight = 0.f;  // the last casr_beam's (casr_beam_rescore's fallback)
   DevBuf mbrws;           // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
   bool mbr_done = false;  // mbrws holds the distances of the last beam's records
+  DevBuf cnws;            // casr_confusion, casr_beam_nbest, casr_beam_confusion: lists, units, votes (carve_confusion)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
   // fallback does.  Default 2: the decode loop launches eagerly (measured faster)
@@ -598,7 +600,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->biasws})
+                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->biasws, &h->cnws})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1595,6 +1597,130 @@ int casr_beam_mbr_distances(casr_handle* h, uint8_t* dist, int32_t* n_rec, void*
   MbrBufs w{};
   carve_mbr(h->mbrws.p, c.a.B, c.a.max_len, c.a.k, w);
   HIP_OK(h, run_mbr_distances(c.a, w, dist, n_rec, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_posterior_units_host(const float* rec_score, const uint8_t* rec_valid, const float* rec_lm, int B,
+                              int max_len, int k, double scale, double lm_weight, double length_weight,
+                              int64_t* rec_unit, int64_t* total) {
+  if (B < 0 || max_len < 1 || k < 1 || (B > 0 && (!rec_score || !rec_valid || !rec_unit)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_posterior_units_host: NULL argument, B < 0, or max_len or k < 1");
+  if (!(scale >= 0.0) || !std::isfinite(scale))
+    return fail(nullptr, CASR_ERR_ARG, "casr_posterior_units_host: scale %g is negative or not finite", scale);
+  const size_t LK = (size_t)max_len * k;
+  for (int b = 0; b < B; ++b) {
+    const int64_t U = cn_units_utterance_host(rec_score + b * LK, rec_valid + b * LK, rec_lm ? rec_lm + b * LK : nullptr,
+                                              max_len, k, scale, lm_weight, length_weight, rec_unit + b * LK);
+    if (total) total[b] = U;
+  }
+  return CASR_OK;
+}
+
+int casr_nbest_host(const int32_t* rec_tokens, const float* rec_score, const uint8_t* rec_valid,
+                    const float* rec_lm, int B, int max_len, int k, int N, double lm_weight, double length_weight,
+                    int32_t* nbest_index, int32_t* nbest_tokens, int32_t* nbest_len, double* nbest_comb) {
+  if (B < 0 || max_len < 1 || k < 1 ||
+      (B > 0 && (!rec_tokens || !rec_score || !rec_valid || !nbest_index || !nbest_tokens || !nbest_len || !nbest_comb)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_nbest_host: NULL argument, B < 0, or max_len or k < 1");
+  if (N < 1 || N > CN_MAX_N) return fail(nullptr, CASR_ERR_ARG, "casr_nbest_host: N = %d not in [1, %d]", N, CN_MAX_N);
+  const size_t LK = (size_t)max_len * k;
+  for (int b = 0; b < B; ++b)
+    cn_nbest_utterance_host(rec_tokens + b * LK * max_len, rec_score + b * LK, rec_valid + b * LK,
+                            rec_lm ? rec_lm + b * LK : nullptr, max_len, k, N, lm_weight, length_weight,
+                            nbest_index + (size_t)b * N, nbest_tokens + (size_t)b * N * max_len,
+                            nbest_len + (size_t)b * N, nbest_comb + (size_t)b * N);
+  return CASR_OK;
+}
+
+int casr_confusion_host(const int32_t* rec_tokens, const uint8_t* rec_valid, const int64_t* rec_unit,
+                        const int32_t* pivot, int B, int max_len, int k, int vocab, int M, int32_t* n_slots,
+                        int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total) {
+  if (B < 0 || max_len < 1 || k < 1 || vocab < 1 ||
+      (B > 0 && (!rec_tokens || !rec_valid || !rec_unit || !pivot || !n_slots || !slot_token || !slot_mass ||
+                 !pivot_mass || !total)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_confusion_host: NULL argument, B < 0, or max_len, k or vocab < 1");
+  if (M < 1 || M > CN_MAX_M) return fail(nullptr, CASR_ERR_ARG, "casr_confusion_host: M = %d not in [1, %d]", M, CN_MAX_M);
+  const size_t LK = (size_t)max_len * k, SM = (size_t)cn_slots(max_len);
+  for (int b = 0; b < B; ++b)
+    n_slots[b] = cn_confusion_utterance_host(rec_tokens + b * LK * max_len, rec_valid + b * LK, rec_unit + b * LK,
+                                             pivot[b], max_len, k, vocab, M, slot_token + b * SM * M,
+                                             slot_mass + b * SM * M, pivot_mass + (size_t)b * max_len, total + b);
+  return CASR_OK;
+}
+
+int casr_confusion(casr_handle* h, const int32_t* rec_tokens, const uint8_t* rec_valid, const int64_t* rec_unit,
+                   const int32_t* pivot, int B, int max_len, int k, int vocab, int M, int32_t* n_slots,
+                   int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total, void* stream) {
+  if (!h || !rec_tokens || !rec_valid || !rec_unit || !pivot || !n_slots || !slot_token || !slot_mass || !pivot_mass ||
+      !total || B < 1 || B > 65535 || max_len < 1 || k < 1 || vocab < 1)
+    return fail(h, CASR_ERR_ARG, "casr_confusion: NULL argument, B outside [1, 65535], or max_len, k or vocab < 1");
+  if (M < 1 || M > CN_MAX_M) return fail(h, CASR_ERR_ARG, "casr_confusion: M = %d not in [1, %d]", M, CN_MAX_M);
+  if (!confusion_supported(B, max_len, k, vocab, false))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_confusion: max_len %d (<= %d), k %d (<= %d), vocab %d (<= %d) and the masses must fit the LDS",
+                max_len, CN_MAX_LEN, k, CN_MAX_K, vocab, CN_MAX_VOCAB);
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_confusion: no guard words");
+  CnBufs w{};
+  HIP_OK(h, h->cnws.ensure(carve_confusion(nullptr, B, max_len, k, true, w)));
+  carve_confusion(h->cnws.p, B, max_len, k, true, w);
+  HIP_OK(h, run_confusion(w, rec_tokens, rec_valid, rec_unit, pivot, B, max_len, k, vocab, M, n_slots, slot_token,
+                          slot_mass, pivot_mass, total, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+// the refusals casr_beam_nbest and casr_beam_confusion share with casr_beam_mbr
+static int beam_records_readable(casr_handle* h, const char* who) {
+  if (!h->beam_done) return fail(h, CASR_ERR_STATE, "%s before casr_beam", who);
+  if (h->beam_lm_done || h->beam_bias_done)
+    return fail(h, CASR_ERR_STATE, "%s after casr_beam_lm or casr_beam_bias: c is the comb of a casr_beam's records", who);
+  if (h->cfg.max_len > CN_MAX_LEN)
+    return fail(h, CASR_ERR_UNSUPPORTED, "%s: max_len %d (<= %d)", who, h->cfg.max_len, CN_MAX_LEN);
+  return CASR_OK;
+}
+
+int casr_beam_nbest(casr_handle* h, int N, const float* rec_lm, double lm_weight, double length_weight,
+                    int32_t* nbest_index, int32_t* nbest_tokens, int32_t* nbest_len, double* nbest_comb,
+                    void* stream) {
+  if (!h || !nbest_index || !nbest_tokens || !nbest_len || !nbest_comb)
+    return fail(h, CASR_ERR_ARG, "casr_beam_nbest: NULL handle or output");
+  if (N < 1 || N > CN_MAX_N) return fail(h, CASR_ERR_ARG, "casr_beam_nbest: N = %d not in [1, %d]", N, CN_MAX_N);
+  int rc = beam_records_readable(h, "casr_beam_nbest");
+  if (rc) return rc;
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  if (rc) return rc;
+  CnBufs w{};
+  HIP_OK(h, h->cnws.ensure(carve_confusion(nullptr, c.a.B, c.a.max_len, c.a.k, false, w)));
+  carve_confusion(h->cnws.p, c.a.B, c.a.max_len, c.a.k, false, w);
+  HIP_OK(h, run_beam_nbest(c.a, h->d, w, N, rec_lm, lm_weight, length_weight, nbest_index, nbest_tokens, nbest_len,
+                           nbest_comb, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_beam_confusion(casr_handle* h, int M, double scale, const float* rec_lm, double lm_weight,
+                        double length_weight, const int32_t* pivot, int32_t* n_slots, int32_t* slot_token,
+                        int64_t* slot_mass, int64_t* pivot_mass, int64_t* total, int64_t* rec_unit, void* stream) {
+  if (!h || !n_slots || !slot_token || !slot_mass || !pivot_mass || !total)
+    return fail(h, CASR_ERR_ARG, "casr_beam_confusion: NULL handle or output");
+  if (M < 1 || M > CN_MAX_M) return fail(h, CASR_ERR_ARG, "casr_beam_confusion: M = %d not in [1, %d]", M, CN_MAX_M);
+  if (!(scale >= 0.0) || !std::isfinite(scale))
+    return fail(h, CASR_ERR_ARG, "casr_beam_confusion: scale %g is negative or not finite", scale);
+  int rc = beam_records_readable(h, "casr_beam_confusion");
+  if (rc) return rc;
+  // the network's own limits (casr_beam_nbest has none of them)
+  if (!confusion_supported(h->B, h->cfg.max_len, h->dec_k, h->cfg.vocab, true))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_confusion: k %d, vocab %d (<= %d): votes are int16 and the masses must fit the LDS",
+                h->dec_k, h->cfg.vocab, CN_MAX_VOCAB);
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  if (rc) return rc;
+  CnBufs w{};
+  HIP_OK(h, h->cnws.ensure(carve_confusion(nullptr, c.a.B, c.a.max_len, c.a.k, true, w)));
+  carve_confusion(h->cnws.p, c.a.B, c.a.max_len, c.a.k, true, w);
+  HIP_OK(h, run_beam_confusion(c.a, h->d, w, M, scale, rec_lm, lm_weight, length_weight, pivot, n_slots, slot_token,
+                               slot_mass, pivot_mass, total, rec_unit, (hipStream_t)stream));
   return CASR_OK;
 }
 

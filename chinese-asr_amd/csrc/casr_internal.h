@@ -604,6 +604,31 @@ hipError_t run_beam_mbr(const DecodeArgs& a, const DecodeBufs& d, const MbrBufs&
                         int32_t* best_index, double* best_risk, double* rec_risk, hipStream_t s);
 hipError_t run_mbr_distances(const DecodeArgs& a, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s);
 
+// confusion.hip: N-best lists and confusion networks over a beam's records (confusion_plan.h).
+// The handle-owned workspace; positions are those in an utterance's list
+struct CnBufs {
+  double* c;       // [B][L k] comb of the utterance's valid records, in list order
+  int64_t* unit;   // [B][L k] their posterior units
+  int32_t* list;   // [B][L k] their flat indices step k + rank, ascending
+  int32_t* count;  // [B]
+  int32_t* ppos;   // [B] the pivot's position in the list, -1 without one
+  int32_t* ptok;   // [B][L] the pivot's tokens
+  int16_t* votes;  // [B][2 L + 1][L k] slot-major (null: an N-best call)
+};
+size_t carve_confusion(void* base, int B, int L, int k, bool votes, CnBufs& w);
+bool confusion_supported(int B, int max_len, int k, int V, bool tree);
+hipError_t run_beam_nbest(const DecodeArgs& a, const DecodeBufs& d, const CnBufs& w, int N, const float* rec_lm,
+                          double lm_weight, double length_weight, int32_t* nbest_index, int32_t* nbest_tokens,
+                          int32_t* nbest_len, double* nbest_comb, hipStream_t s);
+hipError_t run_beam_confusion(const DecodeArgs& a, const DecodeBufs& d, const CnBufs& w, int M, double scale,
+                              const float* rec_lm, double lm_weight, double length_weight, const int32_t* pivot,
+                              int32_t* n_slots, int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass,
+                              int64_t* total, int64_t* rec_unit, hipStream_t s);
+hipError_t run_confusion(const CnBufs& w, const int32_t* rec_tokens, const uint8_t* rec_valid, const int64_t* rec_unit,
+                         const int32_t* pivot, int B, int L, int k, int V, int M, int32_t* n_slots,
+                         int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total, int32_t* err,
+                         hipStream_t s);
+
 // ---- align.hip: the monotone path through align [L][Tp][B] (align_plan.h); group: CASR_OPT_ALIGN_GROUP
 hipError_t launch_align_path(const float* align, const int32_t* enc_len, const int32_t* tgt_len, int B, int Tp, int L,
                              int group, int32_t* first, int32_t* last, int32_t* peak, int32_t* path_score,

@@ -14,8 +14,9 @@ from casr.config import config_from_gpd
 from casr.engine import Engine
 from casr.lib import pack_weights
 from casr.ngram import NgramLM
-from casr.results import (EvalOutput, ScoreOutput, encode_targets, get_wer, greedy_outputs, greedy_steps,
-                          label_smoothed_loss, score_outputs, second_pass_arrays, token_spans, token_times, wer_batch)
+from casr.results import (BeamEvalOutput, EvalOutput, ScoreOutput, confusion_slots, encode_targets, get_wer,
+                          greedy_outputs, greedy_steps, label_smoothed_loss, score_outputs, second_pass_arrays,
+                          token_spans, token_times, wer_batch)
 from casr.vocab import load_vocab
 from casr.weights import check_state_dicts, load_checkpoint, save_checkpoint, synthetic_state_dicts
 
@@ -175,7 +176,8 @@ class Model(object):
     def eval_one_batch_with_beam(self, device, bmsz, data, lens, text, int2word,
                                  second_pass=gpd['second_pass'], lm_model=None,
                                  lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight'], fusion=False,
-                                 mbr=None, bias=None, bias_weight=1.0, timestamps=False):
+                                 mbr=None, bias=None, bias_weight=1.0, timestamps=False, nbest=None, alternatives=None,
+                                 posterior_scale=1.0):
         """model.py:604-987.  ``fusion`` (this path's own addition, default off): with an NgramLM as
         ``lm_model`` the LM is fused into the first pass on the device (casr_beam_lm: every candidate
         ranked by logp + lm_weight lm + length_weight (l + 1), the ranking model.py:843-857 was designed
@@ -198,8 +200,27 @@ class Model(object):
         ``timestamps`` (this path's own addition, default off: nothing else is launched): ``timing`` as
         eval_one_batch_with_greedy fills it, for the hypothesis that was chosen, whatever chose it.  The
         device-only modes score it inside the guarded decode; after a host second pass the scoring runs
-        once the host has chosen, on the encode the handle still holds, and the guard bits are read again."""
+        once the host has chosen, on the encode the handle still holds, and the guard bits are read again.
+        ``nbest`` (this path's own addition, default None: off): N in 1..64, the N best finished
+        hypotheses per utterance by the combined score c (casr_beam_nbest).  ``alternatives`` (default
+        None: off): M in 1..8, per character of the answer, and per gap where something else was likely,
+        the M most probable competitors under the posterior exp(posterior_scale (c - c_max)) over the
+        finished hypotheses (casr_beam_confusion, a confusion network around the answer).  With either the
+        result is a casr.results.BeamEvalOutput: the same nine fields and the attributes ``nbest`` and
+        ``alternatives``.  c is what chose the answer: logp alone after a plain first pass, the second pass's
+        combined score with an NgramLM and ``second_pass``, ``mbr``'s c with ``mbr`` (the pivot is then the
+        MBR choice).  An lm_model that is no NgramLM cannot be read on the device: TypeError; together with
+        ``fusion`` or ``bias``: ValueError (both read the records of a plain beam through its scores).  As
+        with ``mbr``, no host second pass runs under either keyword: ``second_pass`` with ``lm_model`` None
+        keeps the first pass's choice and does not raise the reference's AttributeError."""
         self.model.eval()
+        extras = nbest is not None or alternatives is not None
+        if extras:
+            if bias is not None or fusion:
+                raise ValueError("nbest and alternatives exclude bias and fusion: they read the records of a plain beam")
+            if lm_model is not None and not isinstance(lm_model, NgramLM):
+                raise TypeError("nbest and alternatives need a casr.ngram.NgramLM as lm_model (or None), got "
+                                f"{type(lm_model).__name__}")
         if bias is not None:
             if mbr is not None:
                 raise ValueError("bias and mbr exclude each other: the MBR choice reads the records of a plain beam")
@@ -226,14 +247,24 @@ class Model(object):
         # an NgramLM (casr/ngram.py) is rescored on the device from the beam tree: no record copy and
         # no host pass; any other lm_model keeps the host second pass below
         on_device = bool(second_pass) and isinstance(lm_model, NgramLM)
-        host_pass = bool(second_pass) and not on_device and mbr is None
+        host_pass = bool(second_pass) and not on_device and mbr is None and not extras
 
         def decode():
             r = self.engine.beam(bmsz, lm_weight, length_weight)
             if mbr is not None:
                 r = self.engine.beam_mbr(mbr, lm_model if on_device else None, lm_weight, length_weight)
             elif on_device:
-                r = self.engine.beam_rescore(lm_model, lm_weight, length_weight)
+                r = self.engine.beam_rescore(lm_model, lm_weight, length_weight, records=extras)
+            if extras:
+                # c as the answer was chosen by it: mbr's and the rescore's comb, else the first pass's score
+                weighted = mbr is not None or on_device
+                kw = dict(rec_lm=r.get('rec_lm'), lm_weight=lm_weight if weighted else 0.0,
+                          length_weight=length_weight if weighted else 0.0)
+                if nbest is not None:
+                    r['nbest'] = self.engine.beam_nbest(nbest, **kw)
+                if alternatives is not None:
+                    r['confusion'] = self.engine.beam_confusion(alternatives, posterior_scale,
+                                                                pivot=r['index'] if mbr is not None else None, **kw)
             return self._with_timing(r, timestamps and not host_pass)
 
         bsz, _, r = self._run(data, lens, decode)
@@ -266,8 +297,19 @@ class Model(object):
         wer = None
         if text is not None:
             wer = np.mean(wer_batch(pred_text, text, engine=self.engine))
-        return EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=None,
-                          audio_feat_len=None, text_len=None, timing=timing)
+        out = EvalOutput(pred_text=pred_text, score=score, text=text, wer=wer, n=bsz, alignment=None,
+                         audio_feat_len=None, text_len=None, timing=timing)
+        if not extras:
+            return out
+        lists = slots = None
+        if nbest is not None:
+            nb = {n: r['nbest'][n].cpu().numpy() for n in ('index', 'tokens', 'length', 'comb')}
+            lists = [[(''.join(i2w[t] for t in nb['tokens'][b, j, :nb['length'][b, j]].tolist()), float(nb['comb'][b, j]))
+                      for j in range(nb['index'].shape[1]) if nb['index'][b, j] >= 0] for b in range(bsz)]
+        if alternatives is not None:
+            cn = {n: r['confusion'][n].cpu().numpy() for n in ('slot_token', 'slot_mass', 'n_slots', 'total')}
+            slots = confusion_slots(cn['slot_token'], cn['slot_mass'], cn['n_slots'], cn['total'], i2w)
+        return BeamEvalOutput(*out, nbest=lists, alternatives=slots)
 
     def _first_pass_output(self, bsz, r, text, int2word):
         """The EvalOutput of a beam whose first pass made the choice (beam_lm, beam_bias)."""

@@ -667,6 +667,78 @@ int casr_beam_mbr(casr_handle* h, double scale, const float* rec_lm, double lm_w
                   double* best_risk, double* rec_risk, void* stream);
 int casr_beam_mbr_distances(casr_handle* h, uint8_t* dist, int32_t* n_rec, void* stream);
 
+/* N-best lists and per-character alternatives (a confusion network, "sausage") over the finished
+ * hypotheses of a beam.  The reference has no counterpart; like the MBR choice the operation is DEFINED
+ * BY THE FORMULAS BELOW (tests/confusion_ref.py restates them in Python).  An utterance has the valid
+ * records r_0 .. r_{n-1} in (step, rank) order, l_i tokens each, and c_i, c_max and w_i as under MBR above
+ * (mbr_comb, mbr_weight: the same uncontracted double operations).
+ *   N-best    the records under the total order: a c that is no NaN before a NaN, then the larger c, then
+ *             the lower flat index.  nbest_index [B][N] the flat index step k + rank, -1 past the record
+ *             count; nbest_tokens [B][N][max_len], -1 past each length (ids as casr_beam_records gives
+ *             them); nbest_len [B][N]; nbest_comb [B][N] double, 0 where there is no record.  N in
+ *             1..CASR_NBEST_MAX_N.  No exp: host and device agree bit for bit.
+ *   Units     u_i = (int64) floor(w_i 2^32), 0 for a NaN w_i; the record at c_max has 2^32.  U = sum u_i
+ *             (below 2^44 at max_len 255, k 16).  Everything after this is integer arithmetic: no result
+ *             depends on a reduction order.  exp is the platform's: a device unit may differ from the
+ *             host's by at most 1, nothing else does.  A unit handed in is clamped into [0, 2^32].
+ *   Votes     the pivot a is one valid record of m tokens: S = 2m + 1 slots, odd slot 2i + 1 pivot
+ *             position i, even slot 2g the gap before position g (2m: after the end).  For every record
+ *             b = r_j the backtrace (Ops above: the same cell rule, the same tie order) of the script
+ *             turning a into b votes: a diagonal or replace at (i, j) b[j-1] at slot 2i - 1; a delete at row
+ *             i EPS at slot 2i - 1; an insert of b[j-1] at row i that token at slot 2i, of several inserts
+ *             into one gap the smallest j; every slot the walk does not touch EPS.  Each record casts one
+ *             vote per slot; the pivot votes its tokens at the odd slots and EPS at the gaps.  A token id
+ *             outside [0, V) is 0 before anything else, the alignment included (device: guard bit 1).
+ *   Slots     mass[s][t] = sum of u_j over the records voting t at slot s; over all t it is U.  Per slot
+ *             the M entries (1..CASR_CN_MAX_M) with mass > 0 by larger mass, then smaller token
+ *             (CASR_CN_EPS = -1 first); unused entries (CASR_CN_NONE, 0).
+ *   n_slots [B] 2m + 1, 0 without a pivot; slot_token [B][2 max_len + 1][M] int32 and slot_mass of the same
+ *   shape int64; pivot_mass [B][max_len] int64 the mass of the pivot's own token at its slot (0 past m);
+ *   total [B] int64 = U; rec_unit [B][max_len][k] int64, 0 where there is no record.  pivot [B] flat
+ *   indices: -1, or the index of no valid record, gives n_slots 0 and NONE / 0 rows (total is still U).
+ * The three *_host entries take HOST pointers, the expanded arrays of casr_beam_records (rec_lm NULL or
+ * [B][max_len][k]) and need no GPU; total may be NULL in casr_posterior_units_host; casr_confusion_host
+ * takes rec_unit as an INPUT.  CASR_ERR_ARG: a NULL required argument, B < 0, max_len or k < 1, vocab < 1,
+ * M or N out of range, a scale that is negative or not finite.
+ * casr_confusion: the same operation on DEVICE arrays, any B >= 1, max_len <= 255, k <= 16, vocab <=
+ * 32767 whose masses fit the LDS (8 (vocab + 1) + 4 max_len k <= 160 KB), else CASR_ERR_UNSUPPORTED.  Needs
+ * no weights and no encode.
+ * casr_beam_nbest and casr_beam_confusion read the beam tree the handle still holds after casr_beam: no
+ * record is expanded in memory, the beam state is only read.  rec_lm NULL or the device array
+ * casr_beam_rescore wrote.  pivot NULL: the top of the N-best order; rec_unit NULL or an output.  A
+ * back-pointer outside [0, k) is clamped (guard bit 16).  Kernels (csrc/confusion.hip): prepare, one
+ * workgroup per utterance (the list, c, u, the ranks by an all-pairs compare, the pivot); align, a lane per
+ * record rolling a byte column of D in LDS against the pivot, its 2-bit directions in LDS, walked back
+ * into int16 votes, slot-major, in a handle-owned workspace [B][2 max_len + 1][max_len k]; reduce, one wave
+ * per slot with an LDS histogram of int64 masses under integer atomics and M rounds of arg-max over the
+ * touched bins.  No float atomics.  Errors as casr_beam_mbr: CASR_ERR_STATE before casr_beam and after
+ * casr_beam_lm or casr_beam_bias until the next casr_beam; CASR_ERR_ARG: a NULL handle or required output,
+ * M or N out of range, a scale that is negative or not finite; CASR_ERR_UNSUPPORTED: max_len > 255 and,
+ * for casr_beam_confusion alone, the vocab or LDS limit above.  Nothing is launched or written on an error; none is replayed as a hipGraph or counted among
+ * the timed kernel classes. */
+#define CASR_CN_EPS (-1)
+#define CASR_CN_NONE (-2)
+#define CASR_CN_MAX_M 8
+#define CASR_NBEST_MAX_N 64
+int casr_posterior_units_host(const float* rec_score, const uint8_t* rec_valid, const float* rec_lm, int B,
+                              int max_len, int k, double scale, double lm_weight, double length_weight,
+                              int64_t* rec_unit, int64_t* total);
+int casr_nbest_host(const int32_t* rec_tokens, const float* rec_score, const uint8_t* rec_valid,
+                    const float* rec_lm, int B, int max_len, int k, int N, double lm_weight, double length_weight,
+                    int32_t* nbest_index, int32_t* nbest_tokens, int32_t* nbest_len, double* nbest_comb);
+int casr_confusion_host(const int32_t* rec_tokens, const uint8_t* rec_valid, const int64_t* rec_unit,
+                        const int32_t* pivot, int B, int max_len, int k, int vocab, int M, int32_t* n_slots,
+                        int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total);
+int casr_confusion(casr_handle* h, const int32_t* rec_tokens, const uint8_t* rec_valid, const int64_t* rec_unit,
+                   const int32_t* pivot, int B, int max_len, int k, int vocab, int M, int32_t* n_slots,
+                   int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total, void* stream);
+int casr_beam_nbest(casr_handle* h, int N, const float* rec_lm, double lm_weight, double length_weight,
+                    int32_t* nbest_index, int32_t* nbest_tokens, int32_t* nbest_len, double* nbest_comb,
+                    void* stream);
+int casr_beam_confusion(casr_handle* h, int M, double scale, const float* rec_lm, double lm_weight,
+                        double length_weight, const int32_t* pivot, int32_t* n_slots, int32_t* slot_token,
+                        int64_t* slot_mass, int64_t* pivot_mass, int64_t* total, int64_t* rec_unit, void* stream);
+
 /* Character timestamps: the best monotone path through the attention weights of a decode (the align
  * that casr_greedy and casr_score write), per token its first, last and peak encoder frame.  The
  * reference has no counterpart; like the edit distance the operation is DEFINED BY THE FORMULAS BELOW,
