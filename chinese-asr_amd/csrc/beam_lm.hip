@@ -505,11 +505,10 @@ __global__ void beam_record_lm_kernel(int B, int k, int L, const float* __restri
   out[i] = (l < steps && rec_valid[i]) ? rec_lm[i] : 0.f;
 }
 
-hipError_t run_beam_record_lm(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float* rec_lm,
-                              hipStream_t s) {
-  const size_t n = (size_t)a.B * a.max_len * a.k;
-  hipLaunchKernelGGL(beam_record_lm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.B, a.k, a.max_len,
-                     w.rec_lm, d.rec_valid, d.newdone, rec_lm);
+hipError_t run_beam_record_lm(const BeamTree& t, const BeamLmBufs& w, float* rec_lm, hipStream_t s) {
+  const size_t n = (size_t)t.B * t.L * t.k;
+  hipLaunchKernelGGL(beam_record_lm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t.B, t.k, t.L,
+                     w.rec_lm, t.rec_valid, t.newdone, rec_lm);
   return hipGetLastError();
 }
 

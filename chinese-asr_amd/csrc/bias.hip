@@ -231,11 +231,10 @@ __global__ void beam_record_bias_kernel(int B, int k, int L, const int32_t* __re
   out[i] = (l < steps && rec_valid[i]) ? bias_of(rec_full[i]) : 0.f;
 }
 
-hipError_t run_beam_record_bias(const DecodeArgs& a, const DecodeBufs& d, const BeamBiasBufs& w, float* rec_bias,
-                                hipStream_t s) {
-  const size_t n = (size_t)a.B * a.max_len * a.k;
-  hipLaunchKernelGGL(beam_record_bias_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.B, a.k, a.max_len,
-                     w.rec_full, d.rec_valid, d.newdone, rec_bias);
+hipError_t run_beam_record_bias(const BeamTree& t, const BeamBiasBufs& w, float* rec_bias, hipStream_t s) {
+  const size_t n = (size_t)t.B * t.L * t.k;
+  hipLaunchKernelGGL(beam_record_bias_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t.B, t.k, t.L,
+                     w.rec_full, t.rec_valid, t.newdone, rec_bias);
   return hipGetLastError();
 }
 

@@ -214,16 +214,14 @@ struct casr_handle {
   DecodeBufs d{};
   DevBuf gout;  // internal decode outputs written by captured graphs
   Profiler prof;
-  int dec_k = 0;
-  bool beam_done = false;
-  bool beam_lm_done = false;  // the last beam was casr_beam_lm: lmws holds its rec_lm
-  DevBuf lmws;                // casr_beam_lm: term rows, LM sums, rec_lm (carve_beam_lm)
-  bool beam_bias_done = false;  // the last beam was casr_beam_bias: biasws holds its rec_full
-  DevBuf biasws;                // casr_beam_bias: gain rows, states, sums, rec_full (carve_beam_bias)
-  float beam_lm_weight = 0.f, beam_length_weight = 0.f;  // the last casr_beam's (casr_beam_rescore's fallback)
-  DevBuf mbrws;           // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
-  bool mbr_done = false;  // mbrws holds the distances of the last beam's records
-  DevBuf cnws;            // casr_confusion, casr_beam_nbest, casr_beam_confusion: lists, units, votes (carve_confusion)
+  // the last beam and the view of what it left in the decode workspaces (beam_state.h): set by the
+  // beam entries (beam_ran), spent by casr_encode and by prepare_decode, read through beam_readable
+  BeamState beam;
+  BeamTree tree;
+  DevBuf lmws;    // casr_beam_lm: term rows, LM sums, rec_lm (carve_beam_lm)
+  DevBuf biasws;  // casr_beam_bias: gain rows, states, sums, rec_full (carve_beam_bias)
+  DevBuf mbrws;   // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
+  DevBuf cnws;    // casr_confusion, casr_beam_nbest, casr_beam_confusion: lists, units, votes (carve_confusion)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
   // fallback does.  Default 2: the decode loop launches eagerly (measured faster)
@@ -1104,7 +1102,7 @@ static int encode_impl(casr_handle* h, const float* feat, const int32_t* lens, i
   h->B = B;
   h->Tp = Tp;
   h->encoded = true;
-  h->beam_done = false;
+  h->beam = BeamState{};
   return CASR_OK;
 }
 
@@ -1203,6 +1201,10 @@ static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, De
     if (rc) return rc;
   }
   const int R = plan.R;
+  // from here the decode workspaces are this call's: they are carved anew (another R moves newdone)
+  // and its kernels clear newdone and overwrite the scores, so the last beam is spent.  A call
+  // refused above leaves it readable; a beam entry sets its own state after this (beam_ran)
+  h->beam = BeamState{};
   DecodeBufs& d = h->d;
   d = DecodeBufs{};
   HIP_OK(h, h->st.ensure(carve_state(nullptr, plan, d)));
@@ -1271,6 +1273,26 @@ static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, De
   return CASR_OK;
 }
 
+// a beam entry's decode is prepared: the handle's beam state, and the readers' view of the tree and
+// the records it is about to write (the one place BeamTree is filled)
+static void beam_ran(casr_handle* h, int kind, const DecodeArgs& a, float lm_weight, float length_weight) {
+  const DecodeBufs& d = h->d;
+  h->beam = BeamState{kind, a.k, lm_weight, length_weight};
+  h->tree = BeamTree{a.B, a.k, a.max_len, a.V, d.bp, d.tk, d.newdone, d.rec_score, d.rec_src, d.rec_valid,
+                     {d.score[0], d.score[1]}, d.err};
+}
+
+// the gate of the beam's readers (beam_state.h beam_gate) as the API's refusal; why: what the reader
+// assumes of a casr_beam (the readers with a GATE_AFTER_FUSED refusal)
+static int beam_readable(casr_handle* h, int reader, const char* why = "") {
+  switch (h ? beam_gate(h->beam, reader) : GATE_BEFORE) {
+    case GATE_OK: return CASR_OK;
+    case GATE_AFTER_FUSED:
+      return fail(h, CASR_ERR_STATE, "%s after casr_beam_lm or casr_beam_bias: %s", BEAM_READER_NAME[reader], why);
+    default: return fail(h, CASR_ERR_STATE, "%s before %s", BEAM_READER_NAME[reader], BEAM_READER_FOLLOWS[reader]);
+  }
+}
+
 int casr_greedy(casr_handle* h, int32_t* tokens, int32_t* out_len, uint8_t* finished, float* accum,
                 float* align, void* stream) {
   if (!h || !tokens || !out_len || !finished || !accum) return fail(h, CASR_ERR_ARG, "casr_greedy: NULL output");
@@ -1318,13 +1340,7 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
   if (rc) return rc;
   DecodeArgs& a = c.a;
   hipStream_t s = (hipStream_t)stream;
-  h->dec_k = k;
-  h->beam_done = true;
-  h->beam_lm_done = false;
-  h->beam_bias_done = false;
-  h->mbr_done = false;
-  h->beam_lm_weight = lm_weight;
-  h->beam_length_weight = length_weight;
+  beam_ran(h, BEAM_PLAIN, a, lm_weight, length_weight);
   if (!decode_graph_ok(h)) {
     dg_trace_init();  // CASR_DG_TRACE diagnostics only
     HIP_OK(h, run_beam(a, h->d, lm_weight, length_weight, best_tokens, best_len, best_score, steps, s));
@@ -1352,13 +1368,11 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
 
 int casr_beam_records(casr_handle* h, int32_t* rec_tokens, float* rec_score, uint8_t* rec_valid,
                       void* stream) {
-  if (!h || !h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_records before casr_beam");
+  const int rc = beam_readable(h, READ_RECORDS);
+  if (rc) return rc;
   if (!rec_tokens || !rec_score || !rec_valid) return fail(h, CASR_ERR_ARG, "casr_beam_records: NULL output");
   HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
-  if (rc) return rc;
-  HIP_OK(h, run_beam_records(c.a, h->d, rec_tokens, rec_score, rec_valid, (hipStream_t)stream));
+  HIP_OK(h, run_beam_records(h->tree, rec_tokens, rec_score, rec_valid, (hipStream_t)stream));
   return CASR_OK;
 }
 
@@ -1379,6 +1393,17 @@ int casr_score(casr_handle* h, const int32_t* targets, const int32_t* tgt_len, i
   HIP_OK(h, run_score(c.a, h->d, sb, targets, tgt_len, L, token_logp, total_logp, best_token, best_logp, mean_logp, align,
                       (hipStream_t)stream));
   return CASR_OK;
+}
+
+// casr_lm_create, casr_bias_create: the n host tables copied to `device`, dev[i] of bytes[i] (an empty
+// table keeps a 16-byte allocation).  On an error the caller destroys its object, which frees dev
+static hipError_t upload_tables(int device, int n, const void* const* src, const size_t* bytes, void** dev) {
+  hipError_t e = hipSetDevice(device);
+  for (int i = 0; i < n && e == hipSuccess; ++i) {
+    e = hipMalloc(&dev[i], bytes[i] ? bytes[i] : 16);
+    if (e == hipSuccess && bytes[i]) e = hipMemcpy(dev[i], src[i], bytes[i], hipMemcpyHostToDevice);
+  }
+  return e;
 }
 
 int casr_lm_create(int device, int order, int vocab, const int64_t* count, const int32_t* const* ids,
@@ -1407,11 +1432,7 @@ int casr_lm_create(int device, int order, int vocab, const int64_t* count, const
                               u.list[1].size() * sizeof(NgramSucc), u.list[2].size() * sizeof(NgramSucc),
                               u.dir.size() * sizeof(NgramSuccRange), u.ctab[0].size() * sizeof(NgramCtxEntry),
                               u.ctab[1].size() * sizeof(NgramCtxEntry)};
-    hipError_t e = hipSetDevice(device);
-    for (int i = 0; i < 11 && e == hipSuccess; ++i) {
-      e = hipMalloc(&lm->dev[i], bytes[i] ? bytes[i] : 16);  // (an order without reachable n-grams: an empty list)
-      if (e == hipSuccess && bytes[i]) e = hipMemcpy(lm->dev[i], src[i], bytes[i], hipMemcpyHostToDevice);
-    }
+    const hipError_t e = upload_tables(device, 11, src, bytes, lm->dev);  // (an order without reachable n-grams: an empty list)
     if (e != hipSuccess) {
       casr_lm_destroy(lm);
       return fail(nullptr, CASR_ERR_HIP, "casr_lm_create: %s", hipGetErrorString(e));
@@ -1449,15 +1470,22 @@ int casr_lm_score_host(const casr_lm* lm, const int32_t* tokens, const int32_t* 
   return CASR_OK;
 }
 
+// the LM's device copy serves this handle: the same device, the same vocabulary
+static int lm_matches_handle(casr_handle* h, const casr_lm* lm, const char* who) {
+  if (lm->device != h->device)
+    return fail(h, CASR_ERR_ARG, "%s: the LM is %s, the handle on device %d", who,
+                lm->device < 0 ? "host-only" : "on another device", h->device);
+  if (lm->host.V != h->cfg.vocab)
+    return fail(h, CASR_ERR_ARG, "%s: the LM's vocab %d is not the handle's %d", who, lm->host.V, h->cfg.vocab);
+  return CASR_OK;
+}
+
 int casr_lm_score(casr_handle* h, const casr_lm* lm, const int32_t* tokens, const int32_t* lens, int n, int L,
                   int bos, float* q, void* stream) {
   if (!h || !lm || !tokens || !lens || !q || n < 0 || L < 1)
     return fail(h, CASR_ERR_ARG, "casr_lm_score: NULL argument, n < 0 or L < 1");
-  if (lm->device != h->device)
-    return fail(h, CASR_ERR_ARG, "casr_lm_score: the LM is %s, the handle on device %d",
-                lm->device < 0 ? "host-only" : "on another device", h->device);
-  if (lm->host.V != h->cfg.vocab)
-    return fail(h, CASR_ERR_ARG, "casr_lm_score: the LM's vocab %d is not the handle's %d", lm->host.V, h->cfg.vocab);
+  const int rc = lm_matches_handle(h, lm, "casr_lm_score");
+  if (rc) return rc;
   HIP_OK(h, hipSetDevice(h->device));
   if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_lm_score: no guard words");
   int32_t* err = GUARD(h, 0);
@@ -1470,22 +1498,13 @@ int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, doubl
                       void* stream) {
   if (!h || !lm || !best_tokens || !best_len || !best_score)
     return fail(h, CASR_ERR_ARG, "casr_beam_rescore: NULL handle, LM or output");
-  if (!h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_rescore before casr_beam");
-  if (h->beam_lm_done || h->beam_bias_done)
-    return fail(h, CASR_ERR_STATE, "casr_beam_rescore after casr_beam_lm or casr_beam_bias: the second pass rescores a casr_beam");
-  if (lm->device != h->device)
-    return fail(h, CASR_ERR_ARG, "casr_beam_rescore: the LM is %s, the handle on device %d",
-                lm->device < 0 ? "host-only" : "on another device", h->device);
-  if (lm->host.V != h->cfg.vocab)
-    return fail(h, CASR_ERR_ARG, "casr_beam_rescore: the LM's vocab %d is not the handle's %d", lm->host.V,
-                h->cfg.vocab);
-  if (!rescore_supported(h->cfg.max_len, h->dec_k))
-    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_rescore: max_len %d x k %d past the LDS", h->cfg.max_len, h->dec_k);
-  HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  int rc = beam_readable(h, READ_RESCORE, "the second pass rescores a casr_beam");
+  if (!rc) rc = lm_matches_handle(h, lm, "casr_beam_rescore");
   if (rc) return rc;
-  HIP_OK(h, run_beam_rescore(c.a, h->d, lm->dview, lm_weight, length_weight, h->beam_lm_weight, h->beam_length_weight,
+  if (!rescore_supported(h->cfg.max_len, h->beam.k))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_rescore: max_len %d x k %d past the LDS", h->cfg.max_len, h->beam.k);
+  HIP_OK(h, hipSetDevice(h->device));
+  HIP_OK(h, run_beam_rescore(h->tree, lm->dview, lm_weight, length_weight, h->beam.lm_weight, h->beam.length_weight,
                              best_tokens, best_len, best_score, best_lm, rec_lm, (hipStream_t)stream));
   return CASR_OK;
 }
@@ -1545,13 +1564,19 @@ int casr_align_path(casr_handle* h, const float* align, const int32_t* enc_len, 
   return CASR_OK;
 }
 
+// the posterior scale of casr_mbr_host, casr_beam_mbr, casr_posterior_units_host and casr_beam_confusion
+static int scale_checked(casr_handle* h, const char* who, double scale) {
+  if (!(scale >= 0.0) || !std::isfinite(scale))
+    return fail(h, CASR_ERR_ARG, "%s: scale %g is negative or not finite", who, scale);
+  return CASR_OK;
+}
+
 int casr_mbr_host(const int32_t* rec_tokens, const float* rec_score, const uint8_t* rec_valid, const float* rec_lm,
                   int B, int max_len, int k, double scale, double lm_weight, double length_weight, int32_t* best_index,
                   double* rec_risk) {
   if (B < 0 || max_len < 1 || k < 1 || (B > 0 && (!rec_tokens || !rec_score || !rec_valid || !best_index)))
     return fail(nullptr, CASR_ERR_ARG, "casr_mbr_host: NULL argument, B < 0, or max_len or k < 1");
-  if (!(scale >= 0.0) || !std::isfinite(scale))
-    return fail(nullptr, CASR_ERR_ARG, "casr_mbr_host: scale %g is negative or not finite", scale);
+  if (int rs = scale_checked(nullptr, "casr_mbr_host", scale)) return rs;
   const size_t LK = (size_t)max_len * k;
   for (int b = 0; b < B; ++b)
     best_index[b] = mbr_utterance_host(rec_tokens + b * LK * max_len, rec_score + b * LK, rec_valid + b * LK,
@@ -1565,38 +1590,33 @@ int casr_beam_mbr(casr_handle* h, double scale, const float* rec_lm, double lm_w
                   double* rec_risk, void* stream) {
   if (!h || !best_tokens || !best_len || !best_score)
     return fail(h, CASR_ERR_ARG, "casr_beam_mbr: NULL handle, best_tokens, best_len or best_score");
-  if (!(scale >= 0.0) || !std::isfinite(scale))
-    return fail(h, CASR_ERR_ARG, "casr_beam_mbr: scale %g is negative or not finite", scale);
-  if (!h->beam_done) return fail(h, CASR_ERR_STATE, "casr_beam_mbr before casr_beam");
-  if (h->beam_lm_done || h->beam_bias_done)
-    return fail(h, CASR_ERR_STATE, "casr_beam_mbr after casr_beam_lm or casr_beam_bias: the fallback assumes the scores of a casr_beam");
-  if (!mbr_supported(h->cfg.max_len, h->dec_k))
-    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_mbr: max_len %d x k %d: distances are bytes (max_len <= %d) and the tree must fit 64 KB of LDS",
-                h->cfg.max_len, h->dec_k, EDIT_MBR_MAX_LEN);
-  HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  if (int rs = scale_checked(h, "casr_beam_mbr", scale)) return rs;
+  const int rc = beam_readable(h, READ_MBR, "the fallback assumes the scores of a casr_beam");
   if (rc) return rc;
+  const BeamTree& t = h->tree;
+  if (!mbr_supported(t.L, t.k))
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_mbr: max_len %d x k %d: distances are bytes (max_len <= %d) and the tree must fit 64 KB of LDS",
+                t.L, t.k, EDIT_MBR_MAX_LEN);
+  HIP_OK(h, hipSetDevice(h->device));
   MbrBufs w{};
-  HIP_OK(h, h->mbrws.ensure(carve_mbr(nullptr, c.a.B, c.a.max_len, c.a.k, w)));
-  carve_mbr(h->mbrws.p, c.a.B, c.a.max_len, c.a.k, w);
-  h->mbr_done = true;
-  HIP_OK(h, run_beam_mbr(c.a, h->d, w, h->tune[CASR_OPT_MBR_MAP], scale, rec_lm, lm_weight, length_weight,
-                         h->beam_lm_weight, h->beam_length_weight, best_tokens, best_len, best_score, best_index,
-                         best_risk, rec_risk, (hipStream_t)stream));
+  HIP_OK(h, h->mbrws.ensure(carve_mbr(nullptr, t.B, t.L, t.k, w)));
+  carve_mbr(h->mbrws.p, t.B, t.L, t.k, w);
+  h->beam.mbr = true;
+  HIP_OK(h, run_beam_mbr(t, w, h->tune[CASR_OPT_MBR_MAP], scale, rec_lm, lm_weight, length_weight, h->beam.lm_weight,
+                         h->beam.length_weight, best_tokens, best_len, best_score, best_index, best_risk, rec_risk,
+                         (hipStream_t)stream));
   return CASR_OK;
 }
 
 int casr_beam_mbr_distances(casr_handle* h, uint8_t* dist, int32_t* n_rec, void* stream) {
   if (!h || !dist) return fail(h, CASR_ERR_ARG, "casr_beam_mbr_distances: NULL handle or output");
-  if (!h->beam_done || !h->mbr_done) return fail(h, CASR_ERR_STATE, "casr_beam_mbr_distances before casr_beam_mbr");
-  HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  int rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
+  const int rc = beam_readable(h, READ_MBR_DISTANCES);
   if (rc) return rc;
+  const BeamTree& t = h->tree;
+  HIP_OK(h, hipSetDevice(h->device));
   MbrBufs w{};
-  carve_mbr(h->mbrws.p, c.a.B, c.a.max_len, c.a.k, w);
-  HIP_OK(h, run_mbr_distances(c.a, w, dist, n_rec, (hipStream_t)stream));
+  carve_mbr(h->mbrws.p, t.B, t.L, t.k, w);
+  HIP_OK(h, run_mbr_distances(t, w, dist, n_rec, (hipStream_t)stream));
   return CASR_OK;
 }
 
@@ -1605,8 +1625,7 @@ int casr_posterior_units_host(const float* rec_score, const uint8_t* rec_valid, 
                               int64_t* rec_unit, int64_t* total) {
   if (B < 0 || max_len < 1 || k < 1 || (B > 0 && (!rec_score || !rec_valid || !rec_unit)))
     return fail(nullptr, CASR_ERR_ARG, "casr_posterior_units_host: NULL argument, B < 0, or max_len or k < 1");
-  if (!(scale >= 0.0) || !std::isfinite(scale))
-    return fail(nullptr, CASR_ERR_ARG, "casr_posterior_units_host: scale %g is negative or not finite", scale);
+  if (int rs = scale_checked(nullptr, "casr_posterior_units_host", scale)) return rs;
   const size_t LK = (size_t)max_len * k;
   for (int b = 0; b < B; ++b) {
     const int64_t U = cn_units_utterance_host(rec_score + b * LK, rec_valid + b * LK, rec_lm ? rec_lm + b * LK : nullptr,
@@ -1668,13 +1687,12 @@ int casr_confusion(casr_handle* h, const int32_t* rec_tokens, const uint8_t* rec
   return CASR_OK;
 }
 
-// the refusals casr_beam_nbest and casr_beam_confusion share with casr_beam_mbr
-static int beam_records_readable(casr_handle* h, const char* who) {
-  if (!h->beam_done) return fail(h, CASR_ERR_STATE, "%s before casr_beam", who);
-  if (h->beam_lm_done || h->beam_bias_done)
-    return fail(h, CASR_ERR_STATE, "%s after casr_beam_lm or casr_beam_bias: c is the comb of a casr_beam's records", who);
-  if (h->cfg.max_len > CN_MAX_LEN)
-    return fail(h, CASR_ERR_UNSUPPORTED, "%s: max_len %d (<= %d)", who, h->cfg.max_len, CN_MAX_LEN);
+// the refusals casr_beam_nbest and casr_beam_confusion share: the gate, and the lists' length limit
+static int beam_comb_readable(casr_handle* h, int reader) {
+  const int rc = beam_readable(h, reader, "c is the comb of a casr_beam's records");
+  if (rc) return rc;
+  if (h->tree.L > CN_MAX_LEN)
+    return fail(h, CASR_ERR_UNSUPPORTED, "%s: max_len %d (<= %d)", BEAM_READER_NAME[reader], h->tree.L, CN_MAX_LEN);
   return CASR_OK;
 }
 
@@ -1684,17 +1702,15 @@ int casr_beam_nbest(casr_handle* h, int N, const float* rec_lm, double lm_weight
   if (!h || !nbest_index || !nbest_tokens || !nbest_len || !nbest_comb)
     return fail(h, CASR_ERR_ARG, "casr_beam_nbest: NULL handle or output");
   if (N < 1 || N > CN_MAX_N) return fail(h, CASR_ERR_ARG, "casr_beam_nbest: N = %d not in [1, %d]", N, CN_MAX_N);
-  int rc = beam_records_readable(h, "casr_beam_nbest");
+  const int rc = beam_comb_readable(h, READ_NBEST);
   if (rc) return rc;
+  const BeamTree& t = h->tree;
   HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
-  if (rc) return rc;
   CnBufs w{};
-  HIP_OK(h, h->cnws.ensure(carve_confusion(nullptr, c.a.B, c.a.max_len, c.a.k, false, w)));
-  carve_confusion(h->cnws.p, c.a.B, c.a.max_len, c.a.k, false, w);
-  HIP_OK(h, run_beam_nbest(c.a, h->d, w, N, rec_lm, lm_weight, length_weight, nbest_index, nbest_tokens, nbest_len,
-                           nbest_comb, (hipStream_t)stream));
+  HIP_OK(h, h->cnws.ensure(carve_confusion(nullptr, t.B, t.L, t.k, false, w)));
+  carve_confusion(h->cnws.p, t.B, t.L, t.k, false, w);
+  HIP_OK(h, run_beam_nbest(t, w, N, rec_lm, lm_weight, length_weight, nbest_index, nbest_tokens, nbest_len, nbest_comb,
+                           (hipStream_t)stream));
   return CASR_OK;
 }
 
@@ -1704,33 +1720,27 @@ int casr_beam_confusion(casr_handle* h, int M, double scale, const float* rec_lm
   if (!h || !n_slots || !slot_token || !slot_mass || !pivot_mass || !total)
     return fail(h, CASR_ERR_ARG, "casr_beam_confusion: NULL handle or output");
   if (M < 1 || M > CN_MAX_M) return fail(h, CASR_ERR_ARG, "casr_beam_confusion: M = %d not in [1, %d]", M, CN_MAX_M);
-  if (!(scale >= 0.0) || !std::isfinite(scale))
-    return fail(h, CASR_ERR_ARG, "casr_beam_confusion: scale %g is negative or not finite", scale);
-  int rc = beam_records_readable(h, "casr_beam_confusion");
+  if (int rs = scale_checked(h, "casr_beam_confusion", scale)) return rs;
+  const int rc = beam_comb_readable(h, READ_CONFUSION);
   if (rc) return rc;
+  const BeamTree& t = h->tree;
   // the network's own limits (casr_beam_nbest has none of them)
-  if (!confusion_supported(h->B, h->cfg.max_len, h->dec_k, h->cfg.vocab, true))
+  if (!confusion_supported(t.B, t.L, t.k, t.V, true))
     return fail(h, CASR_ERR_UNSUPPORTED, "casr_beam_confusion: k %d, vocab %d (<= %d): votes are int16 and the masses must fit the LDS",
-                h->dec_k, h->cfg.vocab, CN_MAX_VOCAB);
+                t.k, t.V, CN_MAX_VOCAB);
   HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  rc = prepare_decode(h, PLAN_BEAM, h->dec_k, false, c);
-  if (rc) return rc;
   CnBufs w{};
-  HIP_OK(h, h->cnws.ensure(carve_confusion(nullptr, c.a.B, c.a.max_len, c.a.k, true, w)));
-  carve_confusion(h->cnws.p, c.a.B, c.a.max_len, c.a.k, true, w);
-  HIP_OK(h, run_beam_confusion(c.a, h->d, w, M, scale, rec_lm, lm_weight, length_weight, pivot, n_slots, slot_token,
-                               slot_mass, pivot_mass, total, rec_unit, (hipStream_t)stream));
+  HIP_OK(h, h->cnws.ensure(carve_confusion(nullptr, t.B, t.L, t.k, true, w)));
+  carve_confusion(h->cnws.p, t.B, t.L, t.k, true, w);
+  HIP_OK(h, run_beam_confusion(t, w, M, scale, rec_lm, lm_weight, length_weight, pivot, n_slots, slot_token, slot_mass,
+                               pivot_mass, total, rec_unit, (hipStream_t)stream));
   return CASR_OK;
 }
 
-// the refusals casr_lm_terms and casr_beam_lm share with casr_lm_score
+// casr_lm_terms, casr_beam_lm, casr_beam_bias: lm_matches_handle, and a term row fits its LDS
 static int lm_on_handle(casr_handle* h, const casr_lm* lm, const char* who) {
-  if (lm->device != h->device)
-    return fail(h, CASR_ERR_ARG, "%s: the LM is %s, the handle on device %d", who,
-                lm->device < 0 ? "host-only" : "on another device", h->device);
-  if (lm->host.V != h->cfg.vocab)
-    return fail(h, CASR_ERR_ARG, "%s: the LM's vocab %d is not the handle's %d", who, lm->host.V, h->cfg.vocab);
+  const int rc = lm_matches_handle(h, lm, who);
+  if (rc) return rc;
   if (!lm_terms_supported(lm->host.V))
     return fail(h, CASR_ERR_UNSUPPORTED, "%s: a term row of %d words is past the %d KB of LDS it is assembled in", who,
                 lm->host.V, (int)(LM_TERMS_LDS_BYTES / 1024));
@@ -1778,13 +1788,7 @@ int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, floa
   BeamLmBufs w{};
   HIP_OK(h, h->lmws.ensure(carve_beam_lm(nullptr, a.B, a.plan.R, a.max_len, a.k, a.V, w)));
   carve_beam_lm(h->lmws.p, a.B, a.plan.R, a.max_len, a.k, a.V, w);
-  h->dec_k = k;
-  h->beam_done = true;
-  h->beam_lm_done = true;
-  h->beam_bias_done = false;
-  h->mbr_done = false;
-  h->beam_lm_weight = lm_weight;
-  h->beam_length_weight = length_weight;
+  beam_ran(h, BEAM_LM, a, lm_weight, length_weight);
   // (never a hipGraph: launched eagerly whatever casr_set_graphs says)
   dg_trace_init();  // CASR_DG_TRACE diagnostics only
   HIP_OK(h, run_beam_lm(a, h->d, w, lm->dview, lm->dsucc, lm_weight, length_weight, best_tokens, best_len, best_score,
@@ -1794,15 +1798,14 @@ int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, floa
 }
 
 int casr_beam_record_lm(casr_handle* h, float* rec_lm, void* stream) {
-  if (!h || !h->beam_done || !h->beam_lm_done) return fail(h, CASR_ERR_STATE, "casr_beam_record_lm before casr_beam_lm");
-  if (!rec_lm) return fail(h, CASR_ERR_ARG, "casr_beam_record_lm: NULL output");
-  HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  int rc = prepare_decode(h, PLAN_BEAM_LM, h->dec_k, false, c);
+  const int rc = beam_readable(h, READ_RECORD_LM);
   if (rc) return rc;
+  if (!rec_lm) return fail(h, CASR_ERR_ARG, "casr_beam_record_lm: NULL output");
+  const BeamTree& t = h->tree;
+  HIP_OK(h, hipSetDevice(h->device));
   BeamLmBufs w{};
-  carve_beam_lm(h->lmws.p, c.a.B, c.a.plan.R, c.a.max_len, c.a.k, c.a.V, w);
-  HIP_OK(h, run_beam_record_lm(c.a, h->d, w, rec_lm, (hipStream_t)stream));
+  carve_beam_lm(h->lmws.p, t.B, t.B * t.k, t.L, t.k, t.V, w);
+  HIP_OK(h, run_beam_record_lm(t, w, rec_lm, (hipStream_t)stream));
   return CASR_OK;
 }
 
@@ -1825,11 +1828,7 @@ int casr_bias_create(int device, int vocab, int n_phrases, const int32_t* tokens
     const size_t bytes[5] = {t.node.size() * sizeof(BiasNode), t.ctok.size() * sizeof(int32_t),
                              t.cnext.size() * sizeof(int32_t), t.root_next.size() * sizeof(int32_t),
                              t.root_gain.size() * sizeof(int32_t)};
-    hipError_t e = hipSetDevice(device);
-    for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-      e = hipMalloc(&bo->dev[i], bytes[i] ? bytes[i] : 16);  // (no phrases: the root has no children)
-      if (e == hipSuccess && bytes[i]) e = hipMemcpy(bo->dev[i], src[i], bytes[i], hipMemcpyHostToDevice);
-    }
+    const hipError_t e = upload_tables(device, 5, src, bytes, bo->dev);  // (no phrases: the root has no children)
     if (e != hipSuccess) {
       casr_bias_destroy(bo);
       return fail(nullptr, CASR_ERR_HIP, "casr_bias_create: %s", hipGetErrorString(e));
@@ -1950,13 +1949,7 @@ int casr_beam_bias(casr_handle* h, const casr_bias* bias, const casr_lm* lm, int
   BeamBiasBufs w{};
   HIP_OK(h, h->biasws.ensure(carve_beam_bias(nullptr, a.B, a.plan.R, a.max_len, a.k, a.V, w)));
   carve_beam_bias(h->biasws.p, a.B, a.plan.R, a.max_len, a.k, a.V, w);
-  h->dec_k = k;
-  h->beam_done = true;
-  h->beam_lm_done = lm != nullptr;  // (casr_beam_record_lm reads lmws)
-  h->beam_bias_done = true;
-  h->mbr_done = false;
-  h->beam_lm_weight = lm_weight;
-  h->beam_length_weight = length_weight;
+  beam_ran(h, lm ? BEAM_BIAS_LM : BEAM_BIAS, a, lm_weight, length_weight);  // (with an LM casr_beam_record_lm reads lmws)
   // (never a hipGraph: launched eagerly whatever casr_set_graphs says)
   dg_trace_init();  // CASR_DG_TRACE diagnostics only
   HIP_OK(h, run_beam_bias(a, h->d, lm ? &lw : nullptr, w, bias->dview, lm ? &lm->dview : nullptr,
@@ -1967,16 +1960,14 @@ int casr_beam_bias(casr_handle* h, const casr_bias* bias, const casr_lm* lm, int
 }
 
 int casr_beam_record_bias(casr_handle* h, float* rec_bias, void* stream) {
-  if (!h || !h->beam_done || !h->beam_bias_done)
-    return fail(h, CASR_ERR_STATE, "casr_beam_record_bias before casr_beam_bias");
-  if (!rec_bias) return fail(h, CASR_ERR_ARG, "casr_beam_record_bias: NULL output");
-  HIP_OK(h, hipSetDevice(h->device));
-  DecodeCall c;
-  int rc = prepare_decode(h, PLAN_BEAM_LM, h->dec_k, false, c);
+  const int rc = beam_readable(h, READ_RECORD_BIAS);
   if (rc) return rc;
+  if (!rec_bias) return fail(h, CASR_ERR_ARG, "casr_beam_record_bias: NULL output");
+  const BeamTree& t = h->tree;
+  HIP_OK(h, hipSetDevice(h->device));
   BeamBiasBufs w{};
-  carve_beam_bias(h->biasws.p, c.a.B, c.a.plan.R, c.a.max_len, c.a.k, c.a.V, w);
-  HIP_OK(h, run_beam_record_bias(c.a, h->d, w, rec_bias, (hipStream_t)stream));
+  carve_beam_bias(h->biasws.p, t.B, t.B * t.k, t.L, t.k, t.V, w);
+  HIP_OK(h, run_beam_record_bias(t, w, rec_bias, (hipStream_t)stream));
   return CASR_OK;
 }
 

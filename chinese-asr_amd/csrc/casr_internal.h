@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "beam_state.h"
 #include "bias_plan.h"
 #include "casr.h"
 #include "encode_plan.h"
@@ -437,8 +438,10 @@ hipError_t run_greedy(const DecodeArgs& a, DecodeBufs& d, int32_t* tokens, int32
 hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float length_weight,
                     int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* steps,
                     hipStream_t s);
-hipError_t run_beam_records(const DecodeArgs& a, DecodeBufs& d, int32_t* rec_tokens,
-                            float* rec_score, uint8_t* rec_valid, hipStream_t s);
+// The readers of a finished beam take its BeamTree (beam_state.h): casr_capi.hip fills it from the
+// DecodeArgs and DecodeBufs of the beam entry that ran and keeps it in the handle
+hipError_t run_beam_records(const BeamTree& t, int32_t* rec_tokens, float* rec_score, uint8_t* rec_valid,
+                            hipStream_t s);
 
 // Teacher-forced scoring (casr_score, score.hip).  L steps of the three-launch step without its
 // projection (decoder.hip score_steps), every step's state slab kept in a history, then ONE
@@ -467,13 +470,12 @@ hipError_t run_score(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, co
 // Sentence scores q [n] of tokens [n][L] (LM ids) with lens [n]
 hipError_t launch_lm_score(const NgramView& m, const int32_t* tokens, const int32_t* lens, int n, int L, int bos,
                            float* q, int32_t* err, hipStream_t s);
-// the second pass over the beam state run_beam left in d (one workgroup per utterance); the beam
+// the second pass over the beam tree run_beam left (one workgroup per utterance); the beam
 // weights are casr_beam's own, for its unfinished fallback.  rescore_supported: its LDS fits
 bool rescore_supported(int max_len, int k);
-hipError_t run_beam_rescore(const DecodeArgs& a, const DecodeBufs& d, const NgramView& m, double lm_weight,
-                            double length_weight, float beam_lm_weight, float beam_length_weight,
-                            int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
-                            float* rec_lm, hipStream_t s);
+hipError_t run_beam_rescore(const BeamTree& t, const NgramView& m, double lm_weight, double length_weight,
+                            float beam_lm_weight, float beam_length_weight, int32_t* best_tokens, int32_t* best_len,
+                            float* best_score, float* best_lm, float* rec_lm, hipStream_t s);
 
 // beam_lm.hip: the LM fused into the beam's first pass (casr_lm_terms, casr_beam_lm).
 // Where a term row's context comes from: tree == 0 the arrays ctx [n][3] / nc [n]; tree == 1 the beam
@@ -518,8 +520,7 @@ hipError_t launch_beam_lm_select(const BeamSelArgs& a, const BeamLmArgs& g, int 
 hipError_t launch_beam_lm_finalize(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float lm_weight,
                                    float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
                                    float* best_lm, int32_t* steps, hipStream_t s);
-hipError_t run_beam_record_lm(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float* rec_lm,
-                              hipStream_t s);
+hipError_t run_beam_record_lm(const BeamTree& t, const BeamLmBufs& w, float* rec_lm, hipStream_t s);
 // decoder.hip: run_beam's steps (a.plan: the PLAN_BEAM_LM caller's) with the term rows and the fused
 // select after each
 hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, const NgramView& m,
@@ -576,8 +577,7 @@ hipError_t launch_beam_bias_finalize(const DecodeArgs& a, const DecodeBufs& d, c
                                      const BeamBiasBufs& w, const BiasView& m, float bias_weight, float lm_weight,
                                      float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
                                      float* best_lm, float* best_bias, int32_t* steps, hipStream_t s);
-hipError_t run_beam_record_bias(const DecodeArgs& a, const DecodeBufs& d, const BeamBiasBufs& w, float* rec_bias,
-                                hipStream_t s);
+hipError_t run_beam_record_bias(const BeamTree& t, const BeamBiasBufs& w, float* rec_bias, hipStream_t s);
 // decoder.hip: run_beam_lm's steps with the gain rows (and, with lw, the term rows) before the select
 hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* lw, const BeamBiasBufs& w,
                          const BiasView& bm, const NgramView* m, const NgramSuccView* sv, float bias_weight,
@@ -597,12 +597,12 @@ struct MbrBufs {
 };
 size_t carve_mbr(void* base, int B, int L, int k, MbrBufs& w);
 bool mbr_supported(int max_len, int k);
-// the MBR choice over the beam state run_beam left in d; map: CASR_OPT_MBR_MAP
-hipError_t run_beam_mbr(const DecodeArgs& a, const DecodeBufs& d, const MbrBufs& w, int map, double scale,
-                        const float* rec_lm, double lm_weight, double length_weight, float beam_lm_weight,
-                        float beam_length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
-                        int32_t* best_index, double* best_risk, double* rec_risk, hipStream_t s);
-hipError_t run_mbr_distances(const DecodeArgs& a, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s);
+// the MBR choice over the beam tree run_beam left; map: CASR_OPT_MBR_MAP
+hipError_t run_beam_mbr(const BeamTree& t, const MbrBufs& w, int map, double scale, const float* rec_lm,
+                        double lm_weight, double length_weight, float beam_lm_weight, float beam_length_weight,
+                        int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* best_index,
+                        double* best_risk, double* rec_risk, hipStream_t s);
+hipError_t run_mbr_distances(const BeamTree& t, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s);
 
 // confusion.hip: N-best lists and confusion networks over a beam's records (confusion_plan.h).
 // The handle-owned workspace; positions are those in an utterance's list
@@ -617,13 +617,13 @@ struct CnBufs {
 };
 size_t carve_confusion(void* base, int B, int L, int k, bool votes, CnBufs& w);
 bool confusion_supported(int B, int max_len, int k, int V, bool tree);
-hipError_t run_beam_nbest(const DecodeArgs& a, const DecodeBufs& d, const CnBufs& w, int N, const float* rec_lm,
-                          double lm_weight, double length_weight, int32_t* nbest_index, int32_t* nbest_tokens,
-                          int32_t* nbest_len, double* nbest_comb, hipStream_t s);
-hipError_t run_beam_confusion(const DecodeArgs& a, const DecodeBufs& d, const CnBufs& w, int M, double scale,
-                              const float* rec_lm, double lm_weight, double length_weight, const int32_t* pivot,
-                              int32_t* n_slots, int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass,
-                              int64_t* total, int64_t* rec_unit, hipStream_t s);
+hipError_t run_beam_nbest(const BeamTree& t, const CnBufs& w, int N, const float* rec_lm, double lm_weight,
+                          double length_weight, int32_t* nbest_index, int32_t* nbest_tokens, int32_t* nbest_len,
+                          double* nbest_comb, hipStream_t s);
+hipError_t run_beam_confusion(const BeamTree& t, const CnBufs& w, int M, double scale, const float* rec_lm,
+                              double lm_weight, double length_weight, const int32_t* pivot, int32_t* n_slots,
+                              int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total,
+                              int64_t* rec_unit, hipStream_t s);
 hipError_t run_confusion(const CnBufs& w, const int32_t* rec_tokens, const uint8_t* rec_valid, const int64_t* rec_unit,
                          const int32_t* pivot, int B, int L, int k, int V, int M, int32_t* n_slots,
                          int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total, int32_t* err,

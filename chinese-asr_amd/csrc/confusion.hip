@@ -301,26 +301,26 @@ size_t carve_confusion(void* base, int B, int L, int k, bool votes, CnBufs& w) {
   return cn_round256(c.bytes());
 }
 
-static CnArgs cn_beam_args(const DecodeArgs& a, const DecodeBufs& d, const CnBufs& w, double scale, const float* rec_lm,
-                           double lm_weight, double length_weight) {
+static CnArgs cn_beam_args(const BeamTree& t, const CnBufs& w, double scale, const float* rec_lm, double lm_weight,
+                           double length_weight) {
   CnArgs c{};  // (what is not named stays null: the MBR's outputs and workspace are not read here)
-  c.m.B = a.B;
-  c.m.k = a.k;
-  c.m.L = a.max_len;
-  c.m.V = a.V;
+  c.m.B = t.B;
+  c.m.k = t.k;
+  c.m.L = t.L;
+  c.m.V = t.V;
   c.m.scale = scale;
   c.m.lm_weight = lm_weight;
   c.m.length_weight = length_weight;
-  c.m.score0 = d.score[0];
-  c.m.score1 = d.score[1];
-  c.m.bp = d.bp;
-  c.m.tk = d.tk;
-  c.m.rec_score = d.rec_score;
-  c.m.rec_src = d.rec_src;
-  c.m.rec_valid = d.rec_valid;
-  c.m.newdone = d.newdone;
+  c.m.score0 = t.score[0];
+  c.m.score1 = t.score[1];
+  c.m.bp = t.bp;
+  c.m.tk = t.tk;
+  c.m.rec_score = t.rec_score;
+  c.m.rec_src = t.rec_src;
+  c.m.rec_valid = t.rec_valid;
+  c.m.newdone = t.newdone;
   c.m.rec_lm = rec_lm;
-  c.m.err = d.err;
+  c.m.err = t.err;
   c.w = w;
   c.tree = true;
   return c;
@@ -351,26 +351,26 @@ static hipError_t cn_launch_network(CnArgs& c, const ConfusionPlan& pl, hipStrea
   return hipGetLastError();
 }
 
-hipError_t run_beam_nbest(const DecodeArgs& a, const DecodeBufs& d, const CnBufs& w, int N, const float* rec_lm,
-                          double lm_weight, double length_weight, int32_t* nbest_index, int32_t* nbest_tokens,
-                          int32_t* nbest_len, double* nbest_comb, hipStream_t s) {
-  CnArgs c = cn_beam_args(a, d, w, 0.0, rec_lm, lm_weight, length_weight);
+hipError_t run_beam_nbest(const BeamTree& t, const CnBufs& w, int N, const float* rec_lm, double lm_weight,
+                          double length_weight, int32_t* nbest_index, int32_t* nbest_tokens, int32_t* nbest_len,
+                          double* nbest_comb, hipStream_t s) {
+  CnArgs c = cn_beam_args(t, w, 0.0, rec_lm, lm_weight, length_weight);
   c.N = N;
   c.nbest_index = nbest_index;
   c.nbest_tokens = nbest_tokens;
   c.nbest_len = nbest_len;
   c.nbest_comb = nbest_comb;
-  hipLaunchKernelGGL(cn_prepare_kernel, dim3(a.B), dim3(MBR_THREADS), 0, s, c);
+  hipLaunchKernelGGL(cn_prepare_kernel, dim3(t.B), dim3(MBR_THREADS), 0, s, c);
   return hipGetLastError();
 }
 
-hipError_t run_beam_confusion(const DecodeArgs& a, const DecodeBufs& d, const CnBufs& w, int M, double scale,
-                              const float* rec_lm, double lm_weight, double length_weight, const int32_t* pivot,
-                              int32_t* n_slots, int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass,
-                              int64_t* total, int64_t* rec_unit, hipStream_t s) {
-  const ConfusionPlan pl = confusion_plan(a.B, a.max_len, a.k, a.V, true);
+hipError_t run_beam_confusion(const BeamTree& t, const CnBufs& w, int M, double scale, const float* rec_lm,
+                              double lm_weight, double length_weight, const int32_t* pivot, int32_t* n_slots,
+                              int32_t* slot_token, int64_t* slot_mass, int64_t* pivot_mass, int64_t* total,
+                              int64_t* rec_unit, hipStream_t s) {
+  const ConfusionPlan pl = confusion_plan(t.B, t.L, t.k, t.V, true);
   if (!pl.ok) return hipErrorInvalidValue;
-  CnArgs c = cn_beam_args(a, d, w, scale, rec_lm, lm_weight, length_weight);
+  CnArgs c = cn_beam_args(t, w, scale, rec_lm, lm_weight, length_weight);
   c.M = M;
   c.pivot = pivot;
   c.n_slots = n_slots;

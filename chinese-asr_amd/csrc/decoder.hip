@@ -1884,37 +1884,45 @@ static void launch_beam_select(const DecodeArgs& a, DecodeBufs& d, int l, hipStr
   hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * bs_waves<K2>()), 0, s, beam_sel_args(a, d, l));
 }
 
-hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float length_weight,
-                    int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* steps,
-                    hipStream_t s) {
-  const int R = a.B * a.k;
+// The step loop of the three beam entries (run_beam, run_beam_lm, run_beam_bias): the early-exit
+// counters and the top-finished flags cleared, the initial state, then per step l the decode step the
+// plan picks and `select(l)`, the entry's own select of step l (a callable returning hipError_t).
+// fsel (run_beam alone, a.plan.fuse_select): the folded step with one attention block per utterance
+// (k = 4 or 8 rows per block) runs the select of step l - 1 in step l's attention prologue
+// (CASR_OPT_FUSE_SELECT), so select(l) is called at the last step only.
+// (k = 8 at 4 rows per attention block: both blocks of an utterance run the select, CELL 4)
+template <class Select>
+static hipError_t beam_steps(const DecodeArgs& a, DecodeBufs& d, bool fsel, hipStream_t s, Select&& select) {
   FillList fl;
   fl.add32(d.newdone, 0, a.max_len);
   fl.add8(d.topfin, 0, a.B);
-  hipError_t e0 = fill_multi(fl, s);
-  if (e0 != hipSuccess) return e0;
-  hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, a.k,
+  hipError_t e = fill_multi(fl, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(decode_init_kernel, dim3(a.B * a.k), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, a.k,
                      a.sos, d.tok[0], d.src[0], d.score[0], nullptr);
-  // the folded step with one attention block per utterance (k = 4 or 8 rows per block): the select
-  // of step l - 1 runs in step l's attention prologue (CASR_OPT_FUSE_SELECT; the last step's select
-  // is a launch of its own)
-  // (k = 8 at 4 rows per attention block: both blocks of an utterance run the select, CELL 4)
-  const bool fsel = a.plan.fuse_select;
   for (int l = 0; l < a.max_len; ++l) {
     // the folded step (CASR_OPT_DEC_FOLD): step 0's LSTMCell + attention, then per step the
     // attention with the cell prologue (l >= 1) and the fused GEMM
-    hipError_t e;
     if (!a.plan.fold) {
       e = decode_step(a, d, l, a.B, nullptr, s);
     } else if (l == 0) {
       e = decode_step(a, d, 0, a.B, nullptr, s, nullptr, false);
-    } else {
+    } else {  // (no fsel: the select's tokens and predecessor rows from d.tok / d.src)
       const BeamSelArgs bs = beam_sel_args(a, d, l - 1);
       e = fold_attention_step(a, d, l, a.B, nullptr, false, GreedySel{}, s, fsel ? &bs : nullptr);
     }
     if (e == hipSuccess && a.plan.fold) e = fold_gemm_step(a, d, l, a.B, s);
     if (e != hipSuccess) return e;
     if (fsel && l + 1 < a.max_len) continue;
+    if ((e = select(l)) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float length_weight,
+                    int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* steps,
+                    hipStream_t s) {
+  const hipError_t e = beam_steps(a, d, a.plan.fuse_select, s, [&](int l) {
     ProfScope ps(a.prof, CASR_K_SELECT, s);
     switch (a.plan.K2) {
       case 4: launch_beam_select<4>(a, d, l, s); break;
@@ -1922,7 +1930,9 @@ hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float l
       case 16: launch_beam_select<16>(a, d, l, s); break;
       default: launch_beam_select<32>(a, d, l, s);
     }
-  }
+    return hipSuccess;
+  });
+  if (e != hipSuccess) return e;
   if (a.plan.fin_lds)
     hipLaunchKernelGGL(beam_finalize_wave_kernel, dim3(a.B), dim3(64), a.plan.fin_lds, s, a.B, a.k, a.max_len,
                        lm_weight, length_weight, d.score[0], d.score[1], d.bp, d.tk, d.rec_score, d.rec_src,
@@ -1934,11 +1944,10 @@ hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float l
   return hipGetLastError();
 }
 
-hipError_t run_beam_records(const DecodeArgs& a, DecodeBufs& d, int32_t* rec_tokens,
-                            float* rec_score, uint8_t* rec_valid, hipStream_t s) {
-  hipLaunchKernelGGL(beam_records_kernel, dim3(a.B, a.max_len), dim3(64), 0, s, a.B, a.k, a.max_len,
-                     d.bp, d.tk, d.rec_score, d.rec_src, d.rec_valid, d.newdone, rec_tokens,
-                     rec_score, rec_valid, d.err);
+hipError_t run_beam_records(const BeamTree& t, int32_t* rec_tokens, float* rec_score, uint8_t* rec_valid,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(beam_records_kernel, dim3(t.B, t.L), dim3(64), 0, s, t.B, t.k, t.L, t.bp, t.tk, t.rec_score,
+                     t.rec_src, t.rec_valid, t.newdone, rec_tokens, rec_score, rec_valid, t.err);
   return hipGetLastError();
 }
 
@@ -1950,33 +1959,16 @@ hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, 
                        int32_t* best_len, float* best_score, float* best_lm, int32_t* steps, hipStream_t s) {
   const int R = a.B * a.k;
   if (a.plan.caller != PLAN_BEAM_LM || a.plan.fuse_select) return hipErrorInvalidValue;
-  FillList fl;
-  fl.add32(d.newdone, 0, a.max_len);
-  fl.add8(d.topfin, 0, a.B);
-  hipError_t e0 = fill_multi(fl, s);
-  if (e0 != hipSuccess) return e0;
-  hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, a.k,
-                     a.sos, d.tok[0], d.src[0], d.score[0], nullptr);
-  for (int l = 0; l < a.max_len; ++l) {
-    hipError_t e;
-    if (!a.plan.fold) {
-      e = decode_step(a, d, l, a.B, nullptr, s);
-    } else if (l == 0) {
-      e = decode_step(a, d, 0, a.B, nullptr, s, nullptr, false);
-    } else {
-      e = fold_attention_step(a, d, l, a.B, nullptr, false, GreedySel{}, s, nullptr);
-    }
-    if (e == hipSuccess && a.plan.fold) e = fold_gemm_step(a, d, l, a.B, s);
-    if (e != hipSuccess) return e;
+  hipError_t e = beam_steps(a, d, false, s, [&](int l) {
     ProfScope ps(a.prof, CASR_K_SELECT, s);
     const LmTermsSrc src{1, nullptr, nullptr, d.bp, d.tk, d.newdone, l, a.k, a.B, R};
-    e = launch_lm_terms(m, sv, src, R, a.eos, w.terms, d.err, s);
-    if (e != hipSuccess) return e;
+    const hipError_t et = launch_lm_terms(m, sv, src, R, a.eos, w.terms, d.err, s);
+    if (et != hipSuccess) return et;
     const BeamLmArgs g{w.terms, w.g[l & 1], w.g[(l + 1) & 1], w.rec_lm, lm_weight,
                        (float)((double)length_weight * (double)(l + 1))};
-    e = launch_beam_lm_select(beam_sel_args(a, d, l), g, a.plan.K2, s);
-    if (e != hipSuccess) return e;
-  }
+    return launch_beam_lm_select(beam_sel_args(a, d, l), g, a.plan.K2, s);
+  });
+  if (e != hipSuccess) return e;
   return launch_beam_lm_finalize(a, d, w, lm_weight, length_weight, best_tokens, best_len, best_score, best_lm, steps,
                                  s);
 }
@@ -1991,41 +1983,25 @@ hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* l
   const int R = a.B * a.k;
   if (a.plan.caller != PLAN_BEAM_LM || a.plan.fuse_select) return hipErrorInvalidValue;
   if ((lw != nullptr) != (m != nullptr) || (lw != nullptr) != (sv != nullptr)) return hipErrorInvalidValue;
-  FillList fl;
-  fl.add32(d.newdone, 0, a.max_len);
-  fl.add8(d.topfin, 0, a.B);
-  hipError_t e0 = fill_multi(fl, s);
-  if (e0 != hipSuccess) return e0;
-  hipLaunchKernelGGL(decode_init_kernel, dim3(R), dim3(256), 0, s, d.st[0], a.hfin, a.cfin, a.B, a.k,
-                     a.sos, d.tok[0], d.src[0], d.score[0], nullptr);
-  for (int l = 0; l < a.max_len; ++l) {
-    hipError_t e;
-    if (!a.plan.fold) {
-      e = decode_step(a, d, l, a.B, nullptr, s);
-    } else if (l == 0) {
-      e = decode_step(a, d, 0, a.B, nullptr, s, nullptr, false);
-    } else {
-      e = fold_attention_step(a, d, l, a.B, nullptr, false, GreedySel{}, s, nullptr);
-    }
-    if (e == hipSuccess && a.plan.fold) e = fold_gemm_step(a, d, l, a.B, s);
-    if (e != hipSuccess) return e;
+  hipError_t e = beam_steps(a, d, false, s, [&](int l) {
     ProfScope ps(a.prof, CASR_K_SELECT, s);
     const float len_l = (float)((double)length_weight * (double)(l + 1));
     BeamLmArgs g{nullptr, nullptr, nullptr, nullptr, lm_weight, len_l};
+    hipError_t es;
     if (lw) {
       const LmTermsSrc src{1, nullptr, nullptr, d.bp, d.tk, d.newdone, l, a.k, a.B, R};
-      e = launch_lm_terms(*m, *sv, src, R, a.eos, lw->terms, d.err, s);
-      if (e != hipSuccess) return e;
+      es = launch_lm_terms(*m, *sv, src, R, a.eos, lw->terms, d.err, s);
+      if (es != hipSuccess) return es;
       g = BeamLmArgs{lw->terms, lw->g[l & 1], lw->g[(l + 1) & 1], lw->rec_lm, lm_weight, len_l};
     }
     const BiasRowsSrc bsrc{1, w.st[l & 1], d.newdone, l, a.k, a.B};
-    e = launch_bias_rows(bm, bsrc, R, w.gain, nullptr, d.err, s);
-    if (e != hipSuccess) return e;
+    es = launch_bias_rows(bm, bsrc, R, w.gain, nullptr, d.err, s);
+    if (es != hipSuccess) return es;
     const BeamBiasArgs q{bm, w.gain, w.st[l & 1], w.full[l & 1], w.st[(l + 1) & 1], w.full[(l + 1) & 1], w.rec_full,
                          bias_weight};
-    e = launch_beam_bias_select(beam_sel_args(a, d, l), g, q, a.plan.K2, s);
-    if (e != hipSuccess) return e;
-  }
+    return launch_beam_bias_select(beam_sel_args(a, d, l), g, q, a.plan.K2, s);
+  });
+  if (e != hipSuccess) return e;
   return launch_beam_bias_finalize(a, d, lw, w, bm, bias_weight, lm_weight, length_weight, best_tokens, best_len,
                                    best_score, best_lm, best_bias, steps, s);
 }

@@ -333,26 +333,26 @@ size_t carve_mbr(void* base, int B, int L, int k, MbrBufs& w) {
   return c.bytes(256);
 }
 
-hipError_t run_beam_mbr(const DecodeArgs& a, const DecodeBufs& d, const MbrBufs& w, int map, double scale,
-                        const float* rec_lm, double lm_weight, double length_weight, float beam_lm_weight,
-                        float beam_length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
-                        int32_t* best_index, double* best_risk, double* rec_risk, hipStream_t s) {
-  const EditPlan pl = edit_plan_mbr(a.max_len, a.k, map);
+hipError_t run_beam_mbr(const BeamTree& t, const MbrBufs& w, int map, double scale, const float* rec_lm,
+                        double lm_weight, double length_weight, float beam_lm_weight, float beam_length_weight,
+                        int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* best_index,
+                        double* best_risk, double* rec_risk, hipStream_t s) {
+  const EditPlan pl = edit_plan_mbr(t.L, t.k, map);
   if (pl.form == EDIT_FORM_NONE) return hipErrorInvalidValue;
-  const MbrArgs m{a.B, a.k, a.max_len, scale, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
-                  d.score[0], d.score[1], d.bp, d.tk, d.rec_score, d.rec_src, d.rec_valid, d.newdone, rec_lm, w, a.V,
-                  best_tokens, best_len, best_score, best_index, best_risk, rec_risk, d.err};
-  hipLaunchKernelGGL(mbr_prepare_kernel, dim3(a.B), dim3(MBR_THREADS), 0, s, m);
+  const MbrArgs m{t.B, t.k, t.L, scale, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
+                  t.score[0], t.score[1], t.bp, t.tk, t.rec_score, t.rec_src, t.rec_valid, t.newdone, rec_lm, w, t.V,
+                  best_tokens, best_len, best_score, best_index, best_risk, rec_risk, t.err};
+  hipLaunchKernelGGL(mbr_prepare_kernel, dim3(t.B), dim3(MBR_THREADS), 0, s, m);
   if (pl.form == EDIT_FORM_LANE)
-    hipLaunchKernelGGL(mbr_dist_kernel<EDIT_FORM_LANE>, dim3(a.B, pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, m);
+    hipLaunchKernelGGL(mbr_dist_kernel<EDIT_FORM_LANE>, dim3(t.B, pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, m);
   else
-    hipLaunchKernelGGL(mbr_dist_kernel<EDIT_FORM_WAVE>, dim3(a.B, pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, m);
-  hipLaunchKernelGGL(mbr_reduce_kernel, dim3(a.B), dim3(MBR_THREADS), 0, s, m);
+    hipLaunchKernelGGL(mbr_dist_kernel<EDIT_FORM_WAVE>, dim3(t.B, pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, m);
+  hipLaunchKernelGGL(mbr_reduce_kernel, dim3(t.B), dim3(MBR_THREADS), 0, s, m);
   return hipGetLastError();
 }
 
-hipError_t run_mbr_distances(const DecodeArgs& a, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s) {
-  hipLaunchKernelGGL(mbr_expand_kernel, dim3(a.B), dim3(MBR_THREADS), 0, s, w, a.max_len * a.k, dist, n_rec);
+hipError_t run_mbr_distances(const BeamTree& t, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s) {
+  hipLaunchKernelGGL(mbr_expand_kernel, dim3(t.B), dim3(MBR_THREADS), 0, s, w, t.L * t.k, dist, n_rec);
   return hipGetLastError();
 }
 

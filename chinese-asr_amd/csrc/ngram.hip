@@ -264,14 +264,13 @@ __global__ __launch_bounds__(LMR_THREADS) void lm_rescore_kernel(RescoreArgs a) 
 
 bool rescore_supported(int max_len, int k) { return rescore_lds_bytes(max_len, k) <= 64 * 1024; }
 
-hipError_t run_beam_rescore(const DecodeArgs& a, const DecodeBufs& d, const NgramView& m, double lm_weight,
-                            double length_weight, float beam_lm_weight, float beam_length_weight,
-                            int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
-                            float* rec_lm, hipStream_t s) {
-  RescoreArgs r{m, a.B, a.k, a.max_len, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
-                d.score[0], d.score[1], d.bp, d.tk, d.rec_score, d.rec_src, d.rec_valid, d.newdone,
-                best_tokens, best_len, best_score, best_lm, rec_lm, d.err};
-  hipLaunchKernelGGL(lm_rescore_kernel, dim3(a.B), dim3(LMR_THREADS), rescore_lds_bytes(a.max_len, a.k), s, r);
+hipError_t run_beam_rescore(const BeamTree& t, const NgramView& m, double lm_weight, double length_weight,
+                            float beam_lm_weight, float beam_length_weight, int32_t* best_tokens, int32_t* best_len,
+                            float* best_score, float* best_lm, float* rec_lm, hipStream_t s) {
+  RescoreArgs r{m, t.B, t.k, t.L, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
+                t.score[0], t.score[1], t.bp, t.tk, t.rec_score, t.rec_src, t.rec_valid, t.newdone,
+                best_tokens, best_len, best_score, best_lm, rec_lm, t.err};
+  hipLaunchKernelGGL(lm_rescore_kernel, dim3(t.B), dim3(LMR_THREADS), rescore_lds_bytes(t.L, t.k), s, r);
   return hipGetLastError();
 }
 

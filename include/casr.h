@@ -313,7 +313,8 @@ int casr_encoder_results(casr_handle* h, float* enc, float* h_final, float* c_fi
  *   out_len  [B] final_lens (tokens before the first EOS, model.py:573)
  *   finished [B] 0/1, accum [B] accumulated logp (model.py:567-576)
  *   align    NULL or [max_len][Tp][B] attention weights per step (model.py:553)
- * Score = accum / (out_len + finished) is formed by the host (model.py:593). */
+ * Score = accum / (out_len + finished) is formed by the host (model.py:593).
+ * Spends the last beam: its readers return CASR_ERR_STATE afterwards (casr_beam_records). */
 int casr_greedy(casr_handle* h, int32_t* tokens, int32_t* out_len, uint8_t* finished, float* accum,
                 float* align, void* stream);
 
@@ -327,7 +328,14 @@ int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32
 /* Every finished hypothesis of the last casr_beam, for second-pass rescoring on the host
  * (parse_finished_tensors, model.py:708-765):
  *   rec_tokens [B][max_len][k][max_len] (record at step l has l tokens), rec_score
- *   [B][max_len][k], rec_valid [B][max_len][k] (0/1); order = (step, candidate rank). */
+ *   [B][max_len][k], rec_valid [B][max_len][k] (0/1); order = (step, candidate rank).
+ * The readers of a beam (this call, casr_beam_rescore, casr_beam_mbr, casr_beam_mbr_distances,
+ * casr_beam_nbest, casr_beam_confusion, casr_beam_record_lm, casr_beam_record_bias) read the tree and the
+ * records the last beam entry left in the handle's decode workspaces and leave them as they are, so any
+ * number of them may follow one beam in any order.  A casr_encode, casr_encode_fbank, casr_greedy or
+ * casr_score reuses those workspaces and spends the beam: every reader then returns CASR_ERR_STATE
+ * until the next casr_beam, casr_beam_lm or casr_beam_bias.  A beam entry that is refused (a bad k, a
+ * NULL output) leaves the last beam readable. */
 int casr_beam_records(casr_handle* h, int32_t* rec_tokens, float* rec_score, uint8_t* rec_valid,
                       void* stream);
 
@@ -352,7 +360,8 @@ int casr_beam_records(casr_handle* h, int32_t* rec_tokens, float* rec_score, uin
  * on demand): (L + 1) B state rows of 10 KB plus 1 KB of row partials per scored row (118 MB at
  * B = 256, L = 40).  Never replayed as a hipGraph; the timed classes CASR_K_DEC_LSTM, _ATTENTION,
  * _PROJ and _SELECT cover its launches.  Returns after enqueueing; does not disturb the encode: a
- * greedy or beam decode after it gives the bits it gives without it.
+ * greedy or beam decode after it gives the bits it gives without it.  It spends the last beam
+ * (casr_beam_records), as casr_greedy does.
  * CASR_ERR_STATE before an encode or before weights are bound; CASR_ERR_ARG for a NULL handle,
  * targets, tgt_len, token_logp or total_logp, or L out of range; CASR_ERR_UNSUPPORTED when the
  * vocabulary needs more than 64 projection column blocks (V > 5120). */

@@ -172,6 +172,47 @@ def test_mbr_state_errors():
         e2.close()
 
 
+def _record_bytes(e):
+    return [x.cpu().numpy().view(np.uint8) for x in e.beam_records()]
+
+
+def test_readers_leave_the_tree_and_a_spent_beam_is_refused():
+    """(a) the readers only read: the records before and after them are the same bits; (c) a refused
+    casr_beam leaves the last beam readable; (b) casr_greedy and casr_score reuse the decode workspaces,
+    so every reader after them is CASR_ERR_STATE, not the records of a tree that is gone."""
+    e = _engine(25.0)
+    try:
+        _encode(e)
+        e.beam(4)
+        first = _record_bytes(e)
+        assert first[2].any()  # some record is valid: else the comparisons below would pass vacuously
+        recs = records_by_utterance(*(x.cpu().numpy() for x in e.beam_records()))
+        grams, lm, ref = _lm_from_records(recs, 78)
+        e.device_flags()
+        e.beam_mbr(0.5)
+        e.beam_nbest(3)
+        e.beam_confusion()
+        for x, y in zip(first, _record_bytes(e)):
+            assert np.array_equal(x, y)
+        with pytest.raises(L.CasrError, match="CASR_ERR_ARG"):
+            e.beam(0)
+        for x, y in zip(first, _record_bytes(e)):
+            assert np.array_equal(x, y)
+        targets = torch.full((B, 5), 7, dtype=torch.int32)
+        for spend in (e.greedy, lambda: e.score(targets, torch.full((B,), 5, dtype=torch.int32))):
+            e.beam(4)
+            e.beam_records()
+            spend()
+            for reader in (e.beam_records, lambda: e.beam_rescore(lm, 1.5, 1.5), lambda: e.beam_mbr(0.5),
+                           lambda: e.beam_nbest(3), e.beam_confusion):
+                with pytest.raises(L.CasrError, match="CASR_ERR_STATE"):
+                    reader()
+        assert e.device_flags() == 0
+        lm.close()
+    finally:
+        e.close()
+
+
 class _ScoreOnly:
     def score(self, s, bos=True):
         return 0.0
