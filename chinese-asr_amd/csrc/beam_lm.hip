@@ -1,12 +1,14 @@
 // Shallow fusion of the backoff n-gram LM into the beam search's first pass (include/casr.h
 // casr_lm_terms, casr_beam_lm): the term row of a context (ngram_succ.h's row query, one workgroup
 // per row), the select that ranks by (am + lm_weight lm) + len_l and carries am and lm separately,
-// and the final choice.  The decode steps are run_beam's (decoder.hip run_beam_lm drives them).
+// and the final choice; with their BIAS switch the select and the final choice are casr_beam_bias's too.
+// The decode steps are run_beam's (decoder.hip run_beam_lm, run_beam_bias drive them).
 //
 // The term rows go through a workspace [R][V]: lm_terms_kernel writes a row once, the select reads
 // it beside the logits row.  A row is assembled in LDS (4 V bytes), so the successors' scattered
 // overwrites never leave the CU and the row goes out in one coalesced pass.
 #include "beam_select.h"
+#include "beam_tree.h"
 #include "casr_internal.h"
 
 namespace casr {
@@ -408,108 +410,153 @@ hipError_t launch_beam_bias_select(const BeamSelArgs& a, const BeamLmArgs& g, co
 }
 
 // ------------------------------------------------------------------ the final choice
-__device__ __forceinline__ float lmf_comb(float am, float lm, float lmw, float lenw, int l) {
-  const float len_l = (float)((double)lenw * (double)(l + 1));
-  return __fadd_rn(__fadd_rn(am, __fmul_rn(lmw, lm)), len_l);
+__device__ __forceinline__ float bias_of(int c) { return __int2float_rn(c) * (1.f / 256.f); }
+
+// what the final choice reads beside the tree: the LM sums (LM) and the automaton's states and sums (BIAS)
+struct FusedFinArgs {
+  BeamTree t;
+  float lmw, bw, lenw;
+  const float* g[2];
+  const float* rec_lm;
+  const int32_t* st[2];
+  const int32_t* full[2];
+  const int32_t* rec_full;
+  BiasView m;
+  int32_t* best_tokens;
+  int32_t* best_len;
+  float* best_score;
+  float* best_lm;    // or null
+  float* best_bias;  // BIAS
+  int32_t* steps;
+};
+
+// (am + lm_weight lm) + len_l, with BIAS ((am [+ lm_weight lm]) + bias_weight bias) + len_l: every
+// operation rounded on its own
+template <bool LM, bool BIAS>
+__device__ __forceinline__ float fused_comb(const FusedFinArgs& a, float am, float lm, float bias, int l) {
+  const float len_l = (float)((double)a.lenw * (double)(l + 1));
+  float r = am;
+  if (LM) r = __fadd_rn(r, __fmul_rn(a.lmw, lm));
+  if (BIAS) r = __fadd_rn(r, __fmul_rn(a.bw, bias));
+  return __fadd_rn(r, len_l);
 }
 
-// One thread per utterance: the first maximum of (rec_score + lm_weight rec_lm) + len_l over its
-// valid records in (step, rank) order, or without a record the first maximum over the k live rows of
-// the last executed step; tokens by walking the back-pointers.
-__global__ void beam_lm_finalize_kernel(int B, int k, int L, float lmw, float lenw, const float* __restrict__ score0,
-                                        const float* __restrict__ score1, const float* __restrict__ g0,
-                                        const float* __restrict__ g1, const int32_t* __restrict__ bp,
-                                        const int32_t* __restrict__ tk, const float* __restrict__ rec_score,
-                                        const float* __restrict__ rec_lm, const int32_t* __restrict__ rec_src,
-                                        const uint8_t* __restrict__ rec_valid, const int32_t* __restrict__ newdone,
-                                        int32_t* __restrict__ best_tokens, int32_t* __restrict__ best_len,
-                                        float* __restrict__ best_score, float* __restrict__ best_lm,
-                                        int32_t* __restrict__ steps_out, int32_t* __restrict__ err) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  const int steps = lmf_executed_steps(newdone, L, B);
-  if (b == 0) steps_out[0] = steps;
-  if (b >= B) return;
-  const int R = B * k;
+// One thread per utterance: the first maximum of the combined score over its valid records in (step,
+// rank) order (BIAS: bias_closed), or without a record the first maximum over the k live rows of the last
+// executed step (BIAS: bias_open, C + tail(s)); tokens by walking the back-pointers.
+template <bool LM, bool BIAS>
+__global__ void beam_fused_finalize_kernel(FusedFinArgs a) {
+  const BeamTree& t = a.t;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x, k = t.k, L = t.L;
+  const int steps = beam_executed_steps(t.newdone, L, t.B);
+  if (b == 0) a.steps[0] = steps;
+  if (b >= t.B) return;
   int bl = -1, bc = -1;
-  float bv = 0.f, bs = 0.f, bq = 0.f;
+  float bv = 0.f, bs = 0.f, bq = 0.f, bb = 0.f;
   for (int l = 0; l < steps; ++l)
     for (int c = 0; c < k; ++c) {
       const size_t ri = ((size_t)b * L + l) * k + c;
-      if (!rec_valid[ri]) continue;
-      const float v = lmf_comb(rec_score[ri], rec_lm[ri], lmw, lenw, l);
+      if (!t.rec_valid[ri]) continue;
+      const float lm = LM ? a.rec_lm[ri] : 0.f, bias = BIAS ? bias_of(a.rec_full[ri]) : 0.f;
+      const float v = fused_comb<LM, BIAS>(a, t.rec_score[ri], lm, bias, l);
       if (bl < 0 || v > bv) {
         bl = l;
         bc = c;
         bv = v;
-        bs = rec_score[ri];
-        bq = rec_lm[ri];
+        bs = t.rec_score[ri];
+        bq = lm;
+        bb = bias;
       }
     }
-  int32_t* out = best_tokens + (size_t)b * L;
-  int len, slot, from;
+  int32_t* out = a.best_tokens + (size_t)b * L;
+  int len, slot;
   if (bl >= 0) {
     len = bl;
-    slot = rec_src[((size_t)b * L + bl) * k + bc];
-    from = bl - 1;
-  } else {  // the select of step l writes score[(l + 1) & 1]; the last executed step is steps - 1
-    const float* sf = (steps & 1) ? score1 : score0;
-    const float* gf = (steps & 1) ? g1 : g0;
-    const int ll = steps - 1;
-    int bj = 0;
+    slot = t.rec_src[((size_t)b * L + bl) * k + bc];
+  } else {  // the select of step l writes buffer (l + 1) & 1; the last executed step is steps - 1
+    const int w = steps & 1;
+    len = steps;
+    slot = 0;
     for (int j = 0; j < k; ++j) {
-      const float v = lmf_comb(sf[b * k + j], gf[b * k + j], lmw, lenw, ll);
+      const int rw = b * k + j;
+      float bias = 0.f;
+      if (BIAS) {
+        bool sbad = false;
+        const int s = bias_clamp_state(a.m, a.st[w][rw], &sbad);
+        if (sbad) atomicOr(t.err, CASR_DEV_BAD_TOKEN);
+        bias = bias_of(a.full[w][rw] + a.m.node[s].tail);
+      }
+      const float lm = LM ? a.g[w][rw] : 0.f;
+      const float v = fused_comb<LM, BIAS>(a, t.score[w][rw], lm, bias, steps - 1);
       if (j == 0 || v > bv) {
         bv = v;
-        bj = j;
+        slot = j;
+        bs = t.score[w][rw];
+        bq = lm;
+        bb = bias;
       }
     }
-    bs = sf[b * k + bj];
-    bq = gf[b * k + bj];
-    len = ll + 1;
-    slot = bj;
-    from = ll;
   }
-  for (int s = from; s >= 0; --s) {
-    if ((unsigned)slot >= (unsigned)k) {
-      atomicOr(err, CASR_DEV_BAD_BACKPTR);
-      slot = 0;
-    }
-    const size_t ix = (size_t)s * R + b * k + slot;
-    out[s] = tk[ix];
-    slot = bp[ix];
-  }
+  if (beam_walk(TreeGlobal(t, b), k, slot, len - 1, [&](int s, int32_t tok) { out[s] = tok; }))
+    atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
   for (int s = len; s < L; ++s) out[s] = -1;
-  best_len[b] = len;
-  best_score[b] = bs;
-  best_lm[b] = bq;
+  a.best_len[b] = len;
+  a.best_score[b] = bs;
+  if (a.best_lm) a.best_lm[b] = bq;
+  if (BIAS) a.best_bias[b] = bb;
 }
 
-hipError_t launch_beam_lm_finalize(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float lm_weight,
-                                   float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
-                                   float* best_lm, int32_t* steps, hipStream_t s) {
-  hipLaunchKernelGGL(beam_lm_finalize_kernel, dim3((a.B + 63) / 64), dim3(64), 0, s, a.B, a.k, a.max_len, lm_weight,
-                     length_weight, d.score[0], d.score[1], w.g[0], w.g[1], d.bp, d.tk, d.rec_score, w.rec_lm,
-                     d.rec_src, d.rec_valid, d.newdone, best_tokens, best_len, best_score, best_lm, steps, d.err);
+hipError_t launch_beam_fused_finalize(const BeamTree& t, const BeamLmBufs* lw, const BeamBiasBufs* w,
+                                      const BiasView* m, float bias_weight, float lm_weight, float length_weight,
+                                      int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
+                                      float* best_bias, int32_t* steps, hipStream_t s) {
+  if ((w != nullptr) != (m != nullptr) || (!lw && !w)) return hipErrorInvalidValue;
+  FusedFinArgs f{t, lm_weight, bias_weight, length_weight};
+  if (lw) {
+    f.g[0] = lw->g[0], f.g[1] = lw->g[1];
+    f.rec_lm = lw->rec_lm;
+  }
+  if (w) {
+    f.st[0] = w->st[0], f.st[1] = w->st[1];
+    f.full[0] = w->full[0], f.full[1] = w->full[1];
+    f.rec_full = w->rec_full;
+    f.m = *m;
+  }
+  f.best_tokens = best_tokens, f.best_len = best_len, f.best_score = best_score;
+  f.best_lm = best_lm, f.best_bias = best_bias, f.steps = steps;
+  const auto kern = !w ? beam_fused_finalize_kernel<true, false>
+                       : lw ? beam_fused_finalize_kernel<true, true> : beam_fused_finalize_kernel<false, true>;
+  hipLaunchKernelGGL(kern, dim3((t.B + 63) / 64), dim3(64), 0, s, f);
   return hipGetLastError();
 }
 
-// rec_lm of the valid records of the executed steps, 0 elsewhere
-__global__ void beam_record_lm_kernel(int B, int k, int L, const float* __restrict__ rec_lm,
-                                      const uint8_t* __restrict__ rec_valid, const int32_t* __restrict__ newdone,
-                                      float* __restrict__ out) {
-  const size_t n = (size_t)B * L * k;
+// a per-record term of the fused beams as the API gives it: rec_lm as it is, or (rec_lm null) rec_full
+// through bias_of, for the valid records of the executed steps, 0 elsewhere
+__global__ void beam_record_term_kernel(BeamTree t, const float* __restrict__ rec_lm,
+                                        const int32_t* __restrict__ rec_full, float* __restrict__ out) {
+  const size_t n = (size_t)t.B * t.L * t.k;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int steps = lmf_executed_steps(newdone, L, B);
-  const int l = (int)((i / k) % L);
-  out[i] = (l < steps && rec_valid[i]) ? rec_lm[i] : 0.f;
+  const int steps = beam_executed_steps(t.newdone, t.L, t.B);
+  const int l = (int)((i / t.k) % t.L);
+  out[i] = !(l < steps && t.rec_valid[i]) ? 0.f : rec_lm ? rec_lm[i] : bias_of(rec_full[i]);
+}
+
+static hipError_t run_beam_record_term(const BeamTree& t, const float* rec_lm, const int32_t* rec_full, float* out,
+                                       hipStream_t s) {
+  const size_t n = (size_t)t.B * t.L * t.k;
+  hipLaunchKernelGGL(beam_record_term_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t, rec_lm, rec_full,
+                     out);
+  return hipGetLastError();
 }
 
 hipError_t run_beam_record_lm(const BeamTree& t, const BeamLmBufs& w, float* rec_lm, hipStream_t s) {
-  const size_t n = (size_t)t.B * t.L * t.k;
-  hipLaunchKernelGGL(beam_record_lm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t.B, t.k, t.L,
-                     w.rec_lm, t.rec_valid, t.newdone, rec_lm);
-  return hipGetLastError();
+  return run_beam_record_term(t, w.rec_lm, nullptr, rec_lm, s);
+}
+
+hipError_t run_beam_record_bias(const BeamTree& t, const BeamBiasBufs& w, float* rec_bias, hipStream_t s) {
+  return run_beam_record_term(t, nullptr, w.rec_full, rec_bias, s);
 }
 
 }  // namespace casr
+

@@ -570,14 +570,4 @@ __device__ __forceinline__ void beam_select_block(const BeamSelArgs& a, int b, B
   }
 }
 
-// executed loop steps: the step at which the cumulative count of newdone reached `total`, + 1
-__device__ __forceinline__ int lmf_executed_steps(const int32_t* newdone, int L, int total) {
-  int cum = 0;
-  for (int s = 0; s < L; ++s) {
-    cum += newdone[s];
-    if (cum >= total) return s + 1;
-  }
-  return L;
-}
-
 }  // namespace casr

@@ -1,6 +1,7 @@
 // What a handle knows about its last beam search, and which call may read it (include/casr.h: the
 // casr_beam_* readers), once, as plain C++ that the host code (casr_capi.hip) and the sanitizer program
-// (tests/host_plan/beam_state_check.cpp) both compile.
+// (tests/host_plan/beam_state_check.cpp) both compile.  The kernels take BeamTree by value and read it by
+// beam_tree.h's rules.
 //
 // A beam entry (casr_beam, casr_beam_lm, casr_beam_bias) leaves the beam tree and the finished records
 // in the handle's decode workspaces.  BeamState says which entry that was; BeamTree is the read-only

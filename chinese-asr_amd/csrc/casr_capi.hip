@@ -1274,12 +1274,10 @@ static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, De
 }
 
 // a beam entry's decode is prepared: the handle's beam state, and the readers' view of the tree and
-// the records it is about to write (the one place BeamTree is filled)
+// the records it is about to write (casr_internal.h beam_tree_of)
 static void beam_ran(casr_handle* h, int kind, const DecodeArgs& a, float lm_weight, float length_weight) {
-  const DecodeBufs& d = h->d;
   h->beam = BeamState{kind, a.k, lm_weight, length_weight};
-  h->tree = BeamTree{a.B, a.k, a.max_len, a.V, d.bp, d.tk, d.newdone, d.rec_score, d.rec_src, d.rec_valid,
-                     {d.score[0], d.score[1]}, d.err};
+  h->tree = beam_tree_of(a, h->d);
 }
 
 // the gate of the beam's readers (beam_state.h beam_gate) as the API's refusal; why: what the reader

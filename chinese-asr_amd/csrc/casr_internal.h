@@ -400,6 +400,13 @@ struct DecodeArgs {
   FoldBufs fb;           // fold tables and the gates buffer (plan.fold only)
 };
 
+// the view of the tree and the records a beam entry's decode writes (the one place BeamTree is filled):
+// run_beam* finalize through it, casr_capi.hip keeps it in the handle for the readers
+inline BeamTree beam_tree_of(const DecodeArgs& a, const DecodeBufs& d) {
+  return BeamTree{a.B, a.k, a.max_len, a.V, d.bp, d.tk, d.newdone, d.rec_score, d.rec_src, d.rec_valid,
+                  {d.score[0], d.score[1]}, d.err};
+}
+
 // attention.hip: one decode step's additive attention for all R rows (writes ctx into st)
 hipError_t launch_attention_step(const DecodeArgs& a, float* st, const float* qpart, float* align,
                                  int32_t* newdone, int l, int total, hipStream_t s);
@@ -438,8 +445,8 @@ hipError_t run_greedy(const DecodeArgs& a, DecodeBufs& d, int32_t* tokens, int32
 hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float length_weight,
                     int32_t* best_tokens, int32_t* best_len, float* best_score, int32_t* steps,
                     hipStream_t s);
-// The readers of a finished beam take its BeamTree (beam_state.h): casr_capi.hip fills it from the
-// DecodeArgs and DecodeBufs of the beam entry that ran and keeps it in the handle
+// The readers of a finished beam take its BeamTree (beam_state.h): casr_capi.hip keeps the beam_tree_of
+// the beam entry that ran in the handle; their kernels read it by beam_tree.h's rules
 hipError_t run_beam_records(const BeamTree& t, int32_t* rec_tokens, float* rec_score, uint8_t* rec_valid,
                             hipStream_t s);
 
@@ -517,9 +524,6 @@ struct BeamLmArgs {
   float lm_weight, len_l;  // len_l = (float)((double)length_weight (l + 1))
 };
 hipError_t launch_beam_lm_select(const BeamSelArgs& a, const BeamLmArgs& g, int K2, hipStream_t s);
-hipError_t launch_beam_lm_finalize(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs& w, float lm_weight,
-                                   float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
-                                   float* best_lm, int32_t* steps, hipStream_t s);
 hipError_t run_beam_record_lm(const BeamTree& t, const BeamLmBufs& w, float* rec_lm, hipStream_t s);
 // decoder.hip: run_beam's steps (a.plan: the PLAN_BEAM_LM caller's) with the term rows and the fused
 // select after each
@@ -572,11 +576,12 @@ struct BeamBiasArgs {
 // beam_lm.hip: the fused select with the bias row read beside the logits and, with g.terms, the term rows
 hipError_t launch_beam_bias_select(const BeamSelArgs& a, const BeamLmArgs& g, const BeamBiasArgs& q, int K2,
                                    hipStream_t s);
-// lw null: no LM took part
-hipError_t launch_beam_bias_finalize(const DecodeArgs& a, const DecodeBufs& d, const BeamLmBufs* lw,
-                                     const BeamBiasBufs& w, const BiasView& m, float bias_weight, float lm_weight,
-                                     float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
-                                     float* best_lm, float* best_bias, int32_t* steps, hipStream_t s);
+// the final choice of casr_beam_lm and casr_beam_bias over the tree t.  lw null: no LM took part; w and m
+// null: no bias did (one of the two is there)
+hipError_t launch_beam_fused_finalize(const BeamTree& t, const BeamLmBufs* lw, const BeamBiasBufs* w,
+                                      const BiasView* m, float bias_weight, float lm_weight, float length_weight,
+                                      int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm,
+                                      float* best_bias, int32_t* steps, hipStream_t s);
 hipError_t run_beam_record_bias(const BeamTree& t, const BeamBiasBufs& w, float* rec_bias, hipStream_t s);
 // decoder.hip: run_beam_lm's steps with the gain rows (and, with lw, the term rows) before the select
 hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* lw, const BeamBiasBufs& w,

@@ -1,7 +1,8 @@
 // N-best lists and confusion networks over a beam's finished records on the device (include/casr.h
 // casr_confusion, casr_beam_nbest, casr_beam_confusion).  The unit rule, the N-best order, the vote walk,
 // the slot order and the plan are confusion_plan.h's, the text the host compiles too; the list of an
-// utterance's records, c, c_max and the staged beam tree are mbr_device.h's, shared with casr_beam_mbr.
+// utterance's records, c and c_max are mbr_device.h's, shared with casr_beam_mbr; the tree is read by
+// beam_tree.h's rules.
 //
 // Three kernels: prepare (one workgroup per utterance), align (one wave per workgroup, a lane per record)
 // and reduce (one wave per workgroup, a slot at a time).  After the units everything is integer
@@ -13,7 +14,7 @@
 namespace casr {
 
 struct CnArgs {
-  MbrArgs m;   // B, k, L, the weights, the beam state (tree), rec_valid, V, err
+  MbrArgs m;   // the tree (without one: B, k, L, V, rec_valid, err), the weights
   CnBufs w;
   bool tree;   // the records are the handle's beam tree; else the expanded rec_tokens with units given
   int lanes;   // records per align workgroup
@@ -42,8 +43,9 @@ __global__ __launch_bounds__(MBR_THREADS) void cn_prepare_kernel(CnArgs a) {
   __shared__ int wcount[MBR_THREADS / 64];
   __shared__ unsigned long long usum;
   __shared__ int spos;
-  const int b = blockIdx.x, tid = threadIdx.x, k = a.m.k, L = a.m.L, LK = L * k;
-  const int nn = a.tree ? mbr_executed_steps(a.m.newdone, L, a.m.B) * k : LK;
+  const BeamTree& t = a.m.t;
+  const int b = blockIdx.x, tid = threadIdx.x, k = t.k, L = t.L, LK = L * k;
+  const int nn = a.tree ? beam_executed_steps(t.newdone, L, t.B) * k : LK;
   int32_t* list = a.w.list + (size_t)b * LK;
   double* c = a.w.c + (size_t)b * LK;
   if (tid == 0) {
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(MBR_THREADS) void cn_prepare_kernel(CnArgs a) {
   }
   if (a.M > 0 && a.rec_unit)
     for (int i = tid; i < LK; i += MBR_THREADS) a.rec_unit[(size_t)b * LK + i] = 0;
-  const int n = mbr_list_records(a.m.rec_valid + (size_t)b * LK, nn, LK, list, wcount);
+  const int n = mbr_list_records(t.rec_valid + (size_t)b * LK, nn, LK, list, wcount);
   if (tid == 0) a.w.count[b] = n;
   double cmax = NAN;
   if (a.tree) cmax = mbr_comb_records(a.m, b, n, list, c, red);
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(MBR_THREADS) void cn_prepare_kernel(CnArgs a) {
   }
   const bool top = a.M > 0 && !a.pivot;
   if (a.tree && (a.N > 0 || top)) {
-    const int lim = a.N > 0 ? a.N : 1, R = a.m.B * k;
+    const int lim = a.N > 0 ? a.N : 1;
     for (int r = (n < a.N ? n : a.N) + tid; r < a.N; r += MBR_THREADS) {
       const size_t o = (size_t)b * a.N + r;
       a.nbest_index[o] = -1;
@@ -92,16 +94,9 @@ __global__ __launch_bounds__(MBR_THREADS) void cn_prepare_kernel(CnArgs a) {
       a.nbest_len[o] = l;
       a.nbest_comb[o] = cp;
       int32_t* out = a.nbest_tokens + o * L;
-      int slot = mbr_record_slot(a.m, (size_t)b * LK + fp, l, k);
-      for (int st = l - 1; st >= 0; --st) {
-        if ((unsigned)slot >= (unsigned)k) {
-          atomicOr(a.m.err, CASR_DEV_BAD_BACKPTR);
-          slot = 0;
-        }
-        const size_t ix = (size_t)st * R + b * k + slot;
-        out[st] = a.m.tk[ix];
-        slot = a.m.bp[ix];
-      }
+      if (beam_walk(TreeGlobal(t, b), k, t.rec_src[(size_t)b * LK + fp], l - 1,
+                    [&](int st, int32_t tok) { out[st] = tok; }))
+        atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
       for (int st = l; st < L; ++st) out[st] = -1;
     }
   }
@@ -127,7 +122,8 @@ __global__ __launch_bounds__(MBR_THREADS) void cn_prepare_kernel(CnArgs a) {
 template <bool TREE>
 __global__ __launch_bounds__(CN_WAVE) void cn_align_kernel(CnArgs a) {
   extern __shared__ __attribute__((aligned(16))) int32_t csm[];
-  const int b = blockIdx.x, g = blockIdx.y, ln = threadIdx.x, k = a.m.k, L = a.m.L, LK = L * k, V = a.m.V;
+  const BeamTree& t = a.m.t;
+  const int b = blockIdx.x, g = blockIdx.y, ln = threadIdx.x, k = t.k, L = t.L, LK = L * k, V = t.V;
   const int lanes = a.lanes, n = a.w.count[b], ppos = a.w.ppos[b];
   if (ppos < 0 || g * lanes >= n) return;  // (uniform)
   int32_t* ua = csm;  // the pivot [L]
@@ -137,20 +133,17 @@ __global__ __launch_bounds__(CN_WAVE) void cn_align_kernel(CnArgs a) {
   int16_t* tokl = reinterpret_cast<int16_t*>(bits + edit_bits_words(L, L) * lanes);
   uint8_t* col = reinterpret_cast<uint8_t*>(tokl + (size_t)L * lanes);
   if (TREE) {
-    mbr_stage_tree(a.m, b, mbr_executed_steps(a.m.newdone, L, a.m.B) * k, sbp, stk);
+    mbr_stage_tree(t, b, sbp, stk);
     __syncthreads();
   }
+  const TreeStaged<true> tree{sbp, stk, k};
   const int32_t* list = a.w.list + (size_t)b * LK;
   const int fp = list[ppos], m = fp / k;
-  bool bad = false;
+  bool bad = false, bad_bp = false;  // (bad_bp: a record's start slot; the staged pointers are clamped)
   if (TREE) {
-    if (ln == 0) {
-      int slot = mbr_record_slot(a.m, (size_t)b * LK + fp, m, k);
-      for (int st = m - 1; st >= 0; --st) {
-        ua[st] = cn_token(stk[st * k + slot], V);
-        slot = sbp[st * k + slot];
-      }
-    }
+    if (ln == 0)
+      bad_bp = beam_walk(tree, k, t.rec_src[(size_t)b * LK + fp], m - 1,
+                         [&](int st, int32_t tok) { ua[st] = cn_token(tok, V); });
   } else {
     const int32_t* row = a.rec_tokens + ((size_t)b * LK + fp) * L;
     for (int i = ln; i < m; i += CN_WAVE) {
@@ -166,11 +159,8 @@ __global__ __launch_bounds__(CN_WAVE) void cn_align_kernel(CnArgs a) {
   if (ln < lanes && p < n) {
     const int fq = list[p], lq = fq / k;
     if (TREE) {
-      int slot = mbr_record_slot(a.m, (size_t)b * LK + fq, lq, k);
-      for (int st = lq - 1; st >= 0; --st) {
-        tokl[st * lanes + ln] = (int16_t)cn_token(stk[st * k + slot], V);
-        slot = sbp[st * k + slot];
-      }
+      bad_bp |= beam_walk(tree, k, t.rec_src[(size_t)b * LK + fq], lq - 1,
+                          [&](int st, int32_t tok) { tokl[st * lanes + ln] = (int16_t)cn_token(tok, V); });
     } else {
       const int32_t* row = a.rec_tokens + ((size_t)b * LK + fq) * L;
       for (int j = 0; j < lq; ++j) {
@@ -206,7 +196,8 @@ __global__ __launch_bounds__(CN_WAVE) void cn_align_kernel(CnArgs a) {
         [&](int i, int j) { return (int)((bits[edit_bits_word(i, j, stride) * lanes + ln] >> edit_bits_shift(i)) & 3); },
         [&](int j) { return (int32_t)tokl[j * lanes + ln]; }, [&](int s, int32_t t) { v[(size_t)s * LK] = (int16_t)t; });
   }
-  if (bad) atomicOr(a.m.err, CASR_DEV_BAD_TOKEN);
+  if (bad) atomicOr(t.err, CASR_DEV_BAD_TOKEN);
+  if (bad_bp) atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
 }
 
 // ------------------------------------------------------------------ reduce
@@ -218,7 +209,7 @@ __global__ __launch_bounds__(CN_WAVE) void cn_align_kernel(CnArgs a) {
 __global__ __launch_bounds__(CN_WAVE) void cn_reduce_kernel(CnArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];
   __shared__ int ntouched;
-  const int b = blockIdx.x, y = blockIdx.y, ln = threadIdx.x, k = a.m.k, L = a.m.L, LK = L * k, V = a.m.V, M = a.M;
+  const int b = blockIdx.x, y = blockIdx.y, ln = threadIdx.x, k = a.m.t.k, L = a.m.t.L, LK = L * k, V = a.m.t.V, M = a.M;
   const int SM = cn_slots(L), n = a.w.count[b], ppos = a.w.ppos[b];
   const int S = ppos < 0 ? 0 : cn_slots(a.w.list[(size_t)b * LK + ppos] / k);
   for (int s = y; s < SM; s += gridDim.y)
@@ -304,23 +295,11 @@ size_t carve_confusion(void* base, int B, int L, int k, bool votes, CnBufs& w) {
 static CnArgs cn_beam_args(const BeamTree& t, const CnBufs& w, double scale, const float* rec_lm, double lm_weight,
                            double length_weight) {
   CnArgs c{};  // (what is not named stays null: the MBR's outputs and workspace are not read here)
-  c.m.B = t.B;
-  c.m.k = t.k;
-  c.m.L = t.L;
-  c.m.V = t.V;
+  c.m.t = t;
   c.m.scale = scale;
   c.m.lm_weight = lm_weight;
   c.m.length_weight = length_weight;
-  c.m.score0 = t.score[0];
-  c.m.score1 = t.score[1];
-  c.m.bp = t.bp;
-  c.m.tk = t.tk;
-  c.m.rec_score = t.rec_score;
-  c.m.rec_src = t.rec_src;
-  c.m.rec_valid = t.rec_valid;
-  c.m.newdone = t.newdone;
   c.m.rec_lm = rec_lm;
-  c.m.err = t.err;
   c.w = w;
   c.tree = true;
   return c;
@@ -337,12 +316,12 @@ static hipError_t cn_raise(K kernel, bool raise, size_t bytes) {
 // launched nothing
 static hipError_t cn_launch_network(CnArgs& c, const ConfusionPlan& pl, hipStream_t s) {
   c.lanes = pl.lanes;
-  const dim3 ga(c.m.B, pl.align_groups), gr(c.m.B, pl.reduce_groups);
+  const dim3 ga(c.m.t.B, pl.align_groups), gr(c.m.t.B, pl.reduce_groups);
   hipError_t e = c.tree ? cn_raise(cn_align_kernel<true>, pl.align_raise, pl.align_lds)
                         : cn_raise(cn_align_kernel<false>, pl.align_raise, pl.align_lds);
   if (e != hipSuccess) return e;
   if ((e = cn_raise(cn_reduce_kernel, pl.reduce_raise, pl.reduce_lds)) != hipSuccess) return e;
-  hipLaunchKernelGGL(cn_prepare_kernel, dim3(c.m.B), dim3(MBR_THREADS), 0, s, c);
+  hipLaunchKernelGGL(cn_prepare_kernel, dim3(c.m.t.B), dim3(MBR_THREADS), 0, s, c);
   if (c.tree)
     hipLaunchKernelGGL(cn_align_kernel<true>, ga, dim3(CN_WAVE), pl.align_lds, s, c);
   else
@@ -389,12 +368,12 @@ hipError_t run_confusion(const CnBufs& w, const int32_t* rec_tokens, const uint8
   const ConfusionPlan pl = confusion_plan(B, L, k, V, false);
   if (!pl.ok) return hipErrorInvalidValue;
   CnArgs c{};
-  c.m.B = B;
-  c.m.k = k;
-  c.m.L = L;
-  c.m.V = V;
-  c.m.rec_valid = rec_valid;
-  c.m.err = err;
+  c.m.t.B = B;
+  c.m.t.k = k;
+  c.m.t.L = L;
+  c.m.t.V = V;
+  c.m.t.rec_valid = rec_valid;
+  c.m.t.err = err;
   c.w = w;
   c.tree = false;
   c.M = M;

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "beam_select.h"
+#include "beam_tree.h"
 #include "casr_common.h"
 #include "casr_internal.h"
 
@@ -1323,78 +1324,32 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_select_kernel(BeamSe
   beam_select_block<K2, UNIT_T>(a, blockIdx.x, lds, btr, nullptr, nullptr);
 }
 
-// executed loop steps: the step at which the cumulative count reached `total`, + 1
-__device__ __forceinline__ int executed_steps(const int32_t* newdone, int L, int total) {
-  int cum = 0;
-  for (int s = 0; s < L; ++s) {
-    cum += newdone[s];
-    if (cum >= total) return s + 1;
-  }
-  return L;
-}
-
 // one thread per utterance: first-max finished record (model.py:765) or the unfinished
-// fallback (model.py:961-972); tokens recovered by walking the back-pointers.
-__global__ void beam_finalize_kernel(int B, int k, int L, float lm_weight, float length_weight,
-                                     const float* __restrict__ score0,
-                                     const float* __restrict__ score1,
-                                     const int32_t* __restrict__ bp, const int32_t* __restrict__ tk,
-                                     const float* __restrict__ rec_score,
-                                     const int32_t* __restrict__ rec_src,
-                                     const uint8_t* __restrict__ rec_valid,
-                                     const int32_t* __restrict__ newdone, int32_t* __restrict__ best_tokens,
-                                     int32_t* __restrict__ best_len, float* __restrict__ best_score,
-                                     int32_t* __restrict__ steps_out, int32_t* __restrict__ err) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  const int steps = executed_steps(newdone, L, B);
+// fallback (beam_tree.h beam_live_row); tokens recovered by walking the back-pointers.
+__global__ void beam_finalize_kernel(BeamTree t, float lm_weight, float length_weight,
+                                     int32_t* __restrict__ best_tokens, int32_t* __restrict__ best_len,
+                                     float* __restrict__ best_score, int32_t* __restrict__ steps_out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x, k = t.k, L = t.L;
+  const int steps = beam_executed_steps(t.newdone, L, t.B);
   if (b == 0) steps_out[0] = steps;
-  if (b >= B) return;
-  const int R = B * k;
-  // the select of step l writes score[(l+1)&1]; the last executed step is steps-1
-  const float* score_final = (steps & 1) ? score1 : score0;
+  if (b >= t.B) return;
   int bl = -1, bc = -1;
   float bs = 0.f;
   for (int l = 0; l < steps; ++l)
     for (int c = 0; c < k; ++c) {
       const size_t ri = ((size_t)b * L + l) * k + c;
-      if (rec_valid[ri] && (bl < 0 || rec_score[ri] > bs)) {
+      if (t.rec_valid[ri] && (bl < 0 || t.rec_score[ri] > bs)) {
         bl = l;
         bc = c;
-        bs = rec_score[ri];
+        bs = t.rec_score[ri];
       }
     }
   int32_t* out = best_tokens + (size_t)b * L;
-  int len, slot, from;
-  if (bl >= 0) {
-    len = bl;
-    slot = rec_src[((size_t)b * L + bl) * k + bc];
-    from = bl - 1;
-  } else {
-    const int ll = steps - 1;
-    const float lw = (float)((double)length_weight * (double)(ll + 1));
-    int bj = 0;
-    float bsv = 0.f;
-    for (int j = 0; j < k; ++j) {
-      const float s = (score_final[b * k + j] + lm_weight * 0.f) + lw;
-      if (j == 0 || s > bsv) {
-        bsv = s;
-        bj = j;
-      }
-    }
-    bs = bsv;
-    len = ll + 1;
-    slot = bj;
-    from = ll;
-  }
-  for (int s = from; s >= 0; --s) {
-    if ((unsigned)slot >= (unsigned)k) {
-      atomicOr(err, CASR_DEV_BAD_BACKPTR);
-      slot = 0;
-    }
-    const size_t ix = (size_t)s * R + b * k + slot;
-    out[s] = tk[ix];
-    slot = bp[ix];
-  }
+  const int len = bl >= 0 ? bl : steps;
+  const int slot = bl >= 0 ? t.rec_src[((size_t)b * L + bl) * k + bc]
+                           : beam_live_row(t, b, lm_weight, length_weight, steps, &bs);
+  if (beam_walk(TreeGlobal(t, b), k, slot, len - 1, [&](int s, int32_t tok) { out[s] = tok; }))
+    atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
   for (int s = len; s < L; ++s) out[s] = -1;
   best_len[b] = len;
   best_score[b] = bs;
@@ -1405,27 +1360,26 @@ __global__ void beam_finalize_kernel(int B, int k, int L, float lm_weight, float
 // executed-step count from a wave prefix scan of newdone.  beam_finalize_kernel's thread per
 // utterance paid a memory round trip per back-pointer hop and per newdone word (68 us per beam
 // batch at B = 256, L = 40); here lane 0 walks LDS.  Same sequential order: the same bits.
-__global__ __launch_bounds__(64) void beam_finalize_wave_kernel(
-    int B, int k, int L, float lm_weight, float length_weight, const float* __restrict__ score0,
-    const float* __restrict__ score1, const int32_t* __restrict__ bp, const int32_t* __restrict__ tk,
-    const float* __restrict__ rec_score, const int32_t* __restrict__ rec_src, const uint8_t* __restrict__ rec_valid,
-    const int32_t* __restrict__ newdone, int32_t* __restrict__ best_tokens, int32_t* __restrict__ best_len,
-    float* __restrict__ best_score, int32_t* __restrict__ steps_out, int32_t* __restrict__ err) {
+__global__ __launch_bounds__(64) void beam_finalize_wave_kernel(BeamTree t, float lm_weight, float length_weight,
+                                                                int32_t* __restrict__ best_tokens,
+                                                                int32_t* __restrict__ best_len,
+                                                                float* __restrict__ best_score,
+                                                                int32_t* __restrict__ steps_out) {
   extern __shared__ __attribute__((aligned(16))) int32_t fsm[];
-  const int b = blockIdx.x, ln = threadIdx.x, R = B * k, LK = L * k, LKp = (LK + 7) & ~7;
+  const int b = blockIdx.x, ln = threadIdx.x, B = t.B, k = t.k, L = t.L, LK = L * k, LKp = (LK + 7) & ~7;
   int32_t* sbp = fsm;
   int32_t* stk = sbp + LKp;
   float* srs = reinterpret_cast<float*>(stk + LKp);
   uint8_t* srv = reinterpret_cast<uint8_t*>(srs + LKp);
-  // executed_steps(): the first s whose running sum of newdone reaches B (else L)
+  // beam_executed_steps(): the first s whose running sum of newdone reaches B (else L)
   int steps = L, carry = 0;
   for (int s0 = 0; s0 < L; s0 += 64) {
     const int sl = s0 + ln;
-    int v = sl < L ? newdone[sl] : 0;
+    int v = sl < L ? t.newdone[sl] : 0;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(v, o);
-      if (ln >= o) v += t;
+      const int up = __shfl_up(v, o);
+      if (ln >= o) v += up;
     }
     v += carry;
     const unsigned long long hit = __ballot(sl < L && v >= B);
@@ -1437,18 +1391,15 @@ __global__ __launch_bounds__(64) void beam_finalize_wave_kernel(
   }
   if (b == 0 && ln == 0) steps_out[0] = steps;
   const int n = steps * k;
-  for (int i = ln; i < n; i += 64) {
-    const int st = i / k, c = i - st * k;
-    sbp[i] = bp[(size_t)st * R + b * k + c];
-    stk[i] = tk[(size_t)st * R + b * k + c];
-    srs[i] = rec_score[(size_t)b * LK + i];
-    srv[i] = rec_valid[(size_t)b * LK + i];
-  }
+  // (the pointers staged as they are: casr_beam reports a bad one only where its walk follows it)
+  beam_stage_tree<false>(t, b, steps, sbp, stk, ln, 64, [&](int i, int32_t) {
+    srs[i] = t.rec_score[(size_t)b * LK + i];
+    srv[i] = t.rec_valid[(size_t)b * LK + i];
+  });
   for (int i = n + ln; i < ((n + 7) & ~7); i += 64) srv[i] = 0;  // the scan reads 8 at a time
   __syncthreads();
   int len = 0;
   if (ln == 0) {
-    const float* score_final = (steps & 1) ? score1 : score0;
     int bl = -1, bc = -1;
     float bs = 0.f;
     // records in (step, slot) order, 8 per LDS round trip, compared in that order
@@ -1468,36 +1419,11 @@ __global__ __launch_bounds__(64) void beam_finalize_wave_kernel(
       }
     }
     int32_t* out = best_tokens + (size_t)b * L;
-    int slot, from;
-    if (bl >= 0) {
-      len = bl;
-      slot = rec_src[((size_t)b * L + bl) * k + bc];
-      from = bl - 1;
-    } else {
-      const int ll = steps - 1;
-      const float lw = (float)((double)length_weight * (double)(ll + 1));
-      int bj = 0;
-      float bsv = 0.f;
-      for (int j = 0; j < k; ++j) {
-        const float sv = (score_final[b * k + j] + lm_weight * 0.f) + lw;
-        if (j == 0 || sv > bsv) {
-          bsv = sv;
-          bj = j;
-        }
-      }
-      bs = bsv;
-      len = ll + 1;
-      slot = bj;
-      from = ll;
-    }
-    for (int st = from; st >= 0; --st) {
-      if ((unsigned)slot >= (unsigned)k) {
-        atomicOr(err, CASR_DEV_BAD_BACKPTR);
-        slot = 0;
-      }
-      out[st] = stk[st * k + slot];
-      slot = sbp[st * k + slot];
-    }
+    len = bl >= 0 ? bl : steps;
+    const int slot = bl >= 0 ? t.rec_src[((size_t)b * L + bl) * k + bc]
+                             : beam_live_row(t, b, lm_weight, length_weight, steps, &bs);
+    if (beam_walk(TreeStaged<false>{sbp, stk, k}, k, slot, len - 1, [&](int st, int32_t tok) { out[st] = tok; }))
+      atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
     best_len[b] = len;
     best_score[b] = bs;
   }
@@ -1506,18 +1432,13 @@ __global__ __launch_bounds__(64) void beam_finalize_wave_kernel(
 }
 
 // grid (B, L), block 64: expand every finished record's token sequence.
-__global__ void beam_records_kernel(int B, int k, int L, const int32_t* __restrict__ bp,
-                                    const int32_t* __restrict__ tk, const float* __restrict__ rec_score,
-                                    const int32_t* __restrict__ rec_src,
-                                    const uint8_t* __restrict__ rec_valid,
-                                    const int32_t* __restrict__ newdone, int32_t* __restrict__ out_tok,
-                                    float* __restrict__ out_score, uint8_t* __restrict__ out_valid,
-                                    int32_t* __restrict__ err) {
-  const int b = blockIdx.x, l = blockIdx.y, c = threadIdx.x;
+__global__ void beam_records_kernel(BeamTree t, int32_t* __restrict__ out_tok, float* __restrict__ out_score,
+                                    uint8_t* __restrict__ out_valid) {
+  const int b = blockIdx.x, l = blockIdx.y, c = threadIdx.x, k = t.k, L = t.L;
   if (c >= k) return;
-  const int steps = executed_steps(newdone, L, B);
+  const int steps = beam_executed_steps(t.newdone, L, t.B);
   const size_t ri = ((size_t)b * L + l) * k + c;
-  const bool valid = l < steps && rec_valid[ri];
+  const bool valid = l < steps && t.rec_valid[ri];
   out_valid[ri] = valid;
   int32_t* o = out_tok + ri * L;
   if (!valid) {
@@ -1525,18 +1446,9 @@ __global__ void beam_records_kernel(int B, int k, int L, const int32_t* __restri
     out_score[ri] = 0.f;
     return;
   }
-  out_score[ri] = rec_score[ri];
-  int slot = rec_src[ri];
-  const int R = B * k;
-  for (int s = l - 1; s >= 0; --s) {
-    if ((unsigned)slot >= (unsigned)k) {
-      atomicOr(err, CASR_DEV_BAD_BACKPTR);
-      slot = 0;
-    }
-    const size_t ix = (size_t)s * R + b * k + slot;
-    o[s] = tk[ix];
-    slot = bp[ix];
-  }
+  out_score[ri] = t.rec_score[ri];
+  if (beam_walk(TreeGlobal(t, b), k, t.rec_src[ri], l - 1, [&](int s, int32_t tok) { o[s] = tok; }))
+    atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
   for (int s = l; s < L; ++s) o[s] = -1;
 }
 
@@ -1933,21 +1845,19 @@ hipError_t run_beam(const DecodeArgs& a, DecodeBufs& d, float lm_weight, float l
     return hipSuccess;
   });
   if (e != hipSuccess) return e;
+  const BeamTree t = beam_tree_of(a, d);
   if (a.plan.fin_lds)
-    hipLaunchKernelGGL(beam_finalize_wave_kernel, dim3(a.B), dim3(64), a.plan.fin_lds, s, a.B, a.k, a.max_len,
-                       lm_weight, length_weight, d.score[0], d.score[1], d.bp, d.tk, d.rec_score, d.rec_src,
-                       d.rec_valid, d.newdone, best_tokens, best_len, best_score, steps, d.err);
+    hipLaunchKernelGGL(beam_finalize_wave_kernel, dim3(a.B), dim3(64), a.plan.fin_lds, s, t, lm_weight, length_weight,
+                       best_tokens, best_len, best_score, steps);
   else  // (a max_len x k past the LDS: the thread-per-utterance form)
-    hipLaunchKernelGGL(beam_finalize_kernel, dim3((a.B + 63) / 64), dim3(64), 0, s, a.B, a.k, a.max_len,
-                       lm_weight, length_weight, d.score[0], d.score[1], d.bp, d.tk, d.rec_score, d.rec_src,
-                       d.rec_valid, d.newdone, best_tokens, best_len, best_score, steps, d.err);
+    hipLaunchKernelGGL(beam_finalize_kernel, dim3((a.B + 63) / 64), dim3(64), 0, s, t, lm_weight, length_weight,
+                       best_tokens, best_len, best_score, steps);
   return hipGetLastError();
 }
 
 hipError_t run_beam_records(const BeamTree& t, int32_t* rec_tokens, float* rec_score, uint8_t* rec_valid,
                             hipStream_t s) {
-  hipLaunchKernelGGL(beam_records_kernel, dim3(t.B, t.L), dim3(64), 0, s, t.B, t.k, t.L, t.bp, t.tk, t.rec_score,
-                     t.rec_src, t.rec_valid, t.newdone, rec_tokens, rec_score, rec_valid, t.err);
+  hipLaunchKernelGGL(beam_records_kernel, dim3(t.B, t.L), dim3(64), 0, s, t, rec_tokens, rec_score, rec_valid);
   return hipGetLastError();
 }
 
@@ -1969,8 +1879,8 @@ hipError_t run_beam_lm(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs& w, 
     return launch_beam_lm_select(beam_sel_args(a, d, l), g, a.plan.K2, s);
   });
   if (e != hipSuccess) return e;
-  return launch_beam_lm_finalize(a, d, w, lm_weight, length_weight, best_tokens, best_len, best_score, best_lm, steps,
-                                 s);
+  return launch_beam_fused_finalize(beam_tree_of(a, d), &w, nullptr, nullptr, 0.f, lm_weight, length_weight,
+                                    best_tokens, best_len, best_score, best_lm, nullptr, steps, s);
 }
 
 // casr_beam_bias: run_beam_lm's steps (the same plan); after each step the gain rows of the rows'
@@ -2002,8 +1912,8 @@ hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* l
     return launch_beam_bias_select(beam_sel_args(a, d, l), g, q, a.plan.K2, s);
   });
   if (e != hipSuccess) return e;
-  return launch_beam_bias_finalize(a, d, lw, w, bm, bias_weight, lm_weight, length_weight, best_tokens, best_len,
-                                   best_score, best_lm, best_bias, steps, s);
+  return launch_beam_fused_finalize(beam_tree_of(a, d), lw, &w, &bm, bias_weight, lm_weight, length_weight,
+                                    best_tokens, best_len, best_score, best_lm, best_bias, steps, s);
 }
 
 }  // namespace casr

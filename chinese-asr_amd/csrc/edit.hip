@@ -128,11 +128,12 @@ hipError_t launch_edit_pairs(const int32_t* a, const int32_t* a_len, int La, con
 __global__ __launch_bounds__(MBR_THREADS) void mbr_prepare_kernel(MbrArgs a) {
   __shared__ double red[MBR_THREADS];
   __shared__ int wcount[MBR_THREADS / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, LK = a.L * a.k;
-  const int steps = mbr_executed_steps(a.newdone, a.L, a.B);
+  const BeamTree& t = a.t;
+  const int b = blockIdx.x, tid = threadIdx.x, LK = t.L * t.k;
+  const int steps = beam_executed_steps(t.newdone, t.L, t.B);
   int32_t* list = a.w.list + (size_t)b * LK;
   double* w = a.w.w + (size_t)b * LK;
-  const int n = mbr_list_records(a.rec_valid + (size_t)b * LK, steps * a.k, LK, list, wcount);
+  const int n = mbr_list_records(t.rec_valid + (size_t)b * LK, steps * t.k, LK, list, wcount);
   if (tid == 0) a.w.count[b] = n;
   // c of every record (kept in w), c_max over the workgroup
   const double cmax = mbr_comb_records(a, b, n, list, w, red);
@@ -149,34 +150,31 @@ __global__ __launch_bounds__(MBR_THREADS) void mbr_prepare_kernel(MbrArgs a) {
 template <int FORM>
 __global__ __launch_bounds__(EDIT_WAVE) void mbr_dist_kernel(MbrArgs a) {
   extern __shared__ __attribute__((aligned(16))) int32_t esm[];
-  const int b = blockIdx.x, ln = threadIdx.x, k = a.k, L = a.L, LK = L * k;
+  const BeamTree& t = a.t;
+  const int b = blockIdx.x, ln = threadIdx.x, k = t.k, L = t.L, LK = L * k;
   const int n = a.w.count[b];
   if (n < 2) return;  // (uniform)
-  const int steps = mbr_executed_steps(a.newdone, L, a.B);
   int32_t* sbp = esm;
   int32_t* stk = sbp + LK;
   int32_t* ua = stk + LK;  // record p's tokens [L]
-  mbr_stage_tree(a, b, steps * k, sbp, stk);
+  mbr_stage_tree(t, b, sbp, stk);
   __syncthreads();
+  const TreeStaged<true> tree{sbp, stk, k};
+  bool bad_bp = false;  // a record's start slot outside [0, k) (the staged pointers are clamped)
   const int32_t* list = a.w.list + (size_t)b * LK;
   uint8_t* dist = a.w.dist + (size_t)b * LK * LK;
   for (int p = 1 + blockIdx.y; p < n; p += gridDim.y) {
     const int fp = list[p], lp = fp / k;
-    int slot = mbr_record_slot(a, (size_t)b * LK + fp, lp, k);
+    const int slot = t.rec_src[(size_t)b * LK + fp];
     if (FORM == EDIT_FORM_LANE) {
       uint8_t* row = reinterpret_cast<uint8_t*>(ua + L);  // [L + 1][64]
-      for (int st = lp - 1; st >= 0; --st) {
-        ua[lp - 1 - st] = stk[st * k + slot];
-        slot = sbp[st * k + slot];
-      }
+      bad_bp |= beam_walk(tree, k, slot, lp - 1, [&](int st, int32_t tok) { ua[lp - 1 - st] = tok; });
       for (int q = ln; q < p; q += EDIT_WAVE) {
         const int fq = list[q], lq = fq / k;
-        int sq = mbr_record_slot(a, (size_t)b * LK + fq, lq, k);
+        int sq = beam_record_slot(t, (size_t)b * LK + fq, lq, &bad_bp);
         for (int c = 0; c <= lp; ++c) row[c * EDIT_WAVE + ln] = (uint8_t)c;
         for (int r = 1; r <= lq; ++r) {
-          const int st = lq - r;
-          const int32_t tok = stk[st * k + sq];
-          sq = sbp[st * k + sq];
+          const int32_t tok = beam_hop(tree, lq - r, &sq);
           int diag = row[ln], left = r;
           row[ln] = (uint8_t)r;
           for (int c = 1; c <= lp; ++c) {
@@ -192,17 +190,11 @@ __global__ __launch_bounds__(EDIT_WAVE) void mbr_dist_kernel(MbrArgs a) {
     } else {
       int32_t* ub = ua + L;
       int32_t* carry = ub + L;  // [L + 1]
-      for (int st = lp - 1; st >= 0; --st) {
-        ua[st] = stk[st * k + slot];
-        slot = sbp[st * k + slot];
-      }
+      bad_bp |= beam_walk(tree, k, slot, lp - 1, [&](int st, int32_t tok) { ua[st] = tok; });
       for (int q = 0; q < p; ++q) {
         const int fq = list[q], lq = fq / k;
-        int sq = mbr_record_slot(a, (size_t)b * LK + fq, lq, k);
-        for (int st = lq - 1; st >= 0; --st) {
-          ub[st] = stk[st * k + sq];
-          sq = sbp[st * k + sq];
-        }
+        bad_bp |= beam_walk(tree, k, t.rec_src[(size_t)b * LK + fq], lq - 1,
+                            [&](int st, int32_t tok) { ub[st] = tok; });
         __syncthreads();
         const int d = edit_wave_sweep<false>(ua, lp, ub, lq, carry, nullptr);
         if (ln == 0) dist[(size_t)p * LK + q] = (uint8_t)d;
@@ -210,6 +202,7 @@ __global__ __launch_bounds__(EDIT_WAVE) void mbr_dist_kernel(MbrArgs a) {
       }
     }
   }
+  if (bad_bp) atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
 }
 
 // One workgroup per utterance: risk_p = sum_q w_q d(p, q) in ascending q, the winner by mbr_better, its
@@ -217,7 +210,8 @@ __global__ __launch_bounds__(EDIT_WAVE) void mbr_dist_kernel(MbrArgs a) {
 __global__ __launch_bounds__(MBR_THREADS) void mbr_reduce_kernel(MbrArgs a) {
   __shared__ double redr[MBR_THREADS];
   __shared__ int32_t redi[MBR_THREADS];
-  const int b = blockIdx.x, tid = threadIdx.x, k = a.k, L = a.L, LK = L * k, R = a.B * k;
+  const BeamTree& t = a.t;
+  const int b = blockIdx.x, tid = threadIdx.x, k = t.k, L = t.L, LK = L * k;
   const int n = a.w.count[b];
   const int32_t* list = a.w.list + (size_t)b * LK;
   const double* w = a.w.w + (size_t)b * LK;
@@ -254,52 +248,27 @@ __global__ __launch_bounds__(MBR_THREADS) void mbr_reduce_kernel(MbrArgs a) {
   __syncthreads();  // (redi[0] is rewritten below as the length)
   int32_t* out = a.best_tokens + (size_t)b * L;
   if (win >= 0 ? (bi == win) : (tid == 0)) {
-    int len, slot, from;
+    int len, slot;
     float bs;
     if (win >= 0) {
       const int fi = list[win];
       const size_t ri = (size_t)b * LK + fi;
       len = fi / k;
-      slot = a.rec_src[ri];
-      from = len - 1;
-      bs = a.rec_score[ri];
+      slot = t.rec_src[ri];
+      bs = t.rec_score[ri];
       if (a.best_index) a.best_index[b] = fi;
       if (a.best_risk) a.best_risk[b] = br;
-    } else {  // no record: casr_beam's unfinished fallback (model.py:961-972), its weights, its bits
-      const int steps = mbr_executed_steps(a.newdone, L, a.B);
-      const float* score_final = (steps & 1) ? a.score1 : a.score0;
-      const int ll = steps - 1;
-      const float lw = (float)((double)a.beam_length_weight * (double)(ll + 1));
-      int bj = 0;
-      float bsv = 0.f;
-      for (int j = 0; j < k; ++j) {
-        const float sv = (score_final[b * k + j] + a.beam_lm_weight * 0.f) + lw;
-        if (j == 0 || sv > bsv) {
-          bsv = sv;
-          bj = j;
-        }
-      }
-      bs = bsv;
-      len = ll + 1;
-      slot = bj;
-      from = ll;
+    } else {  // no record: casr_beam's unfinished fallback with its weights
+      len = beam_executed_steps(t.newdone, L, t.B);
+      slot = beam_live_row(t, b, a.beam_lm_weight, a.beam_length_weight, len, &bs);
       if (a.best_index) a.best_index[b] = -1;
       if (a.best_risk) a.best_risk[b] = 0.0;
     }
-    bool bad_bp = false;
-    for (int st = from; st >= 0; --st) {
-      if ((unsigned)slot >= (unsigned)k) {
-        bad_bp = true;
-        slot = 0;
-      }
-      const size_t ix = (size_t)st * R + b * k + slot;
-      out[st] = a.tk[ix];
-      slot = a.bp[ix];
-    }
+    const bool bad_bp = beam_walk(TreeGlobal(t, b), k, slot, len - 1, [&](int st, int32_t tok) { out[st] = tok; });
     a.best_len[b] = len;
     a.best_score[b] = bs;
     redi[0] = len;
-    if (bad_bp) atomicOr(a.err, CASR_DEV_BAD_BACKPTR);
+    if (bad_bp) atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
   }
   __syncthreads();
   const int len = redi[0];
@@ -339,9 +308,8 @@ hipError_t run_beam_mbr(const BeamTree& t, const MbrBufs& w, int map, double sca
                         double* best_risk, double* rec_risk, hipStream_t s) {
   const EditPlan pl = edit_plan_mbr(t.L, t.k, map);
   if (pl.form == EDIT_FORM_NONE) return hipErrorInvalidValue;
-  const MbrArgs m{t.B, t.k, t.L, scale, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
-                  t.score[0], t.score[1], t.bp, t.tk, t.rec_score, t.rec_src, t.rec_valid, t.newdone, rec_lm, w, t.V,
-                  best_tokens, best_len, best_score, best_index, best_risk, rec_risk, t.err};
+  const MbrArgs m{t, scale, lm_weight, length_weight, beam_lm_weight, beam_length_weight, rec_lm, w,
+                  best_tokens, best_len, best_score, best_index, best_risk, rec_risk};
   hipLaunchKernelGGL(mbr_prepare_kernel, dim3(t.B), dim3(MBR_THREADS), 0, s, m);
   if (pl.form == EDIT_FORM_LANE)
     hipLaunchKernelGGL(mbr_dist_kernel<EDIT_FORM_LANE>, dim3(t.B, pl.grid), dim3(EDIT_WAVE), pl.lds_bytes, s, m);

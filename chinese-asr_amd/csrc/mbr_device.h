@@ -1,7 +1,8 @@
 // Device text that the kernels over a beam's finished records share (edit.hip: casr_beam_mbr;
-// confusion.hip: casr_beam_nbest, casr_beam_confusion): the arguments, the executed steps, the list of an
-// utterance's valid records with c and c_max, and the beam tree staged in LDS.
+// confusion.hip: casr_beam_nbest, casr_beam_confusion): the arguments and the list of an utterance's valid
+// records with c and c_max.  How the tree is read (executed steps, staging, walks) is beam_tree.h's.
 #pragma once
+#include "beam_tree.h"
 #include "casr_internal.h"
 #include "edit_plan.h"
 
@@ -9,38 +10,18 @@ namespace casr {
 
 constexpr int MBR_THREADS = 256;
 
-// executed loop steps: the step at which the cumulative count of newdone reached `total`, + 1 (else L)
-__device__ __forceinline__ int mbr_executed_steps(const int32_t* newdone, int L, int total) {
-  int cum = 0;
-  for (int s = 0; s < L; ++s) {
-    cum += newdone[s];
-    if (cum >= total) return s + 1;
-  }
-  return L;
-}
-
 struct MbrArgs {
-  int B, k, L;
+  BeamTree t;
   double scale, lm_weight, length_weight;
   float beam_lm_weight, beam_length_weight;  // casr_beam's (the unfinished fallback)
-  const float* score0;
-  const float* score1;
-  const int32_t* bp;
-  const int32_t* tk;
-  const float* rec_score;
-  const int32_t* rec_src;
-  const uint8_t* rec_valid;
-  const int32_t* newdone;
   const float* rec_lm;  // or null
   MbrBufs w;
-  int V;
   int32_t* best_tokens;
   int32_t* best_len;
   float* best_score;
   int32_t* best_index;  // or null
   double* best_risk;    // or null
   double* rec_risk;     // or null
-  int32_t* err;
 };
 
 // A workgroup of MBR_THREADS: the flat indices i < nn with valid[i], ascending, into list; returns their
@@ -70,12 +51,12 @@ __device__ __forceinline__ int mbr_list_records(const uint8_t* valid, int nn, in
 // c of the listed records of utterance b into c[0 .. n); returns c_max.  red: LDS [MBR_THREADS] doubles
 __device__ __forceinline__ double mbr_comb_records(const MbrArgs& a, int b, int n, const int32_t* list, double* c,
                                                    double* red) {
-  const int tid = threadIdx.x, k = a.k, LK = a.L * k;
+  const int tid = threadIdx.x, k = a.t.k, LK = a.t.L * k;
   double cm = NAN;
   for (int p = tid; p < n; p += MBR_THREADS) {
     const int i = list[p];
     const size_t ri = (size_t)b * LK + i;
-    const double v = mbr_comb(a.rec_score[ri], a.rec_lm ? a.rec_lm[ri] : 0.f, i / k, a.lm_weight, a.length_weight);
+    const double v = mbr_comb(a.t.rec_score[ri], a.rec_lm ? a.rec_lm[ri] : 0.f, i / k, a.lm_weight, a.length_weight);
     c[p] = v;
     cm = mbr_cmax(cm, v);
   }
@@ -88,38 +69,17 @@ __device__ __forceinline__ double mbr_comb_records(const MbrArgs& a, int b, int 
   return red[0];
 }
 
-// stage the beam tree of utterance b (beam_finalize's layout: [step][slot]); a back-pointer outside
-// [0, k) is clamped, a token outside [0, V) is kept as it is; both are reported
-__device__ __forceinline__ void mbr_stage_tree(const MbrArgs& a, int b, int nn, int32_t* sbp, int32_t* stk) {
-  const int k = a.k, R = a.B * k;
-  bool bad_tok = false, bad_bp = false;
-  for (int i = threadIdx.x; i < nn; i += blockDim.x) {
-    const int st = i / k, c = i - st * k;
-    const size_t ix = (size_t)st * R + b * k + c;
-    int p = a.bp[ix];
-    if ((unsigned)p >= (unsigned)k) {
-      if (st > 0) bad_bp = true;  // (step 0 has no predecessor node: its pointer is never followed)
-      p = 0;
-    }
-    const int t = a.tk[ix];
-    if ((unsigned)t >= (unsigned)a.V) bad_tok = true;
-    sbp[i] = p;
-    stk[i] = t;
-  }
+// stage the executed steps of utterance b (beam_tree.h) for a workgroup; a token outside [0, V) is kept
+// as it is and reported, as a clamped back-pointer is
+__device__ __forceinline__ void mbr_stage_tree(const BeamTree& t, int b, int32_t* sbp, int32_t* stk) {
+  bool bad_tok = false;
+  const int steps = beam_executed_steps(t.newdone, t.L, t.B);
+  const bool bad_bp = beam_stage_tree<true>(t, b, steps, sbp, stk, threadIdx.x, blockDim.x,
+                                            [&](int, int32_t tok) { bad_tok |= (unsigned)tok >= (unsigned)t.V; });
   if (blockIdx.y == 0) {
-    if (bad_tok) atomicOr(a.err, CASR_DEV_BAD_TOKEN);
-    if (bad_bp) atomicOr(a.err, CASR_DEV_BAD_BACKPTR);
+    if (bad_tok) atomicOr(t.err, CASR_DEV_BAD_TOKEN);
+    if (bad_bp) atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
   }
-}
-
-// the slot a record's walk starts from (step l - 1), clamped
-__device__ __forceinline__ int mbr_record_slot(const MbrArgs& a, size_t ri, int l, int k) {
-  int slot = a.rec_src[ri];
-  if ((unsigned)slot >= (unsigned)k) {
-    if (l > 0) atomicOr(a.err, CASR_DEV_BAD_BACKPTR);
-    slot = 0;
-  }
-  return slot;
 }
 
 }  // namespace casr

@@ -8,6 +8,7 @@
 // and the rescore computes one term per beam-tree NODE, not per record token: a word's term depends
 // only on its at most three predecessors, which every hypothesis through that node shares.  An
 // utterance has at most steps x k nodes and as many records, so it makes at most 2 steps k queries.
+#include "beam_tree.h"
 #include "casr_internal.h"
 
 namespace casr {
@@ -64,35 +65,16 @@ __device__ __forceinline__ bool lmr_better(double ca, int ia, double cb, int ib)
   return ia < ib;
 }
 
-// executed loop steps: the step at which the cumulative count of newdone reached B, + 1 (else L)
-__device__ __forceinline__ int lmr_executed_steps(const int32_t* newdone, int L, int total) {
-  int cum = 0;
-  for (int s = 0; s < L; ++s) {
-    cum += newdone[s];
-    if (cum >= total) return s + 1;
-  }
-  return L;
-}
-
 struct RescoreArgs {
   NgramView m;
-  int B, k, L;
+  BeamTree t;
   double lm_weight, length_weight;  // the second pass's
   float beam_lm_weight, beam_length_weight;  // casr_beam's (the unfinished fallback)
-  const float* score0;
-  const float* score1;
-  const int32_t* bp;
-  const int32_t* tk;
-  const float* rec_score;
-  const int32_t* rec_src;
-  const uint8_t* rec_valid;
-  const int32_t* newdone;
   int32_t* best_tokens;
   int32_t* best_len;
   float* best_score;
   float* best_lm;  // or null
   float* rec_lm;   // or null
-  int32_t* err;
 };
 
 // LDS of one workgroup: back-pointers, tokens, LM ids and prefix sums [L k] each, then the reduction
@@ -103,7 +85,8 @@ inline size_t rescore_lds_bytes(int L, int k) {
 // One workgroup per utterance.
 __global__ __launch_bounds__(LMR_THREADS) void lm_rescore_kernel(RescoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) int32_t rsm[];
-  const int b = blockIdx.x, tid = threadIdx.x, k = a.k, L = a.L, R = a.B * k, LK = L * k;
+  const BeamTree& t = a.t;
+  const int b = blockIdx.x, tid = threadIdx.x, k = t.k, L = t.L, LK = L * k;
   double* redc = reinterpret_cast<double*>(rsm);  // first: 8-byte aligned
   int32_t* redi = reinterpret_cast<int32_t*>(redc + LMR_THREADS);
   int32_t* sbp = redi + LMR_THREADS;
@@ -111,25 +94,14 @@ __global__ __launch_bounds__(LMR_THREADS) void lm_rescore_kernel(RescoreArgs a) 
   int32_t* sid = stk + LK;
   float* pre = reinterpret_cast<float*>(sid + LK);
   const NgramView& m = a.m;
-  const int steps = lmr_executed_steps(a.newdone, L, a.B);
+  const int steps = beam_executed_steps(t.newdone, L, t.B);
   const int n = steps * k;
-  bool bad_tok = false, bad_bp = false;
+  bool bad_tok = false;
 
-  // stage the executed steps' back-pointers and tokens (beam_finalize's layout: [step][slot]); a token
-  // outside [0, V) scores as <unk>, a back-pointer outside [0, k) is clamped; both are reported
-  for (int i = tid; i < n; i += LMR_THREADS) {
-    const int st = i / k, c = i - st * k;
-    const size_t ix = (size_t)st * R + b * k + c;
-    int p = a.bp[ix];
-    if ((unsigned)p >= (unsigned)k) {
-      if (st > 0) bad_bp = true;  // (step 0 has no predecessor node: its pointer is never followed)
-      p = 0;
-    }
-    const int t = a.tk[ix];
-    sbp[i] = p;
-    stk[i] = t;
-    sid[i] = ngram_lm_id(m, t, m.V, &bad_tok);
-  }
+  // stage the executed steps (beam_tree.h: [step][slot], back-pointers clamped) with the tokens' LM ids
+  // beside; a token outside [0, V) scores as <unk>; both are reported
+  bool bad_bp = beam_stage_tree<true>(t, b, steps, sbp, stk, tid, LMR_THREADS,
+                                      [&](int i, int32_t tok) { sid[i] = ngram_lm_id(m, tok, m.V, &bad_tok); });
   __syncthreads();
 
   // node terms: the word of node (st, c) after its at most order - 1 ancestors, <s> before step 0
@@ -164,15 +136,11 @@ __global__ __launch_bounds__(LMR_THREADS) void lm_rescore_kernel(RescoreArgs a) 
   float bq = 0.f;
   for (int i = tid; i < LK; i += LMR_THREADS) {
     const size_t ri = (size_t)b * LK + i;
-    const bool valid = i < n && a.rec_valid[ri];
+    const bool valid = i < n && t.rec_valid[ri];
     float q = 0.f;
     if (valid) {
       const int l = i / k;
-      int slot = a.rec_src[ri];
-      if ((unsigned)slot >= (unsigned)k) {
-        if (l > 0) bad_bp = true;
-        slot = 0;
-      }
+      int slot = beam_record_slot(t, ri, l, &bad_bp);
       int c[NGRAM_MAX_ORDER - 1] = {0, 0, 0};
       int nc = 0, st = l - 1;
       const int src = slot;
@@ -188,7 +156,7 @@ __global__ __launch_bounds__(LMR_THREADS) void lm_rescore_kernel(RescoreArgs a) 
       const float te = ngram_term(m, c, nc, eos_id);
       q = l == 0 ? te : pre[(l - 1) * k + src] + te;
       // comb = (logp + lm_w q) + len_w l, each one IEEE double operation (never contracted to an fma)
-      const double comb = __dadd_rn(__dadd_rn((double)a.rec_score[ri], __dmul_rn(a.lm_weight, (double)q)),
+      const double comb = __dadd_rn(__dadd_rn((double)t.rec_score[ri], __dmul_rn(a.lm_weight, (double)q)),
                                     __dmul_rn(a.length_weight, (double)l));
       if (lmr_better(comb, i, bc, bi)) {
         bc = comb;
@@ -214,52 +182,29 @@ __global__ __launch_bounds__(LMR_THREADS) void lm_rescore_kernel(RescoreArgs a) 
   // the winner's owner (or thread 0 for the unfinished fallback) walks the back-pointers in LDS
   int32_t* out = a.best_tokens + (size_t)b * L;
   if (win >= 0 ? (bi == win) : (tid == 0)) {
-    int len, slot, from;
-    float bs, lmq;
+    int len, slot;
+    float bs;
     if (win >= 0) {
       const size_t ri = (size_t)b * LK + win;
       len = win / k;
-      slot = a.rec_src[ri];
-      from = len - 1;
-      bs = a.rec_score[ri];
-      lmq = bq;
-    } else {  // no record: casr_beam's unfinished fallback (model.py:961-972), its weights, its bits
-      const float* score_final = (steps & 1) ? a.score1 : a.score0;
-      const int ll = steps - 1;
-      const float lw = (float)((double)a.beam_length_weight * (double)(ll + 1));
-      int bj = 0;
-      float bsv = 0.f;
-      for (int j = 0; j < k; ++j) {
-        const float sv = (score_final[b * k + j] + a.beam_lm_weight * 0.f) + lw;
-        if (j == 0 || sv > bsv) {
-          bsv = sv;
-          bj = j;
-        }
-      }
-      bs = bsv;
-      len = ll + 1;
-      slot = bj;
-      from = ll;
-      lmq = 0.f;
+      slot = t.rec_src[ri];
+      bs = t.rec_score[ri];
+    } else {  // no record: casr_beam's unfinished fallback with its weights, LM sum 0
+      len = steps;
+      slot = beam_live_row(t, b, a.beam_lm_weight, a.beam_length_weight, steps, &bs);
+      bq = 0.f;
     }
-    for (int st = from; st >= 0; --st) {
-      if ((unsigned)slot >= (unsigned)k) {
-        bad_bp = true;
-        slot = 0;
-      }
-      out[st] = stk[st * k + slot];
-      slot = sbp[st * k + slot];
-    }
+    bad_bp |= beam_walk(TreeStaged<true>{sbp, stk, k}, k, slot, len - 1, [&](int st, int32_t tok) { out[st] = tok; });
     a.best_len[b] = len;
     a.best_score[b] = bs;
-    if (a.best_lm) a.best_lm[b] = lmq;
+    if (a.best_lm) a.best_lm[b] = bq;
     redi[0] = len;
   }
   __syncthreads();
   const int len = redi[0];
   for (int st = len + tid; st < L; st += LMR_THREADS) out[st] = -1;
-  if (bad_tok) atomicOr(a.err, CASR_DEV_BAD_TOKEN);
-  if (bad_bp) atomicOr(a.err, CASR_DEV_BAD_BACKPTR);
+  if (bad_tok) atomicOr(t.err, CASR_DEV_BAD_TOKEN);
+  if (bad_bp) atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
 }
 
 bool rescore_supported(int max_len, int k) { return rescore_lds_bytes(max_len, k) <= 64 * 1024; }
@@ -267,9 +212,8 @@ bool rescore_supported(int max_len, int k) { return rescore_lds_bytes(max_len, k
 hipError_t run_beam_rescore(const BeamTree& t, const NgramView& m, double lm_weight, double length_weight,
                             float beam_lm_weight, float beam_length_weight, int32_t* best_tokens, int32_t* best_len,
                             float* best_score, float* best_lm, float* rec_lm, hipStream_t s) {
-  RescoreArgs r{m, t.B, t.k, t.L, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
-                t.score[0], t.score[1], t.bp, t.tk, t.rec_score, t.rec_src, t.rec_valid, t.newdone,
-                best_tokens, best_len, best_score, best_lm, rec_lm, t.err};
+  RescoreArgs r{m, t, lm_weight, length_weight, beam_lm_weight, beam_length_weight,
+                best_tokens, best_len, best_score, best_lm, rec_lm};
   hipLaunchKernelGGL(lm_rescore_kernel, dim3(t.B), dim3(LMR_THREADS), rescore_lds_bytes(t.L, t.k), s, r);
   return hipGetLastError();
 }
