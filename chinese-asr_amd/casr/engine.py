@@ -414,6 +414,62 @@ class Engine:
         _lib.check(self.lib.casr_beam_record_bias(self.handle, _ptr(rec_bias), _stream()), self.handle)
         return rec_bias
 
+    def grammar_accept(self, grammar, tokens, lens):
+        """(consumed, state, accepted) [n] of the rows tokens [n, L] (1 <= L <= 512) with lens [n] under a
+        casr.grammar.Grammar, on the device (casr_grammar_accept): Grammar.walk's values."""
+        dev = self.device
+        tokens = torch.as_tensor(tokens).to(dev, torch.int32).contiguous()
+        lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
+        if tokens.dim() != 2 or lens.shape != (tokens.shape[0],):
+            raise ValueError("grammar_accept: tokens must be [n, L] and lens [n]")
+        n, L = tokens.shape
+        consumed, state = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        ok = torch.empty(n, dtype=torch.uint8, device=dev)
+        _lib.check(self.lib.casr_grammar_accept(self.handle, grammar.on(self), _ptr(tokens), _ptr(lens), n, L,
+                                                _ptr(consumed), _ptr(state), _ptr(ok), _stream()), self.handle)
+        self._keep_grammar = (grammar, tokens, lens)  # read by the enqueued kernel
+        return consumed, state, ok
+
+    def grammar_rows(self, grammar, state, budget):
+        """mask int32 [n, mask_words] (the uint32 words' bits) of grammar states [n] under budgets [n] on
+        the device (casr_grammar_rows): Grammar.rows' values."""
+        dev = self.device
+        state = torch.as_tensor(state).to(dev, torch.int32).contiguous().reshape(-1)
+        n = state.shape[0]
+        budget = torch.as_tensor(budget).to(dev, torch.int32).broadcast_to(state.shape).contiguous()
+        mask = torch.empty(n, grammar.mask_words, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.casr_grammar_rows(self.handle, grammar.on(self), _ptr(state), _ptr(budget), n,
+                                              _ptr(mask), _stream()), self.handle)
+        self._keep_grammar = (grammar, state, budget)  # read by the enqueued kernel
+        return mask
+
+    def beam_grammar(self, grammar, k, lm=None, lm_weight=0.0, length_weight=0.0, start=None):
+        """Beam search over the sentences of a casr.grammar.Grammar and, with ``lm`` (a
+        casr.ngram.NgramLM), the n-gram LM in the first pass (casr_beam_grammar).  ``start`` [B]: the
+        grammar state each utterance starts in (None: state 0; Grammar.union gives the states).  Returns
+        tokens [B, max_len] (-1 past the length), length [B], score [B] (the choice's acoustic
+        log-probability), lm [B] (its LM score; None without an LM), complete [B] (1 where the choice is
+        a finished sentence of the grammar) and steps [1]."""
+        B, L = self._B, self.cfg.max_len
+        dev = self.device
+        if start is not None:
+            start = torch.as_tensor(start).to(dev, torch.int32).contiguous().reshape(-1)
+            if start.shape[0] != B:
+                raise ValueError(f"beam_grammar: start must be [{B}]")
+        toks = torch.empty(B, L, dtype=torch.int32, device=dev)
+        blen = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        best_lm = torch.empty(B, dtype=torch.float32, device=dev) if lm is not None else None
+        complete = torch.empty(B, dtype=torch.uint8, device=dev)
+        steps = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.casr_beam_grammar(self.handle, grammar.on(self), lm.on(self) if lm is not None else None,
+                                              _ptr(start), int(k), ctypes.c_float(lm_weight),
+                                              ctypes.c_float(length_weight), _ptr(toks), _ptr(blen), _ptr(score),
+                                              _ptr(best_lm), _ptr(complete), _ptr(steps), _stream()), self.handle)
+        self._k = k
+        self._keep_lm = (lm, grammar, start)
+        return dict(tokens=toks, length=blen, score=score, lm=best_lm, complete=complete, steps=steps)
+
     def edit_distance(self, a, a_len, b, b_len, ops=False):
         """Edit distances of n pairs on the device (casr_edit_distance): a [n, La], b [n, Lb] int32
         symbols (1 <= La, Lb <= casr.lib.EDIT_MAX_LEN), a_len and b_len [n] -> dist [n] int32, and with

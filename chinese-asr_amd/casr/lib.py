@@ -31,6 +31,9 @@ EXPORTS = [
     "casr_edit_distance_host", "casr_edit_distance", "casr_mbr_host", "casr_beam_mbr", "casr_beam_mbr_distances",
     "casr_bias_create", "casr_bias_destroy", "casr_bias_score_host", "casr_bias_score", "casr_bias_rows_host",
     "casr_bias_rows", "casr_beam_bias", "casr_beam_record_bias",
+    "casr_grammar_create", "casr_grammar_destroy", "casr_grammar_info", "casr_grammar_mask_words",
+    "casr_grammar_accept_host", "casr_grammar_accept", "casr_grammar_rows_host", "casr_grammar_rows",
+    "casr_beam_grammar",
     "casr_align_path_host", "casr_align_path",
     "casr_posterior_units_host", "casr_nbest_host", "casr_confusion_host", "casr_confusion", "casr_beam_nbest",
     "casr_beam_confusion",
@@ -161,6 +164,15 @@ def load(path=None, variant=None):
         "casr_bias_rows": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "casr_beam_bias": (i32, [vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
         "casr_beam_record_bias": (i32, [vp, vp, vp]),
+        "casr_grammar_create": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]),
+        "casr_grammar_destroy": (None, [vp]),
+        "casr_grammar_info": (i32, [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), vp]),
+        "casr_grammar_mask_words": (i32, [i32]),
+        "casr_grammar_accept_host": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+        "casr_grammar_accept": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "casr_grammar_rows_host": (i32, [vp, vp, vp, i32, vp]),
+        "casr_grammar_rows": (i32, [vp, vp, vp, vp, i32, vp, vp]),
+        "casr_beam_grammar": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
         "casr_align_path_host": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "casr_align_path": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "casr_posterior_units_host": (i32, [vp, vp, vp, i32, i32, i32] + [ctypes.c_double] * 3 + [vp, vp]),

@@ -95,8 +95,16 @@ hipError_t launch_lm_terms(const NgramView& m, const NgramSuccView& sv, const Lm
 // ------------------------------------------------------------------ the fused select
 // LDS of one select: the rows' sorted lists and log-sum-exps, the utterance's list, and per wave its
 // threshold candidates
-template <int K2, int NR, int NWV>
-struct BeamLmSelLds {
+// (GRAM: per row its candidate count; an empty base elsewhere, so the other selects' LDS is unchanged)
+template <int NR, bool GRAM>
+struct BeamGramSelLds {};
+template <int NR>
+struct BeamGramSelLds<NR, true> {
+  int ncand[NR];
+};
+
+template <int K2, int NR, int NWV, bool GRAM = false>
+struct BeamLmSelLds : BeamGramSelLds<NR, GRAM> {
   float rv[NR][K2];
   int ri[NR][K2];
   float lse[NR];
@@ -121,16 +129,33 @@ struct BeamLmSelLds {
 //   bias = (float)(v == eos ? C_r : C_r + gain[v]) / 256,  val = ((am + lm_weight lm) + bias_weight bias) + len_l
 // (without LM the lm_weight lm term is left out); the bookkeeping lanes walk the automaton for the
 // chosen candidates' delta and out_sum (bias_plan.h) and pass on (delta, C_r + out_sum).
-template <int K2, bool UNIT_T, bool LM, bool BIAS>
+// GRAM (casr_beam_grammar, never with BIAS; the third operand is then BeamGramArgs): row r carries a grammar
+// state s_r (-1: a dead row) and its mask row (grammar.hip) is read beside the logits.  Only the pairs
+// whose bit is set are candidates: the others are never ranked, whatever their value, so a row's list
+// and the utterance's may be shorter than 2k or empty, and then tau is -inf and it is the bit, not the
+// threshold, that keeps a pair out.  lse is over the whole row.  The bookkeeping lanes get the chosen
+// candidates' successor states with gram_next (grammar_plan.h); the slots no candidate takes are dead rows.
+template <bool GRAM>
+using BeamSideArgs = std::conditional_t<GRAM, BeamGramArgs, BeamBiasArgs>;
+
+template <int K2, bool UNIT_T, bool LM, bool BIAS, bool GRAM = false>
 __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(BeamSelArgs a, BeamLmArgs g,
-                                                                             BeamBiasArgs hb) {
+                                                                             BeamSideArgs<GRAM> sd) {
+  static_assert(!(GRAM && BIAS), "the grammar select takes no bias");
   constexpr int NWV = bs_waves<K2>(), NTH = 64 * NWV;
-  __shared__ BeamLmSelLds<K2, KMAX_BEAM, NWV> S;
+  __shared__ BeamLmSelLds<K2, KMAX_BEAM, NWV, GRAM> S;
   if (done_before(a.newdone, a.l) >= a.B) return;
+  const auto& hb = sd;  // BIAS
+  const auto& gr = sd;  // GRAM
   const float* __restrict__ logits = a.logits;
   const float* __restrict__ terms = g.terms;
-  const int32_t* __restrict__ gains = hb.gain;
-  const float bw = hb.bias_weight;
+  const int32_t* __restrict__ gains = nullptr;
+  float bw = 0.f;
+  if constexpr (!GRAM) {
+    gains = hb.gain;
+    bw = hb.bias_weight;
+  }
+  [[maybe_unused]] const int GW = gram_mask_words(a.V);
   const int V = a.V, B = a.B, k = a.k, l = a.l, L = a.L, eos = a.eos, b = blockIdx.x;
   const float temperature = a.temperature;
   const GreedyPart& gp = a.gp;
@@ -153,7 +178,28 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
     const int4* gn4 = reinterpret_cast<const int4*>(gn);
     const float sc = a.score_cur[row];
     const float gc = (!LM || l == 0) ? 0.f : g.g_cur[row];
-    const int Cc = (!BIAS || l == 0) ? 0 : hb.full_cur[row];
+    int Cc = 0;
+    if constexpr (BIAS) Cc = l == 0 ? 0 : hb.full_cur[row];
+    const uint32_t* mk = nullptr;  // GRAM: the row's mask
+    if constexpr (GRAM) {
+      mk = gr.mask + row * GW;
+      if (gr.st_cur[row] < 0) {  // a dead row offers nothing
+        if (ln < n2k) {
+          S.rv[j][ln] = -INFINITY;
+          S.ri[j][ln] = 0x7fffffff;
+        }
+        if (ln == 0) {
+          S.lse[j] = 0.f;
+          S.ncand[j] = 0;
+        }
+        continue;
+      }
+      int nb = 0;
+      for (int w = ln; w < GW; w += 64) nb += __popc(mk[w]);
+      for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o);
+      if (ln == 0) S.ncand[j] = nb;
+    }
+    auto allowed = [&](int v) { return GRAM ? ((mk[v >> 5] >> (v & 31)) & 1u) != 0 : true; };
     float lse;
     if (UNIT_T && nbp > 0 && gp.tmx && vec) {  // beam_select_block's first form: from the partials
       float mb = -INFINITY, sb = 0.f;
@@ -215,6 +261,9 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
     constexpr int LMS_QB = 20;
     const bool held = vec && V <= 4 * 64 * LMS_QB;
     float vq[LMS_QB][4];
+    // GRAM: float4 i's four bits are nibble (i & 7) of mask word i >> 3; LMS_QB nibbles, 8 to a word
+    [[maybe_unused]] uint32_t nib[(LMS_QB + 7) / 8] = {};
+    auto nib_at = [&](int u, int e) { return GRAM ? ((nib[u >> 3] >> (4 * (u & 7) + e)) & 1u) != 0 : true; };
     if (held) {
 #pragma unroll
       for (int u = 0; u < LMS_QB; ++u) {
@@ -226,14 +275,17 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
           vq[u][1] = val(xq.y, w4.y, g4.y, 4 * i + 1);
           vq[u][2] = val(xq.z, w4.z, g4.z, 4 * i + 2);
           vq[u][3] = val(xq.w, w4.w, g4.w, 4 * i + 3);
+          if constexpr (GRAM) nib[u >> 3] |= ((mk[i >> 3] >> (4 * (i & 7))) & 15u) << (4 * (u & 7));
         } else {
           vq[u][0] = vq[u][1] = vq[u][2] = vq[u][3] = -INFINITY;
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) top2(vq[u][e]);
+        for (int e = 0; e < 4; ++e)
+          if (nib_at(u, e)) top2(vq[u][e]);
       }
     } else {
-      for (int v = ln; v < V; v += 64) top2(val_at(v));  // (a longer or unaligned row: two passes)
+      for (int v = ln; v < V; v += 64)  // (a longer or unaligned row: two passes)
+        if (allowed(v)) top2(val_at(v));
     }
     float tau = -INFINITY;
     for (int c = 0; c < n2k; ++c) {
@@ -263,11 +315,13 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
         const int i = ln + 64 * u;
         if (i < V / 4) {  // (the padding never qualifies, whatever tau is)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) offer(vq[u][e], j * V + 4 * i + e);
+          for (int e = 0; e < 4; ++e)
+            if (nib_at(u, e)) offer(vq[u][e], j * V + 4 * i + e);
         }
       }
     } else {
-      for (int v = ln; v < V; v += 64) offer(val_at(v), j * V + v);
+      for (int v = ln; v < V; v += 64)
+        if (allowed(v)) offer(val_at(v), j * V + v);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -293,7 +347,8 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
     } else {  // more ties at tau than the buffer holds: every element through sorted lane lists
       TopList<K2> tl;
       tl.init();
-      for (int v = ln; v < V; v += 64) tl.insert(val_at(v), j * V + v);
+      for (int v = ln; v < V; v += 64)
+        if (allowed(v)) tl.insert(val_at(v), j * V + v);
       wave_merge<K2>(tl, n2k, S.rv[j], S.ri[j]);
     }
   }
@@ -326,13 +381,22 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
     int cc = inr ? S.ci[c] : 0;
     const bool bad = inr && (unsigned)cc >= (unsigned)(nrows * V);  // NaN rows leave empty slots
     if (bad) cc = 0;
-    if (__ballot(bad) && ln == 0) atomicOr(a.err, CASR_DEV_BAD_CAND);
+    if constexpr (GRAM) {
+      // an empty slot is a fault only where the utterance had more candidates than were ranked (NaN)
+      int want = 0;
+      for (int j = 0; j < nrows; ++j) want += S.ncand[j];
+      want = want < n2k ? want : n2k;
+      if (__popcll(__ballot(inr && !bad)) < want && ln == 0) atomicOr(a.err, CASR_DEV_BAD_CAND);
+    } else {
+      if (__ballot(bad) && ln == 0) atomicOr(a.err, CASR_DEV_BAD_CAND);
+    }
+    const bool has = GRAM ? inr && !bad : inr;  // this lane holds a ranked candidate
     const int beam = cc / V, tok = cc - beam * V;
-    const bool f = inr && tok == eos;
+    const bool f = has && tok == eos;
     const size_t srow = (size_t)(b * k + beam);
     float am = 0.f, lm = 0.f;
-    int bs = 0, bC = 0;  // BIAS: the candidate's successor state and its full
-    if (inr) {
+    int bs = 0, bC = 0;  // BIAS: the candidate's successor state and its full; GRAM: its successor state
+    if (has) {
       am = (xt(logits[srow * V + tok]) - S.lse[beam]) + a.score_cur[srow];
       if constexpr (LM) {
         const float tv = terms[srow * V + tok];
@@ -345,6 +409,10 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
         if (sbad) atomicOr(a.err, CASR_DEV_BAD_TOKEN);
         if (!f) bias_advance(hb.m, tok, &bs, &bC);  // (eos: the record keeps C_r, bias_closed)
       }
+      if constexpr (GRAM) {
+        const int s = gr.st_cur[srow];  // (a state: the row's mask had the candidate's bit)
+        bs = (!f && (unsigned)s < (unsigned)gr.m.n_states) ? gram_next(gr.m, s, tok) : GRAM_DEAD;
+      }
     }
     if (c < k) {  // finished hypotheses among the first k candidates
       const size_t ri = ((size_t)b * L + l) * k + c;
@@ -356,15 +424,28 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
         a.rec_src[ri] = beam;
       }
     }
-    if (ln == 0 && !a.topfin[b] && tok == eos) {  // candidate 0
+    if (ln == 0 && !a.topfin[b] && (tok == eos || !has)) {  // candidate 0 (GRAM: or an empty list)
       a.topfin[b] = 1;
       atomicAdd(&a.newdone[l], 1);
     }
     // active = first k non-EOS candidates in rank order, then EOS ones
-    const unsigned long long ne = __ballot(inr && !f), eo = __ballot(f);
+    const unsigned long long ne = __ballot(has && !f), eo = __ballot(f);
     const unsigned long long below = (1ull << c) - 1ull;
     const int slot = f ? __popcll(ne) + __popcll(eo & below) : __popcll(ne & below);
-    if (inr && slot < k) {
+    if constexpr (GRAM) {
+      // the non-eos candidates alone; the slots they leave are dead rows, every word of the tree in range
+      const int rw = b * k + c;
+      if (c < k && c >= __popcll(ne)) {
+        a.tok_next[rw] = eos;
+        a.src_next[rw] = b * k;
+        a.score_next[rw] = 0.f;
+        if constexpr (LM) g.g_next[rw] = 0.f;
+        gr.st_next[rw] = GRAM_DEAD;
+        a.bp[(size_t)l * R + rw] = 0;
+        a.tk[(size_t)l * R + rw] = eos;
+      }
+    }
+    if (has && (GRAM ? !f : true) && slot < k) {
       const int rw = b * k + slot;
       a.tok_next[rw] = tok;
       a.src_next[rw] = b * k + beam;
@@ -374,6 +455,7 @@ __global__ __launch_bounds__(64 * bs_waves<K2>()) void beam_lm_select_kernel(Bea
         hb.st_next[rw] = bs;
         hb.full_next[rw] = bC;
       }
+      if constexpr (GRAM) gr.st_next[rw] = bs;
       a.bp[(size_t)l * R + rw] = beam;
       a.tk[(size_t)l * R + rw] = tok;
     }
@@ -409,6 +491,30 @@ hipError_t launch_beam_bias_select(const BeamSelArgs& a, const BeamLmArgs& g, co
                  : launch_beam_lm_select_of<false, true>(a, g, q, K2, s);
 }
 
+template <int K2, bool LM>
+static void launch_beam_gram_select_k(const BeamSelArgs& a, const BeamLmArgs& g, const BeamGramArgs& q, hipStream_t s) {
+  auto kern = a.temperature == 1.0f ? beam_lm_select_kernel<K2, true, LM, false, true>
+                                    : beam_lm_select_kernel<K2, false, LM, false, true>;
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * bs_waves<K2>()), 0, s, a, g, q);
+}
+
+template <bool LM>
+static hipError_t launch_beam_gram_select_of(const BeamSelArgs& a, const BeamLmArgs& g, const BeamGramArgs& q, int K2,
+                                             hipStream_t s) {
+  switch (K2) {
+    case 4: launch_beam_gram_select_k<4, LM>(a, g, q, s); break;
+    case 8: launch_beam_gram_select_k<8, LM>(a, g, q, s); break;
+    case 16: launch_beam_gram_select_k<16, LM>(a, g, q, s); break;
+    default: launch_beam_gram_select_k<32, LM>(a, g, q, s);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_beam_gram_select(const BeamSelArgs& a, const BeamLmArgs& g, const BeamGramArgs& q, int K2,
+                                   hipStream_t s) {
+  return g.terms ? launch_beam_gram_select_of<true>(a, g, q, K2, s) : launch_beam_gram_select_of<false>(a, g, q, K2, s);
+}
+
 // ------------------------------------------------------------------ the final choice
 __device__ __forceinline__ float bias_of(int c) { return __int2float_rn(c) * (1.f / 256.f); }
 
@@ -428,6 +534,8 @@ struct FusedFinArgs {
   float* best_lm;    // or null
   float* best_bias;  // BIAS
   int32_t* steps;
+  const int32_t* gst[2];  // GRAM: the rows' grammar states (-1: a dead row)
+  uint8_t* complete;      // GRAM: 1 where the choice is a record
 };
 
 // (am + lm_weight lm) + len_l, with BIAS ((am [+ lm_weight lm]) + bias_weight bias) + len_l: every
@@ -443,8 +551,10 @@ __device__ __forceinline__ float fused_comb(const FusedFinArgs& a, float am, flo
 
 // One thread per utterance: the first maximum of the combined score over its valid records in (step,
 // rank) order (BIAS: bias_closed), or without a record the first maximum over the k live rows of the last
-// executed step (BIAS: bias_open, C + tail(s)); tokens by walking the back-pointers.
-template <bool LM, bool BIAS>
+// executed step (BIAS: bias_open, C + tail(s)); tokens by walking the back-pointers.  GRAM
+// (casr_beam_grammar): the fallback skips the dead rows, and an utterance with neither a record nor a
+// live row gives length 0 and score 0; complete says whether the choice is a record.
+template <bool LM, bool BIAS, bool GRAM = false>
 __global__ void beam_fused_finalize_kernel(FusedFinArgs a) {
   const BeamTree& t = a.t;
   const int b = blockIdx.x * blockDim.x + threadIdx.x, k = t.k, L = t.L;
@@ -477,8 +587,11 @@ __global__ void beam_fused_finalize_kernel(FusedFinArgs a) {
     const int w = steps & 1;
     len = steps;
     slot = 0;
+    [[maybe_unused]] bool any = false;  // GRAM: a live row was seen
     for (int j = 0; j < k; ++j) {
       const int rw = b * k + j;
+      if constexpr (GRAM)
+        if (a.gst[w][rw] < 0) continue;
       float bias = 0.f;
       if (BIAS) {
         bool sbad = false;
@@ -488,15 +601,19 @@ __global__ void beam_fused_finalize_kernel(FusedFinArgs a) {
       }
       const float lm = LM ? a.g[w][rw] : 0.f;
       const float v = fused_comb<LM, BIAS>(a, t.score[w][rw], lm, bias, steps - 1);
-      if (j == 0 || v > bv) {
+      if ((GRAM ? !any : j == 0) || v > bv) {
         bv = v;
         slot = j;
         bs = t.score[w][rw];
         bq = lm;
         bb = bias;
       }
+      any = true;
     }
+    if constexpr (GRAM)
+      if (!any) len = 0;  // (bs and bq are still 0)
   }
+  if constexpr (GRAM) a.complete[b] = bl >= 0 ? 1 : 0;
   if (beam_walk(TreeGlobal(t, b), k, slot, len - 1, [&](int s, int32_t tok) { out[s] = tok; }))
     atomicOr(t.err, CASR_DEV_BAD_BACKPTR);
   for (int s = len; s < L; ++s) out[s] = -1;
@@ -526,6 +643,23 @@ hipError_t launch_beam_fused_finalize(const BeamTree& t, const BeamLmBufs* lw, c
   f.best_lm = best_lm, f.best_bias = best_bias, f.steps = steps;
   const auto kern = !w ? beam_fused_finalize_kernel<true, false>
                        : lw ? beam_fused_finalize_kernel<true, true> : beam_fused_finalize_kernel<false, true>;
+  hipLaunchKernelGGL(kern, dim3((t.B + 63) / 64), dim3(64), 0, s, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_beam_gram_finalize(const BeamTree& t, const BeamLmBufs* lw, const BeamGramBufs& w, float lm_weight,
+                                     float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
+                                     float* best_lm, uint8_t* complete, int32_t* steps, hipStream_t s) {
+  FusedFinArgs f{t, lm_weight, 0.f, length_weight};
+  if (lw) {
+    f.g[0] = lw->g[0], f.g[1] = lw->g[1];
+    f.rec_lm = lw->rec_lm;
+  }
+  f.best_tokens = best_tokens, f.best_len = best_len, f.best_score = best_score;
+  f.best_lm = best_lm, f.best_bias = nullptr, f.steps = steps;
+  f.gst[0] = w.st[0], f.gst[1] = w.st[1];
+  f.complete = complete;
+  const auto kern = lw ? beam_fused_finalize_kernel<true, false, true> : beam_fused_finalize_kernel<false, false, true>;
   hipLaunchKernelGGL(kern, dim3((t.B + 63) / 64), dim3(64), 0, s, f);
   return hipGetLastError();
 }

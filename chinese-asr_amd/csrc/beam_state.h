@@ -3,7 +3,7 @@
 // (tests/host_plan/beam_state_check.cpp) both compile.  The kernels take BeamTree by value and read it by
 // beam_tree.h's rules.
 //
-// A beam entry (casr_beam, casr_beam_lm, casr_beam_bias) leaves the beam tree and the finished records
+// A beam entry (casr_beam, casr_beam_lm, casr_beam_bias, casr_beam_grammar) leaves the beam tree and the finished records
 // in the handle's decode workspaces.  BeamState says which entry that was; BeamTree is the read-only
 // view of what it left, filled once by that entry; beam_gate is the one rule for who may read it.  The
 // state goes back to BEAM_NONE wherever those workspaces are given to another decode: casr_encode and
@@ -21,6 +21,7 @@ struct BeamState {
   int k = 0;
   float lm_weight = 0.f, length_weight = 0.f;  // the beam's own (the readers' unfinished fallback)
   bool mbr = false;                            // casr_beam_mbr's distances of this beam are present
+  bool grammar = false;  // casr_beam_grammar ran it (kind BEAM_PLAIN or BEAM_LM): the tree has dead rows
   bool has_lm() const { return kind == BEAM_LM || kind == BEAM_BIAS_LM; }      // lmws holds rec_lm
   bool has_bias() const { return kind == BEAM_BIAS || kind == BEAM_BIAS_LM; }  // biasws holds rec_full
 };
@@ -37,7 +38,8 @@ constexpr const char* BEAM_READER_FOLLOWS[BEAM_READERS] = {
     "casr_beam", "casr_beam", "casr_beam", "casr_beam", "casr_beam", "casr_beam_mbr", "casr_beam_lm", "casr_beam_bias"};
 
 // GATE_BEFORE: "<reader> before <the call it must follow>"; GATE_AFTER_FUSED: the reader assumes the
-// scores of a casr_beam and the last beam was casr_beam_lm or casr_beam_bias.  Both are CASR_ERR_STATE.
+// scores of a casr_beam and the last beam was casr_beam_lm, casr_beam_bias or casr_beam_grammar.  Both are
+// CASR_ERR_STATE.
 enum { GATE_OK = 0, GATE_BEFORE, GATE_AFTER_FUSED };
 
 inline int beam_gate(const BeamState& s, int reader) {
@@ -46,7 +48,8 @@ inline int beam_gate(const BeamState& s, int reader) {
     case READ_RESCORE:
     case READ_MBR:
     case READ_NBEST:
-    case READ_CONFUSION: return s.kind == BEAM_PLAIN ? GATE_OK : s.kind == BEAM_NONE ? GATE_BEFORE : GATE_AFTER_FUSED;
+    case READ_CONFUSION:
+      return s.kind == BEAM_NONE ? GATE_BEFORE : s.kind == BEAM_PLAIN && !s.grammar ? GATE_OK : GATE_AFTER_FUSED;
     case READ_MBR_DISTANCES: return s.kind != BEAM_NONE && s.mbr ? GATE_OK : GATE_BEFORE;
     case READ_RECORD_LM: return s.has_lm() ? GATE_OK : GATE_BEFORE;
     case READ_RECORD_BIAS: return s.has_bias() ? GATE_OK : GATE_BEFORE;

@@ -220,6 +220,7 @@ struct casr_handle {
   BeamTree tree;
   DevBuf lmws;    // casr_beam_lm: term rows, LM sums, rec_lm (carve_beam_lm)
   DevBuf biasws;  // casr_beam_bias: gain rows, states, sums, rec_full (carve_beam_bias)
+  DevBuf gramws;  // casr_beam_grammar: mask rows, states (carve_beam_gram)
   DevBuf mbrws;   // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
   DevBuf cnws;    // casr_confusion, casr_beam_nbest, casr_beam_confusion: lists, units, votes (carve_confusion)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
@@ -250,6 +251,13 @@ struct casr_bias {
   BiasTables host;
   void* dev[5] = {};  // node, ctok, cnext, root_next, root_gain
   BiasView dview{};
+};
+
+struct casr_grammar {
+  int device = -1;
+  GrammarTables host;
+  void* dev[6] = {};  // arc_off, arc_tok, arc_next, arc_dist, dist, is_final
+  GrammarView dview{};
 };
 
 static int fail(casr_handle* h, int code, const char* fmt, ...);
@@ -598,7 +606,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->biasws, &h->cnws})
+                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->biasws, &h->cnws, &h->gramws})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1286,6 +1294,8 @@ static int beam_readable(casr_handle* h, int reader, const char* why = "") {
   switch (h ? beam_gate(h->beam, reader) : GATE_BEFORE) {
     case GATE_OK: return CASR_OK;
     case GATE_AFTER_FUSED:
+      if (h->beam.grammar)
+        return fail(h, CASR_ERR_STATE, "%s after casr_beam_grammar: %s", BEAM_READER_NAME[reader], why);
       return fail(h, CASR_ERR_STATE, "%s after casr_beam_lm or casr_beam_bias: %s", BEAM_READER_NAME[reader], why);
     default: return fail(h, CASR_ERR_STATE, "%s before %s", BEAM_READER_NAME[reader], BEAM_READER_FOLLOWS[reader]);
   }
@@ -1966,6 +1976,172 @@ int casr_beam_record_bias(casr_handle* h, float* rec_bias, void* stream) {
   BeamBiasBufs w{};
   carve_beam_bias(h->biasws.p, t.B, t.B * t.k, t.L, t.k, t.V, w);
   HIP_OK(h, run_beam_record_bias(t, w, rec_bias, (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_grammar_create(int device, int vocab, int eos_token, int n_states, const int64_t* arc_off,
+                        const int32_t* arc_tok, const int32_t* arc_next, const uint8_t* is_final, casr_grammar** out) {
+  if (!out) return fail(nullptr, CASR_ERR_ARG, "casr_grammar_create: out is NULL");
+  *out = nullptr;
+  if (device < -1) return fail(nullptr, CASR_ERR_ARG, "casr_grammar_create: device %d", device);
+  casr_grammar* go = new casr_grammar();
+  std::string why;
+  const int rc = gram_build(vocab, eos_token, n_states, arc_off, arc_tok, arc_next, is_final, &go->host, &why);
+  if (rc != GRAM_OK) {
+    delete go;
+    return fail(nullptr, rc, "casr_grammar_create: %s", why.c_str());
+  }
+  go->device = device;
+  if (device >= 0) {
+    const GrammarTables& t = go->host;
+    const void* src[6] = {t.arc_off.data(), t.arc_tok.data(),  t.arc_next.data(),
+                          t.arc_dist.data(), t.dist.data(), t.is_final.data()};
+    const size_t bytes[6] = {t.arc_off.size() * sizeof(int32_t), t.arc_tok.size() * sizeof(int32_t),
+                             t.arc_next.size() * sizeof(int32_t), t.arc_dist.size() * sizeof(int32_t),
+                             t.dist.size() * sizeof(int32_t), t.is_final.size()};
+    const hipError_t e = upload_tables(device, 6, src, bytes, go->dev);  // (no arcs: empty arrays)
+    if (e != hipSuccess) {
+      casr_grammar_destroy(go);
+      return fail(nullptr, CASR_ERR_HIP, "casr_grammar_create: %s", hipGetErrorString(e));
+    }
+    go->dview = GrammarView{t.V, t.eos, t.n_states(), static_cast<const int32_t*>(go->dev[0]),
+                            static_cast<const int32_t*>(go->dev[1]), static_cast<const int32_t*>(go->dev[2]),
+                            static_cast<const int32_t*>(go->dev[3]), static_cast<const int32_t*>(go->dev[4]),
+                            static_cast<const uint8_t*>(go->dev[5])};
+  }
+  *out = go;
+  return CASR_OK;
+}
+
+void casr_grammar_destroy(casr_grammar* g) {
+  if (!g) return;
+  if (g->device >= 0 && hipSetDevice(g->device) == hipSuccess)
+    for (void* p : g->dev)
+      if (p) (void)hipFree(p);
+  delete g;
+}
+
+int casr_grammar_info(const casr_grammar* g, int32_t* n_states, int64_t* n_arcs, int32_t* dist) {
+  if (!g) return fail(nullptr, CASR_ERR_ARG, "casr_grammar_info: the grammar is NULL");
+  if (n_states) *n_states = g->host.n_states();
+  if (n_arcs) *n_arcs = (int64_t)g->host.arc_tok.size();
+  if (dist) std::memcpy(dist, g->host.dist.data(), g->host.dist.size() * sizeof(int32_t));
+  return CASR_OK;
+}
+
+int casr_grammar_mask_words(int vocab) { return vocab < 1 ? 0 : gram_mask_words(vocab); }
+
+int casr_grammar_accept_host(const casr_grammar* g, const int32_t* tokens, const int32_t* lens, int n, int L,
+                             int32_t* consumed, int32_t* state, uint8_t* accepted) {
+  if (!g || n < 0 || L < 0 || (n > 0 && (!lens || (!tokens && L > 0))))
+    return fail(nullptr, CASR_ERR_ARG, "casr_grammar_accept_host: NULL argument, n < 0 or L < 0");
+  for (int i = 0; i < n; ++i)
+    if (lens[i] < 0 || lens[i] > L)
+      return fail(nullptr, CASR_ERR_ARG, "casr_grammar_accept_host: lens[%d] = %d not in [0, %d]", i, lens[i], L);
+  const GrammarView m = g->host.view();
+  for (int i = 0; i < n; ++i) {
+    int32_t c, s;
+    uint8_t ok;
+    gram_sentence(m, tokens + (size_t)i * L, lens[i], &c, &s, &ok);
+    if (consumed) consumed[i] = c;
+    if (state) state[i] = s;
+    if (accepted) accepted[i] = ok;
+  }
+  return CASR_OK;
+}
+
+// the refusals casr_grammar_accept, casr_grammar_rows and casr_beam_grammar share
+static int grammar_on_handle(casr_handle* h, const casr_grammar* g, const char* who) {
+  if (g->device != h->device)
+    return fail(h, CASR_ERR_ARG, "%s: the grammar is %s, the handle on device %d", who,
+                g->device < 0 ? "host-only" : "on another device", h->device);
+  if (g->host.V != h->cfg.vocab)
+    return fail(h, CASR_ERR_ARG, "%s: the grammar's vocab %d is not the handle's %d", who, g->host.V, h->cfg.vocab);
+  if (g->host.eos != h->cfg.eos)
+    return fail(h, CASR_ERR_ARG, "%s: the grammar's eos %d is not the handle's %d", who, g->host.eos, h->cfg.eos);
+  if (!gram_rows_supported(g->host.V))
+    return fail(h, CASR_ERR_UNSUPPORTED, "%s: four mask rows of vocab %d are past the %d KB of LDS they are assembled in",
+                who, g->host.V, (int)(GRAM_ROWS_LDS_BYTES / 1024));
+  return CASR_OK;
+}
+
+int casr_grammar_accept(casr_handle* h, const casr_grammar* g, const int32_t* tokens, const int32_t* lens, int n,
+                        int L, int32_t* consumed, int32_t* state, uint8_t* accepted, void* stream) {
+  if (!h || !g || n < 0 || (n > 0 && (!tokens || !lens)))
+    return fail(h, CASR_ERR_ARG, "casr_grammar_accept: NULL argument or n < 0");
+  int rc = grammar_on_handle(h, g, "casr_grammar_accept");
+  if (rc) return rc;
+  if (L < 1 || L > GRAM_MAX_SENT)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_grammar_accept: L = %d not in [1, %d]", L, GRAM_MAX_SENT);
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_grammar_accept: no guard words");
+  HIP_OK(h, launch_gram_accept(g->dview, tokens, lens, n, L, consumed, state, accepted, GUARD(h, 0),
+                               (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_grammar_rows_host(const casr_grammar* g, const int32_t* state, const int32_t* budget, int n,
+                           uint32_t* mask) {
+  if (!g || n < 0 || (n > 0 && (!state || !budget || !mask)))
+    return fail(nullptr, CASR_ERR_ARG, "casr_grammar_rows_host: NULL argument or n < 0");
+  const GrammarView m = g->host.view();
+  for (int i = 0; i < n; ++i)
+    if (state[i] != GRAM_DEAD && (state[i] < 0 || state[i] >= m.n_states))
+      return fail(nullptr, CASR_ERR_ARG, "casr_grammar_rows_host: state[%d] = %d not -1 or in [0, %d)", i, state[i],
+                  m.n_states);
+  const int GW = gram_mask_words(m.V);
+  bool bad = false;
+  for (int i = 0; i < n; ++i) gram_row_host(m, state[i], budget[i], mask + (size_t)i * GW, &bad);
+  return CASR_OK;
+}
+
+int casr_grammar_rows(casr_handle* h, const casr_grammar* g, const int32_t* state, const int32_t* budget, int n,
+                      uint32_t* mask, void* stream) {
+  if (!h || !g || n < 0 || (n > 0 && (!state || !budget || !mask)))
+    return fail(h, CASR_ERR_ARG, "casr_grammar_rows: NULL argument or n < 0");
+  int rc = grammar_on_handle(h, g, "casr_grammar_rows");
+  if (rc) return rc;
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_grammar_rows: no guard words");
+  const GramRowsSrc src{0, state, budget, nullptr, 0, 1, 0, 0};
+  HIP_OK(h, launch_gram_rows(g->dview, src, n, mask, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+int casr_beam_grammar(casr_handle* h, const casr_grammar* g, const casr_lm* lm, const int32_t* start, int k,
+                      float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                      float* best_score, float* best_lm, uint8_t* complete, int32_t* steps, void* stream) {
+  if (!h || !g || !best_tokens || !best_len || !best_score || !complete || !steps)
+    return fail(h, CASR_ERR_ARG, "casr_beam_grammar: NULL handle, grammar or output");
+  if (!h->W) return fail(h, CASR_ERR_STATE, "casr_beam_grammar before casr_bind_weights");
+  if (!h->encoded) return fail(h, CASR_ERR_STATE, "casr_beam_grammar before casr_encode");
+  int rc = grammar_on_handle(h, g, "casr_beam_grammar");
+  if (rc) return rc;
+  if (lm) {
+    rc = lm_on_handle(h, lm, "casr_beam_grammar");
+    if (rc) return rc;
+  }
+  HIP_OK(h, hipSetDevice(h->device));
+  DecodeCall c;
+  rc = prepare_decode(h, PLAN_BEAM_LM, k, false, c);
+  if (rc) return rc;
+  const DecodeArgs& a = c.a;
+  BeamLmBufs lw{};
+  if (lm) {
+    HIP_OK(h, h->lmws.ensure(carve_beam_lm(nullptr, a.B, a.plan.R, a.max_len, a.k, a.V, lw)));
+    carve_beam_lm(h->lmws.p, a.B, a.plan.R, a.max_len, a.k, a.V, lw);
+  }
+  BeamGramBufs w{};
+  HIP_OK(h, h->gramws.ensure(carve_beam_gram(nullptr, a.plan.R, a.V, w)));
+  carve_beam_gram(h->gramws.p, a.plan.R, a.V, w);
+  beam_ran(h, lm ? BEAM_LM : BEAM_PLAIN, a, lm_weight, length_weight);  // (with an LM casr_beam_record_lm reads lmws)
+  h->beam.grammar = true;
+  // (never a hipGraph: launched eagerly whatever casr_set_graphs says)
+  dg_trace_init();  // CASR_DG_TRACE diagnostics only
+  HIP_OK(h, run_beam_grammar(a, h->d, lm ? &lw : nullptr, w, g->dview, lm ? &lm->dview : nullptr,
+                             lm ? &lm->dsucc : nullptr, start, lm_weight, length_weight, best_tokens, best_len,
+                             best_score, lm ? best_lm : nullptr, complete, steps, (hipStream_t)stream));
+  dg_trace_dump();
   return CASR_OK;
 }
 

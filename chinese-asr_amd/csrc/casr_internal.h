@@ -10,6 +10,7 @@
 #include "bias_plan.h"
 #include "casr.h"
 #include "encode_plan.h"
+#include "grammar_plan.h"
 #include "ngram_succ.h"
 #include "ngram_table.h"
 #include "resample_design.h"
@@ -588,6 +589,57 @@ hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* l
                          const BiasView& bm, const NgramView* m, const NgramSuccView* sv, float bias_weight,
                          float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
                          float* best_score, float* best_lm, float* best_bias, int32_t* steps, hipStream_t s);
+
+// grammar.hip: grammar-constrained decoding (grammar_plan.h's acceptor; casr_grammar_accept,
+// casr_grammar_rows, casr_beam_grammar).  Where a mask row's state and budget come from: tree == 0 the
+// arrays state [n] / budget [n]; tree == 1 the row's state at decode step l (row i = b k + j) under the one
+// budget budget_l, skipping the rows the select of step l does not read, as BiasRowsSrc
+struct GramRowsSrc {
+  int tree;
+  const int32_t* state;
+  const int32_t* budget;  // tree == 0
+  const int32_t* newdone;
+  int l, k, B, budget_l;
+};
+constexpr size_t GRAM_ROWS_LDS_BYTES = 64 * 1024;  // four mask rows (V / 2 bytes) are assembled in LDS
+bool gram_rows_supported(int V);
+// mask [n][gram_mask_words(V)] of n rows; m holds device pointers
+hipError_t launch_gram_rows(const GrammarView& m, const GramRowsSrc& src, int n, uint32_t* mask, int32_t* err,
+                            hipStream_t s);
+hipError_t launch_gram_accept(const GrammarView& m, const int32_t* tokens, const int32_t* lens, int n, int L,
+                              int32_t* consumed, int32_t* state, uint8_t* accepted, int32_t* err, hipStream_t s);
+// the rows' states before step 0: start[b] (null: 0) in every row of utterance b
+hipError_t launch_gram_start(const int32_t* start, int B, int k, int32_t* state, hipStream_t s);
+// the constrained beam's own buffers (handle-owned, beside DecodeBufs and BeamLmBufs)
+struct BeamGramBufs {
+  uint32_t* mask;  // [R][GW] the step's mask rows
+  int32_t* st[2];  // [R] the rows' grammar states (ping-pong, as DecodeBufs::score); -1: a dead row
+};
+inline size_t carve_beam_gram(void* base, int R, int V, BeamGramBufs& w) {
+  Carver c(base);
+  w.mask = c.take<uint32_t>((size_t)R * gram_mask_words(V), 16);  // rows read 16 B at a time
+  for (int i = 0; i < 2; ++i) w.st[i] = c.take<int32_t>(R);
+  return c.bytes(256);
+}
+// what the constrained select has beyond a fused select's operands; m holds device pointers
+struct BeamGramArgs {
+  GrammarView m;
+  const uint32_t* mask;
+  const int32_t* st_cur;
+  int32_t* st_next;
+};
+// beam_lm.hip: the fused select with its GRAM switch (g.terms null: no LM), and the final choice of
+// casr_beam_grammar (casr_beam_lm's; its live-row fallback skips the dead rows of st)
+hipError_t launch_beam_gram_select(const BeamSelArgs& a, const BeamLmArgs& g, const BeamGramArgs& q, int K2,
+                                   hipStream_t s);
+hipError_t launch_beam_gram_finalize(const BeamTree& t, const BeamLmBufs* lw, const BeamGramBufs& w, float lm_weight,
+                                     float length_weight, int32_t* best_tokens, int32_t* best_len, float* best_score,
+                                     float* best_lm, uint8_t* complete, int32_t* steps, hipStream_t s);
+// decoder.hip: run_beam_lm's steps with the mask rows (and, with lw, the term rows) before the select
+hipError_t run_beam_grammar(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* lw, const BeamGramBufs& w,
+                            const GrammarView& gm, const NgramView* m, const NgramSuccView* sv, const int32_t* start,
+                            float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                            float* best_score, float* best_lm, uint8_t* complete, int32_t* steps, hipStream_t s);
 
 // edit.hip: edit distance on the device (edit_plan.h's rule, backtrace, total order and plan).
 // n pairs a [n][La] / b [n][Lb] with their lengths; ops null or [n][3]

@@ -1916,4 +1916,38 @@ hipError_t run_beam_bias(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* l
                                     best_tokens, best_len, best_score, best_lm, best_bias, steps, s);
 }
 
+// casr_beam_grammar: run_beam_lm's steps (the same plan); the rows start in start[b] (null: state 0), and
+// after each step the mask rows of the rows' grammar states under the budget max_len - 2 - l (grammar.hip),
+// with an LM (lw, m, sv) its term rows too, and the select with its GRAM switch.
+hipError_t run_beam_grammar(const DecodeArgs& a, DecodeBufs& d, const BeamLmBufs* lw, const BeamGramBufs& w,
+                            const GrammarView& gm, const NgramView* m, const NgramSuccView* sv, const int32_t* start,
+                            float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                            float* best_score, float* best_lm, uint8_t* complete, int32_t* steps, hipStream_t s) {
+  const int R = a.B * a.k;
+  if (a.plan.caller != PLAN_BEAM_LM || a.plan.fuse_select) return hipErrorInvalidValue;
+  if ((lw != nullptr) != (m != nullptr) || (lw != nullptr) != (sv != nullptr)) return hipErrorInvalidValue;
+  hipError_t e = launch_gram_start(start, a.B, a.k, w.st[0], s);
+  if (e != hipSuccess) return e;
+  e = beam_steps(a, d, false, s, [&](int l) {
+    ProfScope ps(a.prof, CASR_K_SELECT, s);
+    const float len_l = (float)((double)length_weight * (double)(l + 1));
+    BeamLmArgs g{nullptr, nullptr, nullptr, nullptr, lm_weight, len_l};
+    hipError_t es;
+    if (lw) {
+      const LmTermsSrc src{1, nullptr, nullptr, d.bp, d.tk, d.newdone, l, a.k, a.B, R};
+      es = launch_lm_terms(*m, *sv, src, R, a.eos, lw->terms, d.err, s);
+      if (es != hipSuccess) return es;
+      g = BeamLmArgs{lw->terms, lw->g[l & 1], lw->g[(l + 1) & 1], lw->rec_lm, lm_weight, len_l};
+    }
+    const GramRowsSrc gsrc{1, w.st[l & 1], nullptr, d.newdone, l, a.k, a.B, a.max_len - 2 - l};
+    es = launch_gram_rows(gm, gsrc, R, w.mask, d.err, s);
+    if (es != hipSuccess) return es;
+    const BeamGramArgs q{gm, w.mask, w.st[l & 1], w.st[(l + 1) & 1]};
+    return launch_beam_gram_select(beam_sel_args(a, d, l), g, q, a.plan.K2, s);
+  });
+  if (e != hipSuccess) return e;
+  return launch_beam_gram_finalize(beam_tree_of(a, d), lw, w, lm_weight, length_weight, best_tokens, best_len,
+                                   best_score, best_lm, complete, steps, s);
+}
+
 }  // namespace casr

@@ -70,16 +70,17 @@ def features_for(audios):
     return [feat[b, :int(lens[b])] for b in range(len(audios))], lens
 
 
-def parse(path, model, audio_base, lm_model, bw, fusion=False, bias=None, bias_weight=1.0):
-    """main.py:27-65: one file -> predicted text.  ``fusion``, ``bias`` (a casr.bias.PhraseBias) and
-    ``bias_weight``: Model.eval_one_batch_with_beam's; with a bias an LM takes part only when fused."""
+def parse(path, model, audio_base, lm_model, bw, fusion=False, bias=None, bias_weight=1.0, grammar=None):
+    """main.py:27-65: one file -> predicted text.  ``fusion``, ``bias`` (a casr.bias.PhraseBias),
+    ``bias_weight`` and ``grammar`` (a casr.grammar.Grammar: the answer is one of its sentences):
+    Model.eval_one_batch_with_beam's; with a bias or a grammar an LM takes part only when fused."""
     data, lens = features_for(read_audio([path]))
     text = None
     if bw is not None:
         if gpd['verbose']:
             print(f"[INFO] Beam Decode [bw={bw}]...")
         res = model.eval_one_batch_with_beam(model.device, bw, data, lens, text, audio_base.int2word,
-                                             **_beam_args(lm_model, fusion, bias, bias_weight))
+                                             **_beam_args(lm_model, fusion, bias, bias_weight, grammar))
     else:
         res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, text)
     return res.pred_text[0]
@@ -98,12 +99,16 @@ def parse_timed(path, model, audio_base, lm_model=None, bw=None, fusion=False, b
     return [(ch, t[0], t[1], t[3]) for ch, t in zip(res.pred_text[0], res.timing[0])]
 
 
-def _beam_args(lm_model, fusion, bias, bias_weight):
-    """The beam's keyword arguments; with a bias the LM enters only fused, and no second pass runs."""
-    if bias is not None and not fusion:
+def _beam_args(lm_model, fusion, bias, bias_weight, grammar=None):
+    """The beam's keyword arguments; with a bias or a grammar the LM enters only fused, and no second pass
+    runs.  The grammar keyword is passed only when one is given."""
+    if (bias is not None or grammar is not None) and not fusion:
         lm_model = None
-    return dict(second_pass=lm_model is not None, lm_model=lm_model, lm_weight=1.5, length_weight=1.5,
-                fusion=fusion and lm_model is not None, bias=bias, bias_weight=bias_weight)
+    kw = dict(second_pass=lm_model is not None, lm_model=lm_model, lm_weight=1.5, length_weight=1.5,
+              fusion=fusion and lm_model is not None, bias=bias, bias_weight=bias_weight)
+    if grammar is not None:
+        kw["grammar"] = grammar
+    return kw
 
 
 def align(path, text, model, audio_base):
@@ -116,13 +121,14 @@ def align(path, text, model, audio_base):
     return [(ch, float(start[i]), float(res.token_logp[0][i])) for i, ch in enumerate(text)]
 
 
-def parse_batch(paths, model, audio_base, lm_model=None, bw=None, fusion=False, bias=None, bias_weight=1.0):
+def parse_batch(paths, model, audio_base, lm_model=None, bw=None, fusion=False, bias=None, bias_weight=1.0,
+                grammar=None):
     """Batched form of parse (the reference's __init__.py names it but never defines it): all
     files go through the GPU path as one batch."""
     data, lens = features_for(read_audio(paths))
     if bw is not None:
         res = model.eval_one_batch_with_beam(model.device, bw, data, lens, None, audio_base.int2word,
-                                             **_beam_args(lm_model, fusion, bias, bias_weight))
+                                             **_beam_args(lm_model, fusion, bias, bias_weight, grammar))
     else:
         res = model.eval_one_batch_with_greedy(model.device, data, lens, audio_base.int2word, None)
     return list(res.pred_text)
@@ -201,13 +207,15 @@ class ASR:
     """main.py:68-102."""
 
     def __init__(self, lm_path=None, bw=None, ckpt='./pretrain-0.06328.ckpt', lm_backend="kenlm", fusion=False,
-                 hotwords=None, hotword_boost=1.0, bias_weight=1.0):
+                 hotwords=None, hotword_boost=1.0, bias_weight=1.0, grammar=None):
         """lm_backend "kenlm" (default: the reference's import) or "casr": the library's own ARPA
         n-gram LM (casr.ngram.NgramLM), rescored on the device; with ``fusion`` (the "casr" backend
         only) fused into the beam's first pass instead (Model.eval_one_batch_with_beam).
         ``hotwords``: a list of phrases, or a text file with one phrase per line and an optional boost
         in nats per token after it (casr.bias.read_hotwords; ``hotword_boost`` serves the others): the
-        beam search favours them (needs ``bw``)."""
+        beam search favours them (needs ``bw``).
+        ``grammar``: a casr.grammar.Grammar, a list of phrases, or a text file with one phrase per line:
+        every answer of __call__ is then one of its sentences (needs ``bw``; not together with hotwords)."""
         self.fusion = bool(fusion)
         if lm_backend not in ("kenlm", "casr"):
             raise ValueError(f"lm_backend must be 'kenlm' or 'casr', got {lm_backend!r}")
@@ -239,10 +247,18 @@ class ASR:
             if bw is None:
                 raise ValueError("hotwords need a beam search: pass bw")
             self.bias = PhraseBias.coerce(hotwords, self.audio_base.word2int, model.cfg.vocab, hotword_boost)
+        self.grammar = None
+        if grammar is not None:
+            from casr.grammar import Grammar
+            if bw is None:
+                raise ValueError("a grammar needs a beam search: pass bw")
+            if hotwords is not None:
+                raise ValueError("grammar and hotwords exclude each other")
+            self.grammar = Grammar.coerce(grammar, self.audio_base.word2int, model.cfg.vocab, model.cfg.eos)
 
     def __call__(self, path):
         return parse(path, self.model, self.audio_base, self.lm_model, self.bw, fusion=self.fusion, bias=self.bias,
-                     bias_weight=self.bias_weight)
+                     bias_weight=self.bias_weight, grammar=self.grammar)
 
     def transcribe(self, path, params=None):
         """A recording of any length -> its text: the segments' texts of transcribe(), joined."""

@@ -177,7 +177,7 @@ class Model(object):
                                  second_pass=gpd['second_pass'], lm_model=None,
                                  lm_weight=gpd['lm_weight'], length_weight=gpd['length_weight'], fusion=False,
                                  mbr=None, bias=None, bias_weight=1.0, timestamps=False, nbest=None, alternatives=None,
-                                 posterior_scale=1.0):
+                                 posterior_scale=1.0, grammar=None, grammar_start=None):
         """model.py:604-987.  ``fusion`` (this path's own addition, default off): with an NgramLM as
         ``lm_model`` the LM is fused into the first pass on the device (casr_beam_lm: every candidate
         ranked by logp + lm_weight lm + length_weight (l + 1), the ranking model.py:843-857 was designed
@@ -212,8 +212,30 @@ class Model(object):
         MBR choice).  An lm_model that is no NgramLM cannot be read on the device: TypeError; together with
         ``fusion`` or ``bias``: ValueError (both read the records of a plain beam through its scores).  As
         with ``mbr``, no host second pass runs under either keyword: ``second_pass`` with ``lm_model`` None
-        keeps the first pass's choice and does not raise the reference's AttributeError."""
+        keeps the first pass's choice and does not raise the reference's AttributeError.
+        ``grammar`` (this path's own addition, default None: off): a casr.grammar.Grammar; every answer is
+        then a sentence of it (casr_beam_grammar: only the grammar's continuations are ranked, and every
+        hypothesis can still finish before max_len), ``score`` the choice's acoustic log-probability.
+        ``grammar_start``: one grammar state per utterance to start in (Grammar.union's), default state 0.
+        With ``fusion`` and an NgramLM the LM is fused as well; otherwise no LM takes part.  ``timestamps``
+        works as elsewhere.  Together with ``bias``, ``mbr``, ``nbest``, ``alternatives`` or a second pass
+        over an ``lm_model`` that is not fused: ValueError (those read a plain beam's tree and scores)."""
         self.model.eval()
+        if grammar is not None:
+            for name, on in (("bias", bias is not None), ("mbr", mbr is not None), ("nbest", nbest is not None),
+                             ("alternatives", alternatives is not None)):
+                if on:
+                    raise ValueError(f"grammar and {name} exclude each other: {name} reads or ranks a plain beam")
+            if second_pass and lm_model is not None and not fusion:
+                raise ValueError("grammar with a second pass: fuse the LM (fusion=True with a casr.ngram.NgramLM) "
+                                 "or drop it; the second pass rescores a plain beam")
+            if fusion and not isinstance(lm_model, NgramLM):
+                raise TypeError(f"fusion=True needs a casr.ngram.NgramLM as lm_model, got {type(lm_model).__name__}")
+            lm = lm_model if fusion else None
+            bsz, _, r = self._run(data, lens, lambda: self._with_timing(
+                self.engine.beam_grammar(grammar, bmsz, lm, lm_weight if fusion else 0.0, length_weight,
+                                         start=grammar_start), timestamps))
+            return self._first_pass_output(bsz, r, text, int2word)
         extras = nbest is not None or alternatives is not None
         if extras:
             if bias is not None or fusion:
@@ -312,7 +334,7 @@ class Model(object):
         return BeamEvalOutput(*out, nbest=lists, alternatives=slots)
 
     def _first_pass_output(self, bsz, r, text, int2word):
-        """The EvalOutput of a beam whose first pass made the choice (beam_lm, beam_bias)."""
+        """The EvalOutput of a beam whose first pass made the choice (beam_lm, beam_bias, beam_grammar)."""
         toks, blen, bscore = (r[n].cpu().numpy() for n in ('tokens', 'length', 'score'))
         self.beam_unfinished = r.get('unfinished')
         i2w = self._int2word(int2word)

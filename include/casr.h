@@ -599,6 +599,107 @@ int casr_beam_bias(casr_handle* h, const casr_bias* bias, const casr_lm* lm_or_n
                    float* best_score, float* best_lm_or_null, float* best_bias, int32_t* steps, void* stream);
 int casr_beam_record_bias(casr_handle* h, float* rec_bias, void* stream);
 
+/* Grammar-constrained decoding: every answer is a sentence of a grammar the caller gives (a voice menu, a
+ * digit string, a closed list of names).  An n-gram LM and hotwords only move scores; a grammar decides
+ * which hypotheses exist.  The reference has no such pass; the operation is DEFINED BY THE RULES BELOW
+ * (csrc/grammar_plan.h is their one text for the kernels and the host; tests/grammar_ref.py restates them).
+ *   Grammar   a deterministic finite acceptor over token ids: states 0 .. S - 1, per state s the arcs
+ *             (token, next) in arc_tok / arc_next [arc_off[s], arc_off[s + 1]), strictly ascending in
+ *             token, and is_final [S] (0 / 1).  Sentences start in state 0 (casr_beam_grammar: in start[b]).
+ *             eos_token is never an arc label: a hypothesis may end exactly in a final state.
+ *   dist[s]   the fewest tokens from s to a final state, by backward breadth-first search.
+ * casr_grammar_create checks the arrays (all HOST) and computes dist.  device >= 0 also uploads the grammar
+ * to that device (synchronously); device = -1 makes a host-only object.  The object is immutable: any
+ * number of handles on its device may share it, from any thread.  It must outlive the work enqueued with it.
+ * CASR_ERR_ARG (casr_last_error(NULL) names the state or arc): a NULL array, vocab or n_states < 1, eos
+ * outside [0, vocab), arc_off not ascending from 0, a token outside [0, vocab) or equal to eos_token, tokens
+ * not strictly ascending within a state, a next outside [0, S), no final state, a state from which no final
+ * state can be reached (the caller trims those out; casr/grammar.py does).  CASR_ERR_UNSUPPORTED: more
+ * than 2^20 states or 2^24 arcs.
+ * casr_grammar_info: n_states, n_arcs and dist [S] (HOST; each may be NULL). */
+typedef struct casr_grammar casr_grammar;
+int casr_grammar_create(int device, int vocab, int eos_token, int n_states, const int64_t* arc_off,
+                        const int32_t* arc_tok, const int32_t* arc_next, const uint8_t* is_final, casr_grammar** out);
+void casr_grammar_destroy(casr_grammar* g);
+int casr_grammar_info(const casr_grammar* g, int32_t* n_states, int64_t* n_arcs, int32_t* dist_host_or_null);
+
+/* Words of a mask row: GW = 4 ceil(vocab / 128) uint32 (160 at vocab 5,004), so rows are 16-byte aligned.
+ * Bit v & 31 of word v >> 5 is token v; bits at and past vocab are 0.  0 for vocab < 1. */
+int casr_grammar_mask_words(int vocab);
+
+/* The walk of the sentences tokens [n][L] with lens [n] from state 0; each output may be NULL:
+ *   consumed [n]  the tokens walked before the first one without an arc, or the length
+ *   state    [n]  the state after those tokens
+ *   accepted [n]  consumed == len and is_final[state]
+ * An id outside [0, V) has no arc.
+ * casr_grammar_accept_host: HOST pointers, any object, no GPU, any L >= 0; CASR_ERR_ARG for a NULL argument
+ * or a length outside [0, L].
+ * casr_grammar_accept: DEVICE pointers, one thread per sentence; a length outside [0, L] is clamped and
+ * raises guard bit 1; 1 <= L <= 512, else CASR_ERR_UNSUPPORTED.  Needs no weights and no encode.
+ * CASR_ERR_ARG: a NULL argument, n < 0, a grammar that is host-only or on another device, or whose vocab or
+ * eos is not the handle's. */
+int casr_grammar_accept_host(const casr_grammar* g, const int32_t* tokens, const int32_t* lens, int n, int L,
+                             int32_t* consumed, int32_t* state, uint8_t* accepted);
+int casr_grammar_accept(casr_handle* h, const casr_grammar* g, const int32_t* tokens, const int32_t* lens, int n,
+                        int L, int32_t* consumed, int32_t* state, uint8_t* accepted, void* stream);
+
+/* The mask rows of grammar states: for state [n] and budget [n], mask [n][GW] uint32.  Bit v != eos of row
+ * i is set iff there is an arc (state[i], v, d) with dist[d] <= budget[i]: the token is allowed and a
+ * final state stays within budget[i] further tokens.  Bit eos is set iff is_final[state[i]], whatever the
+ * budget.  State -1 (a dead beam row) gives an all-zero row.
+ * casr_grammar_rows_host: HOST pointers; any other state outside [0, S) is CASR_ERR_ARG.
+ * casr_grammar_rows: DEVICE pointers, one wave per row, four rows per workgroup: the wave zeroes its GW
+ * words in LDS, its lanes stride the state's arcs and OR their bits in, and the row is written once,
+ * coalesced.  A state other than -1 outside [0, S) gives an all-zero row and raises guard bit 1.
+ * Errors as casr_grammar_accept; CASR_ERR_UNSUPPORTED: four rows past 64 KB of LDS (V > 131,072). */
+int casr_grammar_rows_host(const casr_grammar* g, const int32_t* state, const int32_t* budget, int n,
+                           uint32_t* mask);
+int casr_grammar_rows(casr_handle* h, const casr_grammar* g, const int32_t* state, const int32_t* budget, int n,
+                      uint32_t* mask, void* stream);
+
+/* Beam search over the sentences of a grammar, optionally with the n-gram LM in the first pass.  am, lm,
+ * val = (am + lm_weight lm) + len_l (without an LM the lm_weight lm term is left out), the tie rule,
+ * ranking beam 0 only at step 0, and len_l are casr_beam_lm's, bit for bit; lse is over the whole logits
+ * row (no renormalisation over the allowed set: am stays the acoustic log-probability).
+ * Row r carries a grammar state s_r: start[b] at step 0 (start: DEVICE [B], NULL: all 0), -1 for a dead
+ * row.  At step l, with L = max_len, the CANDIDATES of an utterance are
+ *     (r, v != eos)  with an arc (s_r, v, d) and dist[d] <= L - 2 - l     (the horizon rule)
+ *     (r, eos)       with s_r final
+ * and dead rows offer nothing.  A pair that is not a candidate is never ranked, whatever its value.  The
+ * utterance's list is the top 2k of its candidates by val and may be shorter, or empty.  Records: the eos
+ * candidates among the first k ranks.  Active rows: the non-eos candidates in rank order, at most k, each
+ * carrying its arc's next state; the slots they leave are dead rows (token eos, back-pointer 0, score 0,
+ * state -1), so every word of the tree stays in range for its readers.  An utterance counts as finished
+ * for the early stop when rank 0 is eos or its list is empty.
+ * The horizon rule keeps every live row able to finish by the last step: at step L - 1 only eos is
+ * offered, so an utterance whose start state has dist <= L - 1 always ends with a record, and its output
+ * is always a sentence of the grammar.
+ * The best hypothesis is casr_beam_lm's final choice (the first maximum over the valid records in (step,
+ * rank) order of (rec_score + lm_weight rec_lm) + len_l); without a record, the same over the LIVE rows of
+ * the last executed step; complete [B] is 1 iff the choice is a record.  An utterance with no candidate at
+ * all (its start state has dist > L - 1, or lies outside [0, S), which also raises guard bit 1) gives
+ * best_len 0, best_score 0 and complete 0.  best_score is the choice's am, best_lm (NULL without an LM,
+ * else optional) its lm.  With a grammar that allows every token everywhere, every record of a step
+ * < L - 1 and, where the search ends before step L - 1, every output equals casr_beam_lm's bit for bit
+ * (without an LM and with length_weight 0: casr_beam's).
+ * Per step the mask rows of the rows' states under the budget L - 2 - l go through a handle-owned
+ * workspace of R GW words (casr_grammar_rows' kernel): one bit per token, read by the select beside the
+ * logits and the optional term rows; the bookkeeping lanes look up the chosen candidates' next states (at
+ * most 32 binary searches per utterance).  An empty slot raises guard bit 8 only where the utterance had
+ * more candidates than were ranked (a NaN row).  It counts under CASR_K_SELECT.  Never replayed as a
+ * hipGraph; no float atomics; results do not depend on scheduling.  Returns after enqueueing.
+ * Errors as casr_beam_bias: CASR_ERR_STATE before an encode or before weights are bound; CASR_ERR_ARG: a
+ * NULL handle, grammar or required output, a grammar or LM that is host-only, on another device or of
+ * another vocab, a grammar whose eos is not the handle's, k outside 1..16.  After it casr_beam_rescore,
+ * casr_beam_mbr, casr_beam_nbest and casr_beam_confusion return CASR_ERR_STATE until the next casr_beam
+ * (they assume a tree without dead rows); casr_beam_records works; casr_beam_record_lm works only if an
+ * LM was given. */
+int casr_beam_grammar(casr_handle* h, const casr_grammar* g, const casr_lm* lm_or_null,
+                      const int32_t* start_or_null /* DEVICE [B], NULL: all 0 */, int k,
+                      float lm_weight, float length_weight, int32_t* best_tokens, int32_t* best_len,
+                      float* best_score, float* best_lm_or_null, uint8_t* complete, int32_t* steps,
+                      void* stream);
+
 /* Edit distance, its operation counts, and a minimum-Bayes-risk (MBR) choice among the finished
  * hypotheses of a beam.  The reference computes a WER per utterance with python-Levenshtein
  * (util.py:237-262) and has no MBR; like the n-gram LM, the operation is DEFINED BY THE FORMULAS BELOW.
