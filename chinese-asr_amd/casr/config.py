@@ -48,7 +48,11 @@ class CasrConfig:
 
 def config_from_gpd(gpd):
     """Build the frozen config from a reference-style ``gpd`` dict, rejecting the settings
-    this MI355X path does not implement (it covers the deployed LSTM/Bahdanau config)."""
+    this MI355X path does not implement (it covers the deployed LSTM/Bahdanau config).  Open beyond the
+    deployed values, and tested there: encoder_num_layers 1..8, residual, max_num_words (vocab =
+    max_num_words + 4 >= 4), max_len >= 1, sos / eos anywhere in the vocabulary, temperature > 0.  Two
+    calls depend on the vocabulary: scoring needs vocab <= 5120 and a beam width k needs 2k <= vocab
+    (the library refuses both: include/casr.h)."""
     unsupported = []
     if gpd.get('encoder_type', 'LSTM') != 'LSTM':
         unsupported.append('encoder_type')

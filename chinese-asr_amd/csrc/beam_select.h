@@ -203,7 +203,9 @@ __device__ __forceinline__ void beam_select_block(const BeamSelArgs& a, int b, B
       bool qual[TPL];
 #pragma unroll
       for (int c = 0; c < TPL; ++c) {
-        qual[c] = (tm[c] - lse) + sc >= tau;
+        // (fewer than 2k tiles: the rounds above ran out of maxima and tau is -inf, which the -inf
+        // of a tile past the row would meet; such a tile is never read)
+        qual[c] = tt[c] < ntile && (tm[c] - lse) + sc >= tau;
         if (c >= PRE) {
 #pragma unroll
           for (int h = 0; h < 4; ++h)

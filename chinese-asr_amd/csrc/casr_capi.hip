@@ -1198,6 +1198,8 @@ static int prepare_decode(casr_handle* h, int caller, int k, bool want_align, De
                                       score_len);
   switch (plan.status) {
     case PLAN_BAD_K: return fail(h, CASR_ERR_ARG, "beam width %d not in [1, %d]", k, KMAX_BEAM);
+    case PLAN_K_VOCAB:
+      return fail(h, CASR_ERR_ARG, "beam width %d keeps 2k = %d candidates, more than the vocabulary's %d tokens", k, 2 * k, V);
     case PLAN_LDS:
       return fail(h, CASR_ERR_UNSUPPORTED, "attention needs %d B of LDS (k=%d, Tp=%d) > 160 KiB", plan.lds_bytes, k, Tp);
     case PLAN_VOCAB:

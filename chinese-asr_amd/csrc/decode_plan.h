@@ -141,6 +141,7 @@ enum {
   PLAN_BAD_K,     // beam width outside [1, KMAX_BEAM]: an argument error
   PLAN_LDS,       // unsupported: the three-launch attention's LDS (lds_bytes) is over the limit
   PLAN_VOCAB,     // unsupported (score): more projection column blocks than row partials
+  PLAN_K_VOCAB,   // beam: 2k candidates per utterance from a vocabulary of fewer than 2k tokens: an argument error
 };
 
 // facts of the bound blob and the handle's arithmetic
@@ -224,6 +225,12 @@ inline DecodePlan plan_decode(int caller, int B, int Tp, int k, bool want_align,
   p.score_len = caller == PLAN_SCORE ? score_len : 0;
   if (k < 1 || k > KMAX_BEAM) {
     p.status = PLAN_BAD_K;
+    return p;
+  }
+  // every beam step keeps 2k candidates per utterance (the reference's topk over the vocabulary, which
+  // raises there): with fewer tokens the step-0 list would carry its sentinels into the bookkeeping
+  if (beam && 2 * k > V) {
+    p.status = PLAN_K_VOCAB;
     return p;
   }
   const int R = p.R = B * k;

@@ -41,7 +41,13 @@ enum {
 typedef struct casr_handle casr_handle;
 
 /* Frozen `gpd` values (gpd.py:13-125), bound at import time in the reference
- * (encoder.py:17-24, decoder.py:11-16, attention.py:21). */
+ * (encoder.py:17-24, decoder.py:11-16, attention.py:21).
+ * Six dimensions are fixed by the build (n_mels, feat_dim, enc_hidden, dec_hidden, embed_dim, attn_size:
+ * any other value is CASR_ERR_UNSUPPORTED).  The rest is open: enc_layers 1..CASR_MAX_LAYERS, residual 0 / 1,
+ * vocab >= 4 (not a multiple of 4 too), max_len >= 1, sos and eos any ids of the vocabulary,
+ * temperature > 0; outside these CASR_ERR_ARG.  The suite holds each of them to the float64 accuracy
+ * budget at the values where the plans or the kernels branch (tests/test_gpu_configs.py).  Two calls depend on the vocabulary: casr_score needs vocab <= 5120
+ * (CASR_ERR_UNSUPPORTED beyond), and a beam width k needs 2k <= vocab (casr_beam). */
 typedef struct casr_config {
   int32_t n_mels;      /* 80   gpd['n_mels'] */
   int32_t feat_dim;    /* 720  encoder.py:19 (n_mels * 3 * 3) */
@@ -55,7 +61,8 @@ typedef struct casr_config {
   int32_t max_len;     /* 40   gpd['max_len'] */
   int32_t sos;         /* 1 */
   int32_t eos;         /* 2 */
-  float temperature;   /* gpd['temperature'], model.py:834 (beam only) */
+  float temperature;   /* gpd['temperature'], model.py:834 (beam only: casr_greedy and casr_score give the
+                          same bits at every temperature) */
 } casr_config;
 
 /* HOST pointers to the reference state-dict tensors, in their reference layouts
@@ -321,7 +328,10 @@ int casr_greedy(casr_handle* h, int32_t* tokens, int32_t* out_len, uint8_t* fini
 /* Model.eval_one_batch_with_beam search loop (model.py:660-931) + first-max finalize
  * (model.py:765 / :961-972) for bmsz = k (1..16) on the last encode.
  *   best_tokens [B][max_len], best_len [B], best_score [B], steps [1] loop steps executed.
- * With length_weight the unfinished fallback adds length_weight*(l+1) (model.py:964). */
+ * With length_weight the unfinished fallback adds length_weight*(l+1) (model.py:964).
+ * Every step keeps 2k candidates per utterance (torch.topk over the vocabulary, model.py:863, which
+ * raises for more than it holds): 2k > vocab is CASR_ERR_ARG, here and in casr_beam_lm, casr_beam_bias
+ * and casr_beam_grammar, before anything is launched or any earlier result is spent. */
 int casr_beam(casr_handle* h, int k, float lm_weight, float length_weight, int32_t* best_tokens,
               int32_t* best_len, float* best_score, int32_t* steps, void* stream);
 

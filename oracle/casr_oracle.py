@@ -249,14 +249,15 @@ def _log_softmax(logit):
 
 
 def greedy_decode(feats, lens, enc_sd, dec_sd, sos=1, eos=2, max_len=40, temperature=1.0,
-                  int2word=None, return_alignment=False):
-    """Model.eval_one_batch_with_greedy (model.py:503-602).
+                  int2word=None, return_alignment=False, num_layers=4, residual=True):
+    """Model.eval_one_batch_with_greedy (model.py:503-602); num_layers and residual are the
+    encoder's (encoder_forward).
     Returns dict(tokens=list of lists, score=list[float], text_len=int32[B],
     finished=bool[B], accum=f32[B], steps=int, logit_gap=min top1-top2 gap per step,
     alignment=list of [T, B] (optional), pred_text (if int2word))."""
     lens = np.asarray(lens, np.int64)
     B = len(feats)
-    enc, (h, c) = encoder_forward(feats, lens, enc_sd)
+    enc, (h, c) = encoder_forward(feats, lens, enc_sd, num_layers, residual)
     mask = mask_for_softmax(lens)
     keys = compute_keys(enc, dec_sd)
     tokens = np.full(B, sos, np.int64)
@@ -296,8 +297,9 @@ def greedy_decode(feats, lens, enc_sd, dec_sd, sos=1, eos=2, max_len=40, tempera
 
 def beam_decode(feats, lens, enc_sd, dec_sd, bmsz, sos=1, eos=2, pad=0, max_len=40,
                 temperature=1.0, second_pass=False, lm_model=None, lm_weight=0.0,
-                length_weight=0.0, int2word=None):
-    """Model.eval_one_batch_with_beam (model.py:604-987), rules of SURVEY §3.2:
+                length_weight=0.0, int2word=None, num_layers=4, residual=True):
+    """Model.eval_one_batch_with_beam (model.py:604-987), rules of SURVEY §3.2 (num_layers and
+    residual are the encoder's, encoder_forward):
     l == 0 restricted to beam 0; finished recorded from the first k candidates;
     early stop once every utterance's rank-0 candidate has ever been EOS; active =
     first k non-EOS of the 2k; unfinished fallback adds length_weight*(l+1);
@@ -307,7 +309,7 @@ def beam_decode(feats, lens, enc_sd, dec_sd, bmsz, sos=1, eos=2, pad=0, max_len=
     B = len(feats)
     k = bmsz
     V = dec_sd["proj_linear.weight"].shape[0]
-    enc, (h, c) = encoder_forward(feats, lens, enc_sd)
+    enc, (h, c) = encoder_forward(feats, lens, enc_sd, num_layers, residual)
     mask = mask_for_softmax(lens)
     keys = compute_keys(enc, dec_sd)
     # tile_batch (util.py:41-56): bb = b*k + j

@@ -396,6 +396,121 @@ static void check_gemm_plans() {
           }
 }
 
+// ---------------------------------------------------------------- the accepted vocabularies
+// check_config accepts any vocab >= 4.  Over the small vocabularies, both sides of the partial-block
+// limit of the projection (V = 5120 | 5121) and of the fused GEMM (V = 7168 | 7169), every R of the
+// sweep above and the three callers: each launch's column blocks cover the tiles it must write, and
+// every table a kernel indexes by a column block or a tile (GreedyPart's GP_NB and GP_NT, the k
+// split's DG_KS_GROUPS arrival counters) is only planned within its size.
+static void check_vocab_sweep() {
+  std::vector<int> vs;
+  for (int V = 4; V <= 100; ++V) vs.push_back(V);
+  for (int V = 5000; V <= 5130; ++V) vs.push_back(V);
+  for (int V = 7160; V <= 7175; ++V) vs.push_back(V);
+  for (int V : vs)
+    for (int R : {1, 32, 33, 256, 257, 512, 513, 1024, 2040, 2048, 4096})
+      for (int fold = 0; fold < 2; ++fold)
+        for (int caller : {PLAN_GREEDY, PLAN_BEAM, PLAN_SCORE}) {
+          In in = caller == PLAN_BEAM ? beam((R + 7) / 8, 8) : caller == PLAN_SCORE ? score((R + 39) / 40, 40) : greedy(R);
+          in.V = V;
+          in.opt(CASR_OPT_DEC_FOLD, fold);
+          const DecodePlan q = plan(in);
+          const int vtiles = (V + 15) / 16, ptiles = (V + 63) / 64 * 4, gt0 = (vtiles + 6) / 7 * 7;
+          if (caller == PLAN_BEAM && 16 > V) {  // 2k candidates from fewer than 2k tokens
+            EXPECT(q.status == PLAN_K_VOCAB);
+            continue;
+          }
+          if (caller == PLAN_SCORE && (ptiles + 4) / 5 > GP_NB) {
+            EXPECT(q.status == PLAN_VOCAB);
+            continue;
+          }
+          EXPECT(q.status == PLAN_OK);
+          EXPECT(fold_vtiles(V) == vtiles && fold_gtile0(V) == gt0 && gt0 >= vtiles && gt0 - vtiles < FOLD_NT);
+          // the launches: column blocks x tiles per block over the tiles each must cover
+          EXPECT(q.lstm.NB * DG_SHAPES[q.lstm.shape].NT >= FOLD_GT && q.lstm.ntiles == FOLD_GT);
+          if (!q.fold) {
+            EXPECT(q.proj.ntiles == ptiles && q.proj.NB * DG_SHAPES[q.proj.shape].NT >= ptiles && ptiles >= vtiles);
+            EXPECT(unused(q.fold_gates) && unused(q.fold_last));
+          } else {
+            EXPECT(unused(q.proj) && q.fold_gates.ntiles == gt0 + FOLD_GT && q.fold_last.ntiles == gt0 + FOLD_GT);
+            EXPECT(q.fold_gates.NB * DG_SHAPES[q.fold_gates.shape].NT >= gt0 + FOLD_GT);
+            EXPECT(q.fold_last.NB * DG_SHAPES[q.fold_last.shape].NT >= vtiles);
+            // the fold only while its vocabulary blocks fit the partial blocks, and never for score
+            EXPECT(gt0 / FOLD_NT <= GP_NB && caller != PLAN_SCORE && fold);
+          }
+          if (caller == PLAN_GREEDY) EXPECT(q.fold == (fold && gt0 / FOLD_NT <= GP_NB));
+          // row partials: one per wave column of the planned shape, within GreedyPart's GP_NB
+          const int blocks = q.fold ? (vtiles + 6) / 7 : (ptiles + 4) / 5;
+          EXPECT(q.partials == (blocks <= GP_NB) && q.nbp == (q.partials ? blocks : 0) && q.nbp <= GP_NB);
+          EXPECT(q.tile_max == (caller == PLAN_BEAM && q.partials && V <= 16 * GP_NT));
+          EXPECT(!q.tile_max || vtiles <= GP_NT);
+          EXPECT(q.store_logits == (caller == PLAN_BEAM || !q.partials));
+          if (caller == PLAN_GREEDY) EXPECT(q.fuse_select == q.partials);
+          // the k split only within its arrival counters
+          for (const DgemmPlan* g : {&q.fold_gates, &q.fold_last}) {
+            if (unused(*g)) continue;
+            const bool ks = g->shape == DG_FOLD_32x112_KS;
+            EXPECT(!ks || (g->NB <= DG_KS_GROUPS && q.R <= 32 && caller == PLAN_GREEDY));
+            if (caller == PLAN_GREEDY && q.R <= 32) EXPECT(ks == (g->NB <= DG_KS_GROUPS));
+          }
+          EXPECT(q.ksplit == (q.fold && q.fold_gates.shape == DG_FOLD_32x112_KS));
+          EXPECT(q.ksplit_last == (q.fold && q.fold_last.shape == DG_FOLD_32x112_KS));
+        }
+  // the four boundaries by value.  V = 5120 fills all 64 partial blocks and the whole tile table
+  auto nofold = [](In in) { return in.opt(CASR_OPT_DEC_FOLD, 0); };
+  DecodePlan p = plan(with_vocab(beam(40, 8), 5120));
+  EXPECT(!p.fold && p.partials && p.nbp == GP_NB && p.tile_max && p.proj.ntiles == GP_NT && p.proj.NB == 64);
+  p = plan(with_vocab(nofold(greedy(19)), 5120));
+  EXPECT(!p.fold && p.partials && p.nbp == 64 && p.fuse_select && !p.store_logits);
+  EXPECT(plan(with_vocab(score(5, 40), 5120)).status == PLAN_OK && plan(with_vocab(score(5, 40), 5120)).nbp == 64);
+  p = plan(with_vocab(beam(128, 8), 5120));
+  EXPECT(p.fold && p.partials && p.nbp == 46 && p.tile_max && p.fuse_select);
+  // V = 5121: 324 projection tiles, 65 blocks: the three-launch step without partials and tile maxima
+  p = plan(with_vocab(beam(40, 8), 5121));
+  EXPECT(p.status == PLAN_OK && !p.fold && !p.partials && p.nbp == 0 && !p.tile_max && p.store_logits && p.proj.NB == 65);
+  p = plan(with_vocab(nofold(greedy(19)), 5121));
+  EXPECT(!p.fold && !p.partials && p.nbp == 0 && !p.fuse_select && p.store_logits);
+  EXPECT(plan(with_vocab(score(5, 40), 5121)).status == PLAN_VOCAB);
+  p = plan(with_vocab(greedy(19), 5121));  // (the fused GEMM's seven-tile blocks: 321 tiles, 46 blocks)
+  EXPECT(p.fold && p.partials && p.nbp == 46 && p.fuse_select);
+  p = plan(with_vocab(beam(128, 8), 5121));  // ... the folded beam keeps its partials, not the tile maxima
+  EXPECT(p.fold && p.partials && p.nbp == 46 && !p.tile_max && p.fuse_select);
+  // V = 7168: 448 vocabulary tiles, no pad tile, fold_blocks == 64: the last vocabulary that folds.  The
+  // gate steps' 83 column blocks are past the arrival counters, the last step's 64 fit them
+  p = plan(with_vocab(greedy(19), 7168));
+  EXPECT(fold_vtiles(7168) == 448 && fold_gtile0(7168) == 448);
+  EXPECT(p.fold && p.partials && p.nbp == 64 && p.fuse_select && !p.store_logits);
+  EXPECT(same(p.fold_gates, DG_FOLD_32x112, 83, 1, 88, 576, 16) && !p.ksplit);
+  EXPECT(same(p.fold_last, DG_FOLD_32x112_KS, 64, 1, 256, 576, 16) && p.ksplit_last);
+  EXPECT(plan(with_vocab(beam(128, 8), 7168)).fold && !plan(with_vocab(beam(128, 8), 7168)).tile_max);
+  // V = 7169: 449 tiles, 65 blocks: even greedy keeps the three-launch step, with a full-row select
+  p = plan(with_vocab(greedy(19), 7169));
+  EXPECT(fold_vtiles(7169) == 449 && fold_gtile0(7169) == 455);
+  EXPECT(p.status == PLAN_OK && !p.fold && !p.build_fold32 && !p.partials && !p.fuse_select && p.store_logits);
+  EXPECT(!p.ksplit && !p.ksplit_last && p.proj.ntiles == 452 && p.proj.NB == 91);
+  EXPECT(!plan(with_vocab(beam(128, 8), 7169)).fold && !plan(with_vocab(beam(128, 8), 7169)).partials);
+  EXPECT(plan(with_vocab(score(5, 40), 7169)).status == PLAN_VOCAB);
+}
+
+// A beam step keeps 2k candidates per utterance (model.py:863, torch.topk over the vocabulary, raises
+// there): refused for every beam caller, before anything else is planned
+static void check_width_against_vocab() {
+  for (int caller : {PLAN_BEAM, PLAN_BEAM_LM})
+    for (int V : {4, 5, 31, 32, 33, 83})
+      for (int k = 1; k <= KMAX_BEAM; ++k) {
+        In in = with_vocab(beam(3, k), V);
+        in.caller = caller;
+        const DecodePlan p = plan(in);
+        EXPECT(p.status == (2 * k > V ? PLAN_K_VOCAB : PLAN_OK));
+        if (p.status != PLAN_OK) EXPECT(p.R == 0 && p.K2 == 0 && unused(p.lstm) && unused(p.proj));
+      }
+  EXPECT(plan(with_vocab(beam(3, 4), 4)).status == PLAN_K_VOCAB);   // the pair that must never launch
+  EXPECT(plan(with_vocab(beam(3, 2), 4)).status == PLAN_OK && plan(with_vocab(beam(3, 2), 4)).K2 == 4);
+  EXPECT(plan(with_vocab(beam(3, 17), 4)).status == PLAN_BAD_K);    // (the width's own range comes first)
+  // greedy and score have no width
+  EXPECT(plan(with_vocab(greedy(3), 4)).status == PLAN_OK && plan(with_vocab(score(3, 1), 4)).status == PLAN_OK);
+}
+
 static void check_keys() {
   const DecodePlan p = plan(beam(256, 8));
   const float sc[2] = {0.25f, 0.5f};
@@ -530,6 +645,8 @@ int main() {
   check_score();
   check_shape_table();
   check_gemm_plans();
+  check_vocab_sweep();
+  check_width_against_vocab();
   check_keys();
   check_carving();
   check_options();

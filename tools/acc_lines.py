@@ -9,6 +9,11 @@ The log-mel front end has two lines per case, "log" and "lin" (the log output, a
 frame's largest float64 mel power); its shape is case-form (form q16 or wave), and the arithmetic
 column only names the engine that ran it.  The beam lines are one per case (B, k, weights).
 
+A log of tests/test_gpu_configs.py has the same lines, the shape column naming the configuration and the
+case (V4-fold, l8r1-per-step, L1-B3k8, ...), and goes to profiles/accuracy/accuracy_budget_configs.json:
+
+  python tools/acc_lines.py pytest_configs.log profiles/accuracy/accuracy_budget_configs.json
+
 A log of tests/test_gpu_accuracy_s16x1.py (arithmetic s16x1) has a second line per quantity,
 "[acc] stage shape s16x1 what cost e_dev_max=.. e_dev_rms=.. e_model_max=.. e_model_rms=..": the
 device's and the float64 s16x1 model's distance from the unrounded float64 stage.  Its ratios are to the
