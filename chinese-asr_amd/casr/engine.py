@@ -492,6 +492,36 @@ class Engine:
         self._keep_edit = (a, a_len, b, b_len)  # read by the enqueued kernel
         return (dist, counts) if ops else dist
 
+    def edit_align(self, a, a_len, b, b_len, ops=True, maps=True):
+        """The edit script of n long pairs on the device (casr_edit_align): a [n, La], b [n, Lb] int32
+        symbols (1 <= La, Lb <= casr.lib.EDIT_ALIGN_MAX_LEN), a_len and b_len [n] -> dict of dist [n],
+        and with ``ops`` the counts ops [n, 3], with ``maps`` b_of_a [n, La] and a_of_b [n, Lb] (-1: no
+        partner); the values casr.lib.edit_align_host gives.  Needs no weights and no encode, leaves
+        the last encode and beam as they are; returns after enqueueing."""
+        dev = self.device
+        a = torch.as_tensor(a).to(dev, torch.int32).contiguous()
+        b = torch.as_tensor(b).to(dev, torch.int32).contiguous()
+        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+            raise ValueError("edit_align: a must be [n, La] and b [n, Lb]")
+        n = a.shape[0]
+        a_len = torch.as_tensor(a_len).to(dev, torch.int32).contiguous()
+        b_len = torch.as_tensor(b_len).to(dev, torch.int32).contiguous()
+        if a_len.shape != (n,) or b_len.shape != (n,):
+            raise ValueError(f"edit_align: a_len and b_len must be [n={n}]")
+        dist = torch.empty(n, dtype=torch.int32, device=dev)
+        counts = torch.empty(n, 3, dtype=torch.int32, device=dev) if ops else None
+        b_of_a = torch.empty(a.shape, dtype=torch.int32, device=dev) if maps else None
+        a_of_b = torch.empty(b.shape, dtype=torch.int32, device=dev) if maps else None
+        _lib.check(self.lib.casr_edit_align(self.handle, _ptr(a), _ptr(a_len), int(a.shape[1]), _ptr(b), _ptr(b_len),
+                                            int(b.shape[1]), n, _ptr(dist), _ptr(counts), _ptr(b_of_a), _ptr(a_of_b),
+                                            _stream()), self.handle)
+        self._keep_edit_align = (a, a_len, b, b_len)  # read by the enqueued kernels
+        return dict(dist=dist, ops=counts, b_of_a=b_of_a, a_of_b=a_of_b)
+
+    def edit_align_workspace_bytes(self):
+        """Bytes of casr_edit_align's workspace this engine's handle holds now."""
+        return int(self.lib.casr_edit_align_workspace_bytes(self.handle))
+
     def beam_mbr(self, scale, lm=None, lm_weight=0.0, length_weight=0.0, records=False):
         """The minimum-Bayes-risk choice over the last beam()'s finished hypotheses on the device
         (casr_beam_mbr): per utterance the record with the lowest expected edit distance to the

@@ -28,6 +28,8 @@ EXPORTS = [
     "casr_lm_terms_host", "casr_lm_terms", "casr_beam_lm", "casr_beam_record_lm",
     "casr_segment_default_params", "casr_segment_bound", "casr_segment_host", "casr_segment",
     "casr_gather_segments",
+    "casr_edit_align_host", "casr_edit_align_tiles_host", "casr_edit_align", "casr_edit_align_plan",
+    "casr_edit_align_workspace_bytes",
     "casr_edit_distance_host", "casr_edit_distance", "casr_mbr_host", "casr_beam_mbr", "casr_beam_mbr_distances",
     "casr_bias_create", "casr_bias_destroy", "casr_bias_score_host", "casr_bias_score", "casr_bias_rows_host",
     "casr_bias_rows", "casr_beam_bias", "casr_beam_record_bias",
@@ -153,6 +155,11 @@ def load(path=None, variant=None):
         "casr_gather_segments": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
         "casr_edit_distance_host": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp]),
         "casr_edit_distance": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
+        "casr_edit_align_host": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "casr_edit_align_tiles_host": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "casr_edit_align": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "casr_edit_align_plan": (i32, [i32, i32, i32, i32, vp, vp]),
+        "casr_edit_align_workspace_bytes": (ctypes.c_int64, [vp]),
         "casr_mbr_host": (i32, [vp, vp, vp, vp, i32, i32, i32] + [ctypes.c_double] * 3 + [vp, vp]),
         "casr_beam_mbr": (i32, [vp, ctypes.c_double, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]),
         "casr_beam_mbr_distances": (i32, [vp, vp, vp, vp]),
@@ -303,6 +310,8 @@ def pack_weights(cfg, enc_sd, dec_sd):
 
 
 EDIT_MAX_LEN = 512  # include/casr.h CASR_EDIT_MAX_LEN: the longest row of the device entry
+EDIT_ALIGN_MAX_LEN = 32768  # include/casr.h CASR_EDIT_ALIGN_MAX_LEN: the longest row of casr_edit_align
+EDIT_ALIGN_TILE = (128, 64)  # csrc/edit_align_plan.h EA_TR, EA_TC: rows and columns of a tile
 BIAS_MAX_LEN = 16   # include/casr.h CASR_BIAS_MAX_LEN: the longest phrase
 ALIGN_MAX_TP = 1024  # include/casr.h CASR_ALIGN_MAX_TP: the longest row of casr_align_path
 CN_EPS, CN_NONE = -1, -2  # include/casr.h CASR_CN_EPS, CASR_CN_NONE: "nothing here", an unused entry
@@ -332,6 +341,40 @@ def edit_distance_host(a, a_len, b, b_len, ops=False):
     check(lib.casr_edit_distance_host(p(a), p(a_len), a.shape[1], p(b), p(b_len), b.shape[1], n, p(dist), p(counts)),
           lib=lib)
     return (dist, counts) if ops else dist
+
+
+def edit_align_host(a, a_len, b, b_len, tiles=False):
+    """casr_edit_align_host: a [n, La], b [n, Lb] int32 symbols with their lengths -> dict of dist [n],
+    ops [n, 3] (insert, delete, replace), b_of_a [n, La] and a_of_b [n, Lb] int32: where the backtrace
+    takes a diagonal step through cell (i, j), b_of_a[i] = j and a_of_b[j] = i; -1 for a deleted or
+    inserted symbol and past a length.  ``tiles``: computed in the device's tile order
+    (casr_edit_align_tiles_host), the same values.  Host only, no GPU."""
+    lib = load()
+    a, b = np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError("edit_align_host: a must be [n, La] and b [n, Lb]")
+    n = a.shape[0]
+    a_len, b_len = _i32(a_len, (n,)), _i32(b_len, (n,))
+    dist = np.zeros(n, np.int32)
+    counts = np.zeros((n, 3), np.int32)
+    b_of_a = np.full(a.shape, -1, np.int32)
+    a_of_b = np.full(b.shape, -1, np.int32)
+    fn = lib.casr_edit_align_tiles_host if tiles else lib.casr_edit_align_host
+    check(fn(_p(a), _p(a_len), a.shape[1], _p(b), _p(b_len), b.shape[1], n, _p(dist), _p(counts), _p(b_of_a),
+             _p(a_of_b)), lib=lib)
+    return dict(dist=dist, ops=counts, b_of_a=b_of_a, a_of_b=a_of_b)
+
+
+def edit_align_plan(La, Lb, n=1, bits=True):
+    """casr_edit_align_plan: what casr_edit_align does with n pairs of [La] x [Lb] -> dict of ok,
+    tiles_r, tiles_c, launches, bits_bytes, bytes (the workspace) and grid (workgroups per launch)."""
+    lib = load()
+    out = np.zeros(6, np.int64)
+    check(lib.casr_edit_align_plan(int(La), int(Lb), int(n), int(bool(bits)), _p(out), None), lib=lib)
+    grid = np.zeros(int(out[3]), np.int64)
+    check(lib.casr_edit_align_plan(int(La), int(Lb), int(n), int(bool(bits)), _p(out), _p(grid)), lib=lib)
+    return dict(ok=bool(out[0]), tiles_r=int(out[1]), tiles_c=int(out[2]), launches=int(out[3]),
+                bits_bytes=int(out[4]), bytes=int(out[5]), grid=grid.tolist())
 
 
 def mbr_host(rec_tokens, rec_score, rec_valid, scale, rec_lm=None, lm_weight=0.0, length_weight=0.0, risk=False):

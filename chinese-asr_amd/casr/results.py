@@ -150,6 +150,26 @@ def wer_batch(preds, refs, normalize=True, return_tuple=False, engine=None):
     return out
 
 
+def wer_long(hyps, refs, engine=None):
+    """(distance, insert, delete, replace) of every (hyp, ref) pair, as integers, for texts of any
+    length up to casr.lib.EDIT_ALIGN_MAX_LEN symbols: ``wer_batch(.., normalize=False,
+    return_tuple=True)`` without its limit of casr.lib.EDIT_MAX_LEN on the device.  With an ``engine``
+    the pairs go to the device in one call (casr_edit_align without its maps), else, or past the
+    device's limits, to the host entry (casr_edit_align_host)."""
+    from . import lib as _lib
+    hyps, refs = list(hyps), list(refs)
+    n = min(len(hyps), len(refs))
+    a, a_len = _symbol_rows(hyps[:n])
+    b, b_len = _symbol_rows(refs[:n])
+    if engine is not None and n and _lib.edit_align_plan(a.shape[1], b.shape[1], n)["ok"]:
+        r = engine.edit_align(a, a_len, b, b_len, ops=True, maps=False)
+        dist, ops = r["dist"].cpu().numpy(), r["ops"].cpu().numpy()
+    else:
+        r = _lib.edit_align_host(a, a_len, b, b_len)
+        dist, ops = r["dist"], r["ops"]
+    return [(int(d),) + tuple(int(x) for x in o) for d, o in zip(dist.tolist(), ops.tolist())]
+
+
 def greedy_outputs(tokens, out_len, finished, accum):
     """model.py:582-593.  Host numpy inputs.  Returns (token lists, scores)."""
     toks = [tokens[b, :out_len[b]].tolist() for b in range(tokens.shape[0])]

@@ -101,6 +101,7 @@ class Segment:
     score: float
     truncated: bool  # the decode used all max_len steps without an EOS: lower max_frames
     chars: list = None  # transcribe(timestamps=True): [(char, start_s, end_s, confidence)] in recording time
+    interpolated: bool = False  # align_long: the span could not be scored; its times are evenly spaced
 
 
 def frame_time(frame):

@@ -2,6 +2,7 @@
 // per-handle device workspaces, and the encode / decode drivers.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include "align_plan.h"
 #include "casr_internal.h"
 #include "confusion_plan.h"
+#include "edit_align_plan.h"
 #include "edit_plan.h"
 
 namespace casr {
@@ -222,6 +224,7 @@ struct casr_handle {
   DevBuf biasws;  // casr_beam_bias: gain rows, states, sums, rec_full (carve_beam_bias)
   DevBuf gramws;  // casr_beam_grammar: mask rows, states (carve_beam_gram)
   DevBuf mbrws;   // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
+  DevBuf eaws;    // casr_edit_align: direction bits and the tile hand-offs (edit_align_plan)
   DevBuf cnws;    // casr_confusion, casr_beam_nbest, casr_beam_confusion: lists, units, votes (carve_confusion)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
@@ -606,7 +609,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->biasws, &h->cnws, &h->gramws})
+                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->eaws, &h->biasws, &h->cnws, &h->gramws})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1542,6 +1545,72 @@ int casr_edit_distance(casr_handle* h, const int32_t* a, const int32_t* a_len, i
   HIP_OK(h, hipSetDevice(h->device));
   if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_edit_distance: no guard words");
   HIP_OK(h, launch_edit_pairs(a, a_len, La, b, b_len, Lb, n, dist, ops, GUARD(h, 0), (hipStream_t)stream));
+  return CASR_OK;
+}
+
+static int edit_align_host_entry(const char* who, bool tiles, const int32_t* a, const int32_t* a_len, int La,
+                                 const int32_t* b, const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops,
+                                 int32_t* b_of_a, int32_t* a_of_b) {
+  if (n < 0 || La < 0 || Lb < 0 || (n > 0 && (!a_len || !b_len || !dist || (!a && La > 0) || (!b && Lb > 0))))
+    return fail(nullptr, CASR_ERR_ARG, "%s: NULL argument, or n, La or Lb < 0", who);
+  for (int i = 0; i < n; ++i)
+    if (a_len[i] < 0 || a_len[i] > La || b_len[i] < 0 || b_len[i] > Lb)
+      return fail(nullptr, CASR_ERR_ARG, "%s: pair %d has lengths %d, %d outside [0, %d], [0, %d]", who, i, a_len[i],
+                  b_len[i], La, Lb);
+  if (b_of_a) std::fill(b_of_a, b_of_a + (size_t)n * La, -1);
+  if (a_of_b) std::fill(a_of_b, a_of_b + (size_t)n * Lb, -1);
+  for (int i = 0; i < n; ++i)
+    dist[i] = (tiles ? ea_pair_tiles : ea_pair_rows)(a + (size_t)i * La, a_len[i], b + (size_t)i * Lb, b_len[i],
+                                                     ops ? ops + (size_t)i * 3 : nullptr,
+                                                     b_of_a ? b_of_a + (size_t)i * La : nullptr,
+                                                     a_of_b ? a_of_b + (size_t)i * Lb : nullptr);
+  return CASR_OK;
+}
+
+int casr_edit_align_host(const int32_t* a, const int32_t* a_len, int La, const int32_t* b, const int32_t* b_len, int Lb,
+                         int n, int32_t* dist, int32_t* ops, int32_t* b_of_a, int32_t* a_of_b) {
+  return edit_align_host_entry("casr_edit_align_host", false, a, a_len, La, b, b_len, Lb, n, dist, ops, b_of_a, a_of_b);
+}
+
+int casr_edit_align_tiles_host(const int32_t* a, const int32_t* a_len, int La, const int32_t* b, const int32_t* b_len,
+                               int Lb, int n, int32_t* dist, int32_t* ops, int32_t* b_of_a, int32_t* a_of_b) {
+  return edit_align_host_entry("casr_edit_align_tiles_host", true, a, a_len, La, b, b_len, Lb, n, dist, ops, b_of_a,
+                               a_of_b);
+}
+
+int casr_edit_align_plan(int La, int Lb, int n, int with_bits, int64_t* out, int64_t* grid) {
+  if (!out) return fail(nullptr, CASR_ERR_ARG, "casr_edit_align_plan: NULL out");
+  const EaPlan pl = edit_align_plan(La, Lb, n, with_bits != 0);
+  out[0] = pl.ok;
+  out[1] = pl.tiles_r;
+  out[2] = pl.tiles_c;
+  out[3] = pl.launches;
+  out[4] = (int64_t)pl.bits_bytes;
+  out[5] = (int64_t)pl.bytes;
+  if (grid)
+    for (int d = 0; d < pl.launches; ++d) grid[d] = (int64_t)ea_diag_tiles(d, pl.tiles_r, pl.tiles_c) * n;
+  return CASR_OK;
+}
+
+int64_t casr_edit_align_workspace_bytes(const casr_handle* h) { return h ? (int64_t)h->eaws.n : -1; }
+
+int casr_edit_align(casr_handle* h, const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
+                    const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops, int32_t* b_of_a, int32_t* a_of_b,
+                    void* stream) {
+  if (!h || n < 0 || (n > 0 && (!a || !a_len || !b || !b_len || !dist)))
+    return fail(h, CASR_ERR_ARG, "casr_edit_align: NULL argument or n < 0");
+  if (La < 1 || Lb < 1 || La > EA_MAX_LEN || Lb > EA_MAX_LEN)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_edit_align: La = %d, Lb = %d not in [1, %d]", La, Lb, EA_MAX_LEN);
+  const EaPlan pl = edit_align_plan(La, Lb, n, ops || b_of_a || a_of_b);
+  if (!pl.ok)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_edit_align: the direction bits of %d pairs of %d x %d pass %zu bytes", n,
+                La, Lb, EA_BITS_LIMIT);
+  if (n == 0) return CASR_OK;
+  HIP_OK(h, hipSetDevice(h->device));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_edit_align: no guard words");
+  HIP_OK(h, h->eaws.ensure(pl.bytes));
+  HIP_OK(h, run_edit_align(a, a_len, La, b, b_len, Lb, n, dist, ops, b_of_a, a_of_b, h->eaws.p, GUARD(h, 0),
+                           (hipStream_t)stream));
   return CASR_OK;
 }
 

@@ -661,6 +661,12 @@ hipError_t run_beam_mbr(const BeamTree& t, const MbrBufs& w, int map, double sca
                         double* best_risk, double* rec_risk, hipStream_t s);
 hipError_t run_mbr_distances(const BeamTree& t, const MbrBufs& w, uint8_t* dist, int32_t* n_rec, hipStream_t s);
 
+// edit_align.hip: the edit script of long pairs (edit_align_plan.h's tiles, bit layout, backtrace and
+// plan).  ws: edit_align_plan(..).bytes of workspace; ops, b_of_a [n][La] and a_of_b [n][Lb] may be null
+hipError_t run_edit_align(const int32_t* a, const int32_t* a_len, int La, const int32_t* b, const int32_t* b_len,
+                          int Lb, int n, int32_t* dist, int32_t* ops, int32_t* b_of_a, int32_t* a_of_b, void* ws,
+                          int32_t* err, hipStream_t s);
+
 // confusion.hip: N-best lists and confusion networks over a beam's records (confusion_plan.h).
 // The handle-owned workspace; positions are those in an utterance's list
 struct CnBufs {

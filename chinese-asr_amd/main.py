@@ -5,7 +5,9 @@
 the reference signatures and results; ``align(path, text, model, audio_base)`` is this path's own
 addition (forced alignment of a given transcript), and so are ``transcribe(paths, model, audio_base)``
 (recordings of any length, cut at their pauses on the device: casr_segment), ``parse_timed`` and
-``ASR.subtitles`` (a start, an end and a confidence per decoded character: casr_align_path).  The chain wav ->
+``ASR.subtitles`` (a start, an end and a confidence per decoded character: casr_align_path), and
+``align_long`` / ``ASR.align`` (a long recording timed against the text known to be spoken in it:
+casr_edit_align, casr.longalign).  The chain wav ->
 log-mel -> delta/stack -> CMVN (eps 1e-6, main.py:37) -> encoder -> greedy / beam (+ second pass with a KenLM-like
 ``lm_model.score(s, bos=True)``) runs on the GPU through the casr C ABI.  Format conversion
 (``convert_audio``: ffmpeg + sox, main.py:19-24) uses the external tools where both are present;
@@ -147,6 +149,15 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
     ``params.max_frames`` then).  A recording with no speech returns [].  With ``timestamps`` every
     decoded segment's ``chars`` holds [(char, start_s, end_s, confidence)], one per character of its
     text, in the recording's time (parse_timed's tuples, offset by the segment's start)."""
+    return _transcribe(paths, model, audio_base, lm_model, bw, params, batch_size, fusion, bias, bias_weight,
+                       timestamps)[0]
+
+
+def _transcribe(paths, model, audio_base, lm_model, bw, params, batch_size, fusion, bias, bias_weight, timestamps):
+    """transcribe's work -> (its result, what a second pass over the same segments needs: None without a
+    segment, else a dict of the log-mel ``fb``, the segments' ``src``, ``starts``, ``lens`` on the device,
+    ``src_h`` and ``lens_h`` on the host, all ``segs`` in (recording, time) order and ``todo``, the
+    indices of those long enough to decode)."""
     import numpy as np
     import torch
     from data import _engine
@@ -167,7 +178,7 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
     counts = n_seg.cpu().tolist()  # the one read the decode's shape depends on
     out = [[] for _ in audios]
     if sum(counts) == 0:
-        return out
+        return out, None
     src = torch.tensor([b for b, c in enumerate(counts) for _ in range(c)], dtype=torch.int64, device=eng.device)
     slot = torch.tensor([i for c in counts for i in range(c)], dtype=torch.int64, device=eng.device)
     starts, lens = start[src, slot], length[src, slot]  # (recording, time) order, no sorting
@@ -200,7 +211,99 @@ def transcribe(paths, model, audio_base, lm_model=None, bw=None, params=None, ba
                 segs[i].chars = [(ch, t0 + t[0], t0 + t[1], t[3]) for ch, t in zip(res.pred_text[j], res.timing[j])]
     for b, s in zip(src_h, segs):
         out[b].append(s)
-    return out
+    return out, dict(fb=fb, src=src, starts=starts, lens=lens, src_h=src_h, lens_h=lens_h, segs=segs, todo=todo)
+
+
+def align_long(paths, texts, model, audio_base, params=None, batch_size=256, bw=None, lm_model=None, fusion=False,
+               bias=None, bias_weight=1.0):
+    """Recordings of any length and the text known to be spoken in each -> per recording a
+    casr.longalign.AlignedRecording: the list of casr.segment.Segment whose ``text`` is the part of the
+    transcript spoken in the segment and whose ``chars`` hold [(char, start_s, end_s, confidence)] for
+    every character of it in recording time, plus the recording's ``dist`` and ``ops`` (the character
+    errors of the decode against the transcript: how far the alignment can be trusted).
+    casr.longalign states the policy.  The steps: transcribe's own segmentation and decode (greedy, or a
+    beam with ``bw`` and transcribe's other arguments); ONE casr_edit_align call for all recordings,
+    decoded ids against transcript ids; a span of the transcript per segment (assign_spans); a second
+    pass over the segments, ``batch_size`` at a time in the same order, gathered and encoded as the
+    first, that scores every span teacher-forced with its closing eos (a span of exactly max_len tokens
+    without it, as transcribe times a decode that ran to max_len) and runs the monotone path through its
+    attention (casr_score, casr_align_path).  ``confidence`` is exp of the character's teacher-forced
+    log-probability, as transcribe(timestamps=True) reports it; None for a character outside the
+    vocabulary and in an ``interpolated`` segment."""
+    import numpy as np
+    import torch
+    from data import _engine
+    from casr import lib as _lib
+    from casr import longalign as LA
+
+    paths, texts = list(paths), list(texts)
+    if len(paths) != len(texts):
+        raise ValueError(f"align_long: {len(paths)} recordings but {len(texts)} texts")
+    w2i, i2w = audio_base.word2int, audio_base.int2word
+    out, st = _transcribe(paths, model, audio_base, lm_model, bw, params, batch_size, fusion, bias, bias_weight, False)
+    ref = [LA.text_ids(t, w2i) for t in texts]
+    hyp = [[i for s in segs for i in LA.hyp_ids(s.text, w2i)] for segs in out]
+    n = len(paths)
+    eng = _engine()
+    a = np.zeros((n, max([1] + [len(h) for h in hyp])), np.int32)
+    b = np.zeros((n, max([1] + [len(r[0]) for r in ref])), np.int32)
+    for k in range(n):
+        a[k, :len(hyp[k])] = hyp[k]
+        b[k, :len(ref[k][0])] = ref[k][0]
+    a_len, b_len = [len(h) for h in hyp], [len(x[0]) for x in ref]
+    if _lib.edit_align_plan(a.shape[1], b.shape[1], n)["ok"]:
+        r = eng.edit_align(a, a_len, b, b_len)
+        dist, ops, a_of_b = (r[key].cpu().numpy() for key in ("dist", "ops", "a_of_b"))
+    else:  # past the device entry's limits (include/casr.h): the host entry, the same values
+        r = _lib.edit_align_host(a, a_len, b, b_len)
+        dist, ops, a_of_b = r["dist"], r["ops"], r["a_of_b"]
+    result, spans = [], []
+    for k in range(n):
+        ids, pos = ref[k]
+        if not out[k] and ids:
+            raise RuntimeError(f"align_long: recording {k} has no speech segment to hold its transcript")
+        sp = LA.assign_spans([len(s.text) for s in out[k]], a_of_b[k, :len(ids)])
+        for s, txt in zip(out[k], LA.span_text(texts[k], pos, sp)):
+            s.text, s.score, s.truncated, s.chars, s.interpolated = txt, 0.0, False, [], False
+        spans += [(k, lo, hi) for lo, hi in sp]
+        result.append(LA.AlignedRecording(out[k], dist[k], ops[k], len(hyp[k]), len(ids)))
+    if st is None:
+        return result
+    segs, L = st['segs'], model.cfg.max_len
+    timed = [None] * len(segs)  # per segment [(start_s, end_s, confidence)] of its span's characters
+    scored = set()
+    for c0 in range(0, len(st['todo']), int(batch_size)):
+        idx = st['todo'][c0:c0 + int(batch_size)]
+        sel = torch.tensor(idx, dtype=torch.int64, device=eng.device)
+        seg_fb, seg_frames = eng.gather_segments(st['fb'], st['src'][sel], st['starts'][sel], st['lens'][sel],
+                                                 t_seg=max(st['lens_h'][i] for i in idx))
+        feat, flen = eng.features(seg_fb, seg_frames, eps=1e-6)
+        flen = flen.cpu()
+        data = [feat[i, :int(flen[i])] for i in range(len(idx))]
+        toks = []
+        for i in idx:
+            k, lo, hi = spans[i]
+            toks.append(ref[k][0][lo:hi] if hi - lo <= L else [])  # (L tokens: scored without the eos)
+        if not any(toks):
+            continue
+        tgt = np.zeros((len(idx), L), np.int32)
+        for j, t in enumerate(toks):
+            tgt[j, :len(t)] = t
+        _, _, td = model._run(data, flen, lambda: model._timed(tgt, [len(t) for t in toks]))
+        for j, (i, sp) in enumerate(zip(idx, model._spans(td, toks, i2w))):
+            if toks[j]:
+                t0 = segs[i].start_s
+                timed[i] = [(t0 + x[0], t0 + x[1], x[3]) for x in sp]
+                scored.add(i)
+    for i, s in enumerate(segs):
+        k, lo, hi = spans[i]
+        if hi > lo and i not in scored:
+            s.interpolated = True
+            timed[i] = LA.interpolate(hi - lo, s.start_s, s.end_s)
+        s.chars = LA.span_chars(texts[k], ref[k][1], lo, hi, timed[i], s.start_s)
+        conf = [c[3] for c in s.chars if c[3] is not None]
+        s.score = float(np.mean(np.log(conf))) if conf and min(conf) > 0 else 0.0
+    return result
 
 
 class ASR:
@@ -266,13 +369,23 @@ class ASR:
                           fusion=self.fusion, bias=self.bias, bias_weight=self.bias_weight)[0]
         return ''.join(s.text for s in segs)
 
-    def subtitles(self, path, fmt="srt", params=None):
+    def align(self, path, text, params=None):
+        """A recording of any length and the text spoken in it -> align_long's result for it: the
+        segments with the transcript's characters timed, and the decode's character errors."""
+        return align_long([path], [text], self.model, self.audio_base, params=params, bw=self.bw,
+                          lm_model=self.lm_model, fusion=self.fusion, bias=self.bias, bias_weight=self.bias_weight)[0]
+
+    def subtitles(self, path, fmt="srt", params=None, text=None):
         """A recording of any length -> its subtitles as SubRip ("srt") or WebVTT ("vtt") text: the
         segments of transcribe(timestamps=True), one cue each, split between characters while a cue
-        is too long (casr.subtitles.cues)."""
+        is too long (casr.subtitles.cues).  With ``text``, the transcript known to be spoken, the cues
+        carry that text, timed by align()."""
         from casr import subtitles
         if fmt not in ("srt", "vtt"):
             raise ValueError(f"fmt must be 'srt' or 'vtt', got {fmt!r}")
+        if text is not None:
+            cue_list = subtitles.cues(self.align(path, text, params=params))
+            return subtitles.to_srt(cue_list) if fmt == "srt" else subtitles.to_vtt(cue_list)
         segs = transcribe([path], self.model, self.audio_base, self.lm_model, self.bw, params=params,
                           fusion=self.fusion, bias=self.bias, bias_weight=self.bias_weight, timestamps=True)[0]
         cue_list = subtitles.cues(segs)

@@ -752,6 +752,44 @@ int casr_edit_distance_host(const int32_t* a, const int32_t* a_len, int La, cons
 int casr_edit_distance(casr_handle* h, const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
                        const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops, void* stream);
 
+/* The edit script of long pairs: distance, counts and WHICH symbol of b each symbol of a became.
+ * Distance, cell rule and backtrace are the ones above; what is new is the length of the rows and the
+ * two maps:
+ *   b_of_a NULL or [n][La]  b_of_a[i] = j where the backtrace takes a diagonal step (match or replace)
+ *                           through cell (i, j), 0-based; -1 for a deleted a[i] and at or past a_len
+ *   a_of_b NULL or [n][Lb]  a_of_b[j] = i at the same steps; -1 for an inserted b[j] and at or past b_len
+ *   dist [n]; ops NULL or [n][3] as above.  All results are integers; the host and the device entry
+ *   agree exactly, and with casr_edit_distance on dist and ops.
+ * casr_edit_align_host: any La, Lb >= 0 and no GPU; errors as casr_edit_distance_host.
+ * casr_edit_align_tiles_host: the same results computed in the order the device takes (tile by tile,
+ * launch by launch, through the same hand-off arrays; csrc/edit_align_plan.h): a check of that order
+ * that needs no GPU.
+ * casr_edit_align: 1 <= La, Lb <= CASR_EDIT_ALIGN_MAX_LEN, else CASR_ERR_UNSUPPORTED; lengths may be 0;
+ * a length outside [0, L] is clamped and raises guard bit 1.  The table is cut into tiles of 64
+ * columns by 128 rows, one wave per tile, one ordinary launch per anti-diagonal of tiles, the pairs
+ * of a call side by side (csrc/edit_align.hip); the direction bits (2 per cell of n La x Lb tables
+ * rounded up to whole tiles: 256 MB for one pair at the limit) go to a workspace the handle owns and
+ * grows on demand.  A call whose bits would pass 1 GiB returns CASR_ERR_UNSUPPORTED before anything is
+ * allocated or launched.  Needs no weights and no encode, spends no beam and disturbs no encode;
+ * returns after enqueueing (growing the workspace waits for the device first); never replayed as a
+ * hipGraph.
+ * casr_edit_align_plan: what the device entry would do with a call, without a GPU: out[0] = 1 if it is
+ * taken, 0 if refused; [1] tile rows, [2] tile columns of a pair; [3] sweep launches; [4] direction-bit
+ * bytes; [5] workspace bytes; grid (NULL or [out[3]]) the workgroups of every sweep launch.
+ * casr_edit_align_workspace_bytes: bytes of that workspace the handle holds now (-1: NULL handle). */
+#define CASR_EDIT_ALIGN_MAX_LEN 32768
+int casr_edit_align_host(const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
+                         const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops,
+                         int32_t* b_of_a, int32_t* a_of_b);
+int casr_edit_align_tiles_host(const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
+                               const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops,
+                               int32_t* b_of_a, int32_t* a_of_b);
+int casr_edit_align(casr_handle* h, const int32_t* a, const int32_t* a_len, int La, const int32_t* b,
+                    const int32_t* b_len, int Lb, int n, int32_t* dist, int32_t* ops, int32_t* b_of_a,
+                    int32_t* a_of_b, void* stream);
+int casr_edit_align_plan(int La, int Lb, int n, int with_bits, int64_t* out /* [6] */, int64_t* grid);
+int64_t casr_edit_align_workspace_bytes(const casr_handle* h);
+
 /* MBR on the host, on the expanded arrays casr_beam_records writes (rec_lm NULL or [B][max_len][k]):
  *   best_index [B]  the flat index step k + rank of the choice, -1 without a record
  *   rec_risk   NULL or [B][max_len][k] double, 0 where there is no valid record
