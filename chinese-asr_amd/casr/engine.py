@@ -297,6 +297,24 @@ class Engine:
         self._keep_lm = (lm, tokens, lens)  # read by the enqueued kernel
         return q
 
+    def lm_estimate(self, tokens, offsets, order):
+        """An interpolated modified-Kneser-Ney n-gram model of the flat corpus on the device
+        (casr_lm_estimate; include/casr.h has the definition): tokens [total] LM ids, offsets [n + 1]
+        ascending from 0 -> casr.ngram.LmEstimate, whose counts and float64 p and gamma are the host
+        entry's bit for bit (the order within an order is unspecified: ``.sorted()``).  A bad id is
+        counted as <unk> and a descending offset clamped, both raising guard bit 1.  Needs no weights
+        and no encode; synchronous."""
+        from .ngram import LmEstimate
+        dev = self.device
+        tokens = torch.as_tensor(tokens).to(dev, torch.int32).contiguous().reshape(-1)
+        offsets = torch.as_tensor(offsets).to(dev, torch.int64).contiguous().reshape(-1)
+        if tokens.numel() == 0:
+            tokens = torch.zeros(1, dtype=torch.int32, device=dev)  # (a pointer to pass; never read)
+        out = ctypes.c_void_p()
+        _lib.check(self.lib.casr_lm_estimate(self.handle, int(order), _ptr(tokens), _ptr(offsets),
+                                             offsets.numel() - 1, _stream(), ctypes.byref(out)), self.handle)
+        return LmEstimate(self.lib, out, order)
+
     def beam_rescore(self, lm, lm_weight, length_weight, records=False):
         """The second pass (model.py:749-763) over the last beam()'s finished hypotheses on the device
         (casr_beam_rescore): lm a casr.ngram.NgramLM.  Returns tokens [B, max_len] (-1 past the

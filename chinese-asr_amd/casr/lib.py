@@ -39,6 +39,9 @@ EXPORTS = [
     "casr_align_path_host", "casr_align_path",
     "casr_posterior_units_host", "casr_nbest_host", "casr_confusion_host", "casr_confusion", "casr_beam_nbest",
     "casr_beam_confusion",
+    "casr_lm_estimate_host", "casr_lm_estimate", "casr_lm_estimate_combine", "casr_lm_estimate_info",
+    "casr_lm_estimate_arrays", "casr_lm_estimate_counts", "casr_lm_estimate_timing", "casr_lm_estimate_destroy",
+    "casr_lm_estimate_workspace_bytes",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -189,6 +192,15 @@ def load(path=None, variant=None):
         "casr_beam_nbest": (i32, [vp, i32, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp]),
         "casr_beam_confusion": (i32, [vp, i32, ctypes.c_double, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp,
                                       vp, vp, vp]),
+        "casr_lm_estimate_host": (i32, [i32, i32, vp, vp, ctypes.c_int64, ctypes.POINTER(vp)]),
+        "casr_lm_estimate": (i32, [vp, i32, vp, vp, ctypes.c_int64, vp, ctypes.POINTER(vp)]),
+        "casr_lm_estimate_combine": (i32, [i32]),
+        "casr_lm_estimate_info": (i32, [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+        "casr_lm_estimate_arrays": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+        "casr_lm_estimate_counts": (i32, [vp, i32, vp]),
+        "casr_lm_estimate_timing": (i32, [vp, vp]),
+        "casr_lm_estimate_destroy": (None, [vp]),
+        "casr_lm_estimate_workspace_bytes": (ctypes.c_int64, [i32, ctypes.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -216,3 +216,136 @@ class NgramLM:
         ids = self.ids_of(sentence)
         row = np.array([ids + [0] * (1 - min(len(ids), 1))], np.int32)
         return float(self.score_ids(row, [len(ids)], bos)[0])
+
+    def write_arpa(self, path, int2word):
+        """The model as an ARPA file: per order the n-grams in ascending key order (ascending id
+        tuples), values with 7 significant digits (``%.7g``), no backoff column at the top order.
+        ``int2word``: the word of every ASR id (a list or a dict); <s>, </s> and <unk> are written
+        as such.  Reading the file back gives the same n-grams in the same order and, for every
+        value x, np.float32(float('%.7g' % x)): within 5e-7 |x| of x (the 7th digit) plus one float32
+        rounding; 0 and -99 come back exactly."""
+        ids, prob, back = self._arrays
+        V = self.vocab
+        special = {V: BOS, V + 1: EOS, V + 2: UNK}
+        with open(path, "w", encoding="utf-8") as f:
+            f.write("\\data\\\n")
+            for n, a in enumerate(ids, 1):
+                f.write(f"ngram {n}={len(a)}\n")
+            for n, (a, p, b) in enumerate(zip(ids, prob, back), 1):
+                f.write(f"\n\\{n}-grams:\n")
+                rows = a.tolist()
+                for i in np.lexsort(a.T[::-1]).tolist():
+                    words = " ".join(special[t] if t >= V else int2word[t] for t in rows[i])
+                    line = "%.7g\t%s" % (float(p[i]), words)
+                    if n < self.order:
+                        line += "\t%.7g" % float(b[i])
+                    f.write(line + "\n")
+            f.write("\n\\end\\\n")
+
+
+# ---------------------------------------------------------------------------- estimation
+class LmEstimate:
+    """What casr_lm_estimate_host / casr_lm_estimate returned (include/casr.h has the definition), as
+    numpy arrays: per order n, ids[n-1] int32 [count, n], prob and backoff float32 (the stored
+    model), raw and adjusted int64 (c_n and a_n), p and gamma float64; ``discounts`` [order, 3],
+    ``fallback`` [order] bool, ``n_types`` (|W|), ``positions`` and ``timing_ms`` (the device entry's
+    stages: count, extend, stats, prob, compact, copy, -, all)."""
+
+    def __init__(self, lib, ptr, order):
+        try:
+            count = np.zeros(4, np.int64)
+            disc = np.zeros((4, 3), np.float64)
+            fb = np.zeros(4, np.int32)
+            nt, pos = ctypes.c_int64(), ctypes.c_int64()
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            _lib.check(lib.casr_lm_estimate_info(ptr, p(count), p(disc), p(fb), ctypes.byref(nt), ctypes.byref(pos)),
+                       lib=lib)
+            self.order = int(order)
+            self.discounts, self.fallback = disc[:self.order].copy(), fb[:self.order].astype(bool)
+            self.n_types, self.positions = nt.value, pos.value
+            self.ids, self.prob, self.backoff, self.raw, self.adjusted, self.p, self.gamma = ([] for _ in range(7))
+            for n in range(1, self.order + 1):
+                c = int(count[n - 1])
+                ids, prob, back = np.zeros((c, n), np.int32), np.zeros(c, np.float32), np.zeros(c, np.float32)
+                raw, adj = np.zeros(c, np.int64), np.zeros(c, np.int64)
+                pf, gf = np.zeros(c, np.float64), np.zeros(c, np.float64)
+                _lib.check(lib.casr_lm_estimate_arrays(ptr, n, p(ids), p(prob), p(back), p(adj), p(pf), p(gf)), lib=lib)
+                _lib.check(lib.casr_lm_estimate_counts(ptr, n, p(raw)), lib=lib)
+                for lst, a in zip((self.ids, self.prob, self.backoff, self.raw, self.adjusted, self.p, self.gamma),
+                                  (ids, prob, back, raw, adj, pf, gf)):
+                    lst.append(a)
+            ms = np.zeros(8, np.float64)
+            _lib.check(lib.casr_lm_estimate_timing(ptr, p(ms)), lib=lib)
+            self.timing_ms = ms
+        finally:
+            lib.casr_lm_estimate_destroy(ptr)
+
+    def sorted(self):
+        """Every order in ascending key order (what the host entry gives; the device entry's order is
+        unspecified).  Returns self."""
+        for n in range(self.order):
+            ix = np.lexsort(self.ids[n].T[::-1])
+            for lst in (self.ids, self.prob, self.backoff, self.raw, self.adjusted, self.p, self.gamma):
+                lst[n] = np.ascontiguousarray(lst[n][ix])
+        return self
+
+
+def flatten(sentences, vocab, word2int=None):
+    """(tokens int32 [total], offsets int64 [n + 1]) of a list of id lists, or of strings taken one
+    character at a time through ``word2int`` (a character outside the vocabulary is <unk> = vocab + 2,
+    as NgramLM.ids_of gives it; spaces are skipped)."""
+    V = int(vocab)
+    rows = []
+    for s in sentences:
+        if isinstance(s, str):
+            if word2int is None:
+                raise ValueError("estimate: string sentences need word2int")
+            row = []
+            for ch in s:
+                if ch.isspace():
+                    continue
+                t = word2int.get(ch, -1)
+                row.append(t if 0 <= t < V else V + 2)
+        else:
+            row = [int(t) for t in s]
+        rows.append(row)
+    offsets = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=offsets[1:])
+    tokens = np.array([t for r in rows for t in r], np.int32)
+    return tokens, offsets
+
+
+def estimate_host(tokens, offsets, order, vocab):
+    """casr_lm_estimate_host on the flat corpus -> LmEstimate (ascending key order).  No GPU."""
+    lib = _lib.load()
+    tokens = np.ascontiguousarray(tokens, np.int32)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    out = ctypes.c_void_p()
+    rc = lib.casr_lm_estimate_host(int(order), int(vocab), tokens.ctypes.data_as(ctypes.c_void_p),
+                                   offsets.ctypes.data_as(ctypes.c_void_p), len(offsets) - 1, ctypes.byref(out))
+    _lib.check(rc, lib=lib)
+    return LmEstimate(lib, out, order)
+
+
+def workspace_bytes(order, positions):
+    """casr_lm_estimate_workspace_bytes: the device entry's counting tables for that many positions
+    (-1 for what it refuses)."""
+    return int(_lib.load().casr_lm_estimate_workspace_bytes(int(order), int(positions)))
+
+
+def estimate(sentences, order, vocab, word2int=None, engine=None):
+    """An interpolated modified-Kneser-Ney NgramLM of the given order (1..4) from ``sentences`` (id
+    lists, or strings split per character through ``word2int``): on ``engine``'s device
+    (Engine.lm_estimate), or without one through the host entry.  The model carries ``.discounts``
+    [order, 3], ``.fallback`` [order] (orders that use (0.5, 1, 1.5)) and ``.estimate`` (the
+    LmEstimate); ``.on(engine)``, rescoring and fusion work as for a model read from a file."""
+    tokens, offsets = flatten(sentences, vocab, word2int)
+    if engine is None:
+        est = estimate_host(tokens, offsets, order, vocab)
+    else:
+        if engine.cfg.vocab != int(vocab):
+            raise ValueError(f"estimate: vocab {vocab} is not the engine's {engine.cfg.vocab}")
+        est = engine.lm_estimate(tokens, offsets, order).sorted()
+    lm = NgramLM.from_ids(est.ids, est.prob, est.backoff, word2int if word2int is not None else {}, vocab)
+    lm.discounts, lm.fallback, lm.estimate = est.discounts, est.fallback, est
+    return lm

@@ -225,6 +225,7 @@ struct casr_handle {
   DevBuf gramws;  // casr_beam_grammar: mask rows, states (carve_beam_gram)
   DevBuf mbrws;   // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
   DevBuf eaws;    // casr_edit_align: direction bits and the tile hand-offs (edit_align_plan)
+  DevBuf estws;   // casr_lm_estimate: the counting tables (lm_estimate_plan.h est_carve)
   DevBuf cnws;    // casr_confusion, casr_beam_nbest, casr_beam_confusion: lists, units, votes (carve_confusion)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
@@ -609,7 +610,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->eaws, &h->biasws, &h->cnws, &h->gramws})
+                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->eaws, &h->biasws, &h->cnws, &h->gramws, &h->estws})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1505,6 +1506,114 @@ int casr_lm_score(casr_handle* h, const casr_lm* lm, const int32_t* tokens, cons
   HIP_OK(h, launch_lm_score(lm->dview, tokens, lens, n, L, bos != 0, q, err, (hipStream_t)stream));
   return CASR_OK;
 }
+
+// ---- Kneser-Ney estimation (lm_estimate_plan.h; the kernels in lm_estimate.hip)
+struct casr_lm_est {
+  casr::EstResult r;
+};
+static int g_est_combine = 1;
+
+int casr_lm_estimate_host(int order, int vocab, const int32_t* tokens, const int64_t* offsets, int64_t n,
+                          casr_lm_est** est) {
+  if (!est) return fail(nullptr, CASR_ERR_ARG, "casr_lm_estimate_host: est is NULL");
+  *est = nullptr;
+  casr_lm_est* o = new casr_lm_est();
+  std::string why;
+  const int rc = est_estimate_host(order, vocab, tokens, offsets, n, &o->r, &why);
+  if (rc != NGRAM_OK) {
+    delete o;
+    return fail(nullptr, rc, "casr_lm_estimate_host: %s", why.c_str());
+  }
+  *est = o;
+  return CASR_OK;
+}
+
+int casr_lm_estimate(casr_handle* h, int order, const int32_t* tokens, const int64_t* offsets, int64_t n,
+                     void* stream, casr_lm_est** est) {
+  if (est) *est = nullptr;
+  if (!h || !tokens || !offsets || !est) return fail(h, CASR_ERR_ARG, "casr_lm_estimate: NULL argument");
+  if (order < 1 || order > NGRAM_MAX_ORDER) return fail(h, CASR_ERR_ARG, "casr_lm_estimate: order %d outside 1..4", order);
+  if (n < 1) return fail(h, CASR_ERR_ARG, "casr_lm_estimate: n < 1");
+  const int V = h->cfg.vocab;
+  if ((int64_t)V + 3 > NGRAM_MAX_IDS) return fail(h, CASR_ERR_UNSUPPORTED, "casr_lm_estimate: vocab + 3 = %d > 65535", V + 3);
+  if (n > EST_MAX_POSITIONS) return fail(h, CASR_ERR_UNSUPPORTED, "casr_lm_estimate: more than 2^28 positions");
+  HIP_OK(h, hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  int64_t total = 0;
+  HIP_OK(h, hipMemcpyAsync(&total, offsets + n, sizeof total, hipMemcpyDeviceToHost, s));
+  HIP_OK(h, hipStreamSynchronize(s));
+  if (total < 0) return fail(h, CASR_ERR_ARG, "casr_lm_estimate: offsets[n] = %lld < 0", (long long)total);
+  if (total + n > EST_MAX_POSITIONS)
+    return fail(h, CASR_ERR_UNSUPPORTED, "casr_lm_estimate: %lld positions > 2^28", (long long)(total + n));
+  if (!guard_words(h)) return fail(h, CASR_ERR_HIP, "casr_lm_estimate: no guard words");
+  HIP_OK(h, h->estws.ensure((size_t)est_workspace_bytes(order, total + n)));
+  casr_lm_est* o = new casr_lm_est();
+  uint32_t flags = 0;
+  const hipError_t e = run_lm_estimate(order, V, tokens, offsets, n, total, h->estws.p, g_est_combine, GUARD(h, 0), s,
+                                       &o->r, &flags);
+  if (e != hipSuccess || (flags & EST_FLAG_FULL)) {
+    delete o;
+    if (e != hipSuccess) return fail(h, CASR_ERR_HIP, "casr_lm_estimate: %s", hipGetErrorString(e));
+    return fail(h, CASR_ERR_ARG, "casr_lm_estimate: the offsets overlap: a counting table proved full");
+  }
+  *est = o;
+  return CASR_OK;
+}
+
+int casr_lm_estimate_combine(int on) {
+  const int was = g_est_combine;
+  g_est_combine = on != 0;
+  return was;
+}
+
+int casr_lm_estimate_info(const casr_lm_est* est, int64_t* count, double* discount, int32_t* fallback,
+                          int64_t* n_types, int64_t* positions) {
+  if (!est) return fail(nullptr, CASR_ERR_ARG, "casr_lm_estimate_info: NULL object");
+  const EstResult& r = est->r;
+  for (int m = 0; m < NGRAM_MAX_ORDER; ++m) {
+    if (count) count[m] = (int64_t)r.key[m].size();
+    if (fallback) fallback[m] = r.fallback[m];
+    for (int k = 0; k < 3 && discount; ++k) discount[3 * m + k] = r.D[m][k];
+  }
+  if (n_types) *n_types = r.n_types;
+  if (positions) *positions = r.positions;
+  return CASR_OK;
+}
+
+int casr_lm_estimate_arrays(const casr_lm_est* est, int n, int32_t* ids, float* prob, float* backoff,
+                            int64_t* adjusted, double* p_f64, double* gamma_f64) {
+  if (!est || n < 1 || n > est->r.order)
+    return fail(nullptr, CASR_ERR_ARG, "casr_lm_estimate_arrays: NULL object or n outside 1..order");
+  const EstResult& r = est->r;
+  const size_t c = r.key[n - 1].size();
+  for (size_t i = 0; i < c; ++i) {
+    if (ids) est_key_ids(r.key[n - 1][i], n, ids + i * n);
+    if (prob) prob[i] = est_stored_prob(r, n, i);
+    if (backoff) backoff[i] = est_stored_backoff(r, n, i);
+    if (adjusted) adjusted[i] = r.adjusted[n - 1][i];
+    if (p_f64) p_f64[i] = r.p[n - 1][i];
+    if (gamma_f64) gamma_f64[i] = r.gamma[n - 1][i];
+  }
+  return CASR_OK;
+}
+
+int casr_lm_estimate_counts(const casr_lm_est* est, int n, int64_t* raw) {
+  if (!est || !raw || n < 1 || n > est->r.order)
+    return fail(nullptr, CASR_ERR_ARG, "casr_lm_estimate_counts: NULL argument or n outside 1..order");
+  const std::vector<uint32_t>& c = est->r.count[n - 1];
+  for (size_t i = 0; i < c.size(); ++i) raw[i] = c[i];
+  return CASR_OK;
+}
+
+int casr_lm_estimate_timing(const casr_lm_est* est, double* ms) {
+  if (!est || !ms) return fail(nullptr, CASR_ERR_ARG, "casr_lm_estimate_timing: NULL argument");
+  for (int i = 0; i < 8; ++i) ms[i] = est->r.stage_ms[i];
+  return CASR_OK;
+}
+
+void casr_lm_estimate_destroy(casr_lm_est* est) { delete est; }
+
+int64_t casr_lm_estimate_workspace_bytes(int order, int64_t positions) { return est_workspace_bytes(order, positions); }
 
 int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, double length_weight,
                       int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm, float* rec_lm,

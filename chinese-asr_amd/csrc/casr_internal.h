@@ -11,6 +11,7 @@
 #include "casr.h"
 #include "encode_plan.h"
 #include "grammar_plan.h"
+#include "lm_estimate_plan.h"
 #include "ngram_succ.h"
 #include "ngram_table.h"
 #include "resample_design.h"
@@ -478,6 +479,12 @@ hipError_t run_score(const DecodeArgs& a, DecodeBufs& d, const ScoreBufs& sb, co
 // Sentence scores q [n] of tokens [n][L] (LM ids) with lens [n]
 hipError_t launch_lm_score(const NgramView& m, const int32_t* tokens, const int32_t* lens, int n, int L, int bos,
                            float* q, int32_t* err, hipStream_t s);
+// lm_estimate.hip: the Kneser-Ney estimate of a corpus of `total` tokens in n sentences (device pointers)
+// over the zeroed-by-it workspace ws of est_workspace_bytes(order, total + n); synchronises the stream.
+// *flags: EST_FLAG_FULL where the result is refused (*out is then untouched); combine = 0 counts
+// without the LDS combining (the same result)
+hipError_t run_lm_estimate(int order, int V, const int32_t* tokens, const int64_t* offsets, int64_t n, int64_t total,
+                           void* ws, int combine, int32_t* err, hipStream_t s, EstResult* out, uint32_t* flags);
 // the second pass over the beam tree run_beam left (one workgroup per utterance); the beam
 // weights are casr_beam's own, for its unfinished fallback.  rescore_supported: its LDS fits
 bool rescore_supported(int max_len, int k);

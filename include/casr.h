@@ -517,6 +517,71 @@ int casr_beam_lm(casr_handle* h, const casr_lm* lm, int k, float lm_weight, floa
                  void* stream);
 int casr_beam_record_lm(casr_handle* h, float* rec_lm, void* stream);
 
+/* Estimating the n-gram LM from a token corpus: an interpolated modified-Kneser-Ney model of order N in
+ * 1..4, the estimator lmplz implements.  As with casr_lm_*, the operation is DEFINED BY THE FORMULAS
+ * BELOW, not by another tool's output; parity with lmplz is expected to float rounding and NOT PINNED.
+ *   Input     tokens [total] int32 LM ids, offsets [n + 1] int64 ascending from 0 to total; sentence i is
+ *             tokens[offsets[i] : offsets[i + 1]] and may be empty.  Ids 0 .. V - 1 and V + 2 = <unk>
+ *             (counted as a word) may occur; <s> = V and </s> = V + 1 may not, they are the padding:
+ *             every sentence is counted as <s> w_1 .. w_l </s>.  P = total + n positions.
+ *   Counts    c_n(g), n = 1..N: the windows of n consecutive ids of the padded sentences equal to g.
+ *   Adjusted  a_N = c_N; for n < N, a_n(g) = c_n(g) where g starts with <s>, else the number of
+ *             distinct v with c_{n+1}(v g) > 0.  The unigram <s> takes no part in what follows.
+ *   Discounts t_{n,k} = the n-grams with a_n = k (k = 1..4); Y = t1 / (t1 + 2 t2); D_n(k) = k -
+ *             (((k + 1) Y) t_{k+1}) / t_k for k = 1, 2, 3.  Where t1..t4 are not all positive or some
+ *             D_n(k) is not in (0, k], order n FALLS BACK to D_n = (0.5, 1, 1.5).  D(a) = D(min(a, 3)).
+ *   Context   for an (n - 1)-gram c (the empty one for n = 1): S_n(c) = sum_w a_n(c w), N_k(c) = the w
+ *             with min(a_n(c w), 3) = k; gamma_n(c) = ((D_n(1) N_1 + D_n(2) N_2) + D_n(3) N_3) / S_n(c).
+ *   p         u = (a - D(a)) / S.  p_1(w) = u + gamma_1() / |W| with |W| the unigram types other than
+ *             <s> and <unk>, plus 1; <unk> always has a unigram (u = 0 where it was never seen).
+ *             p_n(w | c) = u + gamma_n(c) p_{n-1}(w | c without its first word).  All float64, every
+ *             operation one IEEE operation in the order written, nothing contracted to an fma.
+ *   Stored    prob = f32(log10 p); backoff of an n-gram g, n < N: f32(log10 gamma_{n+1}(g)) where
+ *             something follows g in the corpus, else 0; the unigram <s> has prob -99.  Orders 2..N hold
+ *             exactly the distinct windows.  An ASR id the corpus never holds gets no unigram:
+ *             casr_lm_create's redirect to <unk> applies.
+ * Both entries run one text (csrc/lm_estimate_plan.h); the log10 and the rounding to f32 happen on the
+ * host for both, in casr_lm_estimate_arrays, so their float64 p and gamma agree bit for bit.
+ * casr_lm_estimate_host: HOST pointers, no GPU; within an order the n-grams are in ascending key order
+ * (= ascending id tuples).  CASR_ERR_ARG: order outside 1..4, n < 1, vocab < 1, a NULL argument, offsets
+ * that do not ascend from 0, an id that is neither in [0, V) nor V + 2.  CASR_ERR_UNSUPPORTED: V + 3 >
+ * 65,535, P > 2^28 (counts are 32 bits wide).
+ * casr_lm_estimate: DEVICE pointers, V = the handle's vocab; needs no weights and no encode; synchronous
+ * (it returns with the result on the host); the order within an order is unspecified.  Counting tables
+ * of the power of two >= 2 P slots per order live in a workspace the handle keeps
+ * (casr_lm_estimate_workspace_bytes); every probe loop is bounded by the capacity.  A bad id is counted
+ * as <unk>, and offsets are clamped (sentence i = [clamp(offsets[i], 0, total), clamp(offsets[i + 1],
+ * that start, total))); both raise guard bit 1.  Offsets that overlap so far that a table proves full
+ * are refused with CASR_ERR_ARG.  Otherwise errors as the host entry, checked before anything is
+ * launched (total is read from offsets[n] first).
+ * casr_lm_estimate_combine: whether the count kernel combines equal keys in LDS before the global
+ * atomic (default 1; the same result either way; process-wide, for measurements).  Returns the
+ * previous value. */
+typedef struct casr_lm_est casr_lm_est;
+int casr_lm_estimate_host(int order, int vocab, const int32_t* tokens, const int64_t* offsets, int64_t n,
+                          casr_lm_est** est);
+int casr_lm_estimate(casr_handle* h, int order, const int32_t* tokens, const int64_t* offsets, int64_t n,
+                     void* stream, casr_lm_est** est);
+int casr_lm_estimate_combine(int on);
+/* count [4]: n-grams per order (0 above N); discount [4][3]: D_n(1..3); fallback [4]: 1 where the order
+ * fell back; n_types: |W|; positions: P.  Any output may be NULL. */
+int casr_lm_estimate_info(const casr_lm_est* est, int64_t* count, double* discount, int32_t* fallback,
+                          int64_t* n_types, int64_t* positions);
+/* Order n's arrays, HOST outputs, any of them NULL: ids [count][n], prob and backoff [count] (what
+ * casr_lm_create takes), adjusted [count] (a_n; c_1 for the unigram <s>), p_f64 [count] (0 for the
+ * unigram <s>) and gamma_f64 [count] (gamma_{n+1} of the n-gram as a context; 0 where it is none).
+ * casr_lm_estimate_counts: the raw counts c_n [count].  casr_lm_estimate_timing: milliseconds of the
+ * device entry's stages (count, extend, stats, prob, compact, copy, 0, all); zeros from the host entry.
+ * CASR_ERR_ARG: a NULL object, n outside 1..N. */
+int casr_lm_estimate_arrays(const casr_lm_est* est, int n, int32_t* ids, float* prob, float* backoff,
+                            int64_t* adjusted, double* p_f64, double* gamma_f64);
+int casr_lm_estimate_counts(const casr_lm_est* est, int n, int64_t* raw);
+int casr_lm_estimate_timing(const casr_lm_est* est, double* ms);
+void casr_lm_estimate_destroy(casr_lm_est* est);
+/* Bytes of casr_lm_estimate's counting tables for P positions (the plan; no GPU): -1 for an order
+ * outside 1..4 or P outside [1, 2^28].  The dense result arrays (32 bytes per n-gram) come on top. */
+int64_t casr_lm_estimate_workspace_bytes(int order, int64_t positions);
+
 /* Hotword (contextual) biasing: the caller lists phrases (names, product terms, addresses) and the beam
  * search favours hypotheses that spell them WHILE it searches.  An n-gram LM cannot do this: the words
  * that need the help are the ones its training text never saw.  The reference has no such pass; like
