@@ -315,6 +315,18 @@ class Engine:
                                              offsets.numel() - 1, _stream(), ctypes.byref(out)), self.handle)
         return LmEstimate(self.lib, out, order)
 
+    def lm_prune(self, lm, theta):
+        """Relative-entropy pruning of a casr.ngram.NgramLM on the device (casr_lm_prune; include/casr.h
+        has the definition) -> casr.ngram.LmPruned, whose decisions, float64 backoffs and stored
+        values are the host entry's bit for bit (the order within an order is unspecified:
+        ``.sorted()``).  Needs no weights and no encode; synchronous.  NgramLM.prune(theta, engine)
+        builds the pruned model from it."""
+        from .ngram import LmPruned
+        out = ctypes.c_void_p()
+        _lib.check(self.lib.casr_lm_prune(self.handle, lm.on(self), ctypes.c_double(theta), _stream(),
+                                          ctypes.byref(out)), self.handle)
+        return LmPruned(self.lib, out, lm.order)
+
     def beam_rescore(self, lm, lm_weight, length_weight, records=False):
         """The second pass (model.py:749-763) over the last beam()'s finished hypotheses on the device
         (casr_beam_rescore): lm a casr.ngram.NgramLM.  Returns tokens [B, max_len] (-1 past the

@@ -42,6 +42,8 @@ EXPORTS = [
     "casr_lm_estimate_host", "casr_lm_estimate", "casr_lm_estimate_combine", "casr_lm_estimate_info",
     "casr_lm_estimate_arrays", "casr_lm_estimate_counts", "casr_lm_estimate_timing", "casr_lm_estimate_destroy",
     "casr_lm_estimate_workspace_bytes",
+    "casr_lm_prune_host", "casr_lm_prune", "casr_lm_prune_info", "casr_lm_prune_arrays", "casr_lm_prune_decisions",
+    "casr_lm_prune_timing", "casr_lm_prune_destroy", "casr_lm_prune_workspace_bytes",
 ]
 
 # arithmetic of the MFMA contractions (casr_set_precision); s16x1 is the opt-in perf arithmetic of
@@ -201,6 +203,14 @@ def load(path=None, variant=None):
         "casr_lm_estimate_timing": (i32, [vp, vp]),
         "casr_lm_estimate_destroy": (None, [vp]),
         "casr_lm_estimate_workspace_bytes": (ctypes.c_int64, [i32, ctypes.c_int64]),
+        "casr_lm_prune_host": (i32, [vp, ctypes.c_double, ctypes.POINTER(vp)]),
+        "casr_lm_prune": (i32, [vp, vp, ctypes.c_double, vp, ctypes.POINTER(vp)]),
+        "casr_lm_prune_info": (i32, [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
+        "casr_lm_prune_arrays": (i32, [vp, i32, vp, vp, vp, vp]),
+        "casr_lm_prune_decisions": (i32, [vp, i32, vp, vp, vp]),
+        "casr_lm_prune_timing": (i32, [vp, vp]),
+        "casr_lm_prune_destroy": (None, [vp]),
+        "casr_lm_prune_workspace_bytes": (ctypes.c_int64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -7,6 +7,10 @@ second pass calls (casr.results.second_pass_arrays).  ``on(engine)`` gives the d
 ``Engine.lm_score`` and ``Engine.beam_rescore`` take.  The query is defined in include/casr.h: the
 textbook ARPA backoff query.  It should agree with KenLM to float rounding; KenLM is not available
 here, so that statement is not pinned by any test.
+
+``estimate`` builds a model from sentences (casr_lm_estimate*) and ``NgramLM.prune`` makes any model
+smaller by relative-entropy pruning (casr_lm_prune*); both run on an Engine's device or, without one,
+through their host entries, with the same bits either way.
 """
 import ctypes
 import os
@@ -241,6 +245,75 @@ class NgramLM:
                         line += "\t%.7g" % float(b[i])
                     f.write(line + "\n")
             f.write("\n\\end\\\n")
+
+    def prune(self, theta, engine=None):
+        """The model after relative-entropy pruning at threshold ``theta`` (casr_lm_prune; include/casr.h
+        has the definition): on ``engine``'s device, or without one through the host entry, with the
+        same bits either way.  The result is an NgramLM of the kept n-grams with renewed backoffs (the
+        model itself, bit for bit, where nothing was removable); it carries ``.pruned``, the LmPruned
+        with the counts, tau and every n-gram's decision."""
+        if engine is None:
+            out = ctypes.c_void_p()
+            rc = self._lib.casr_lm_prune_host(self._host, ctypes.c_double(theta), ctypes.byref(out))
+            _lib.check(rc, lib=self._lib)
+            res = LmPruned(self._lib, out, self.order)
+        else:
+            res = engine.lm_prune(self, theta).sorted()
+        lm = NgramLM.from_ids(res.ids, res.prob, res.backoff, self.word2int, self.vocab)
+        lm.pruned = res
+        return lm
+
+    def prune_workspace_bytes(self):
+        """casr_lm_prune_workspace_bytes: the device entry's workspace for this model."""
+        return int(self._lib.casr_lm_prune_workspace_bytes(self._host))
+
+
+class LmPruned:
+    """What casr_lm_prune_host / casr_lm_prune returned, as numpy arrays: per order n the kept n-grams
+    ids[n-1] int32 [count_out, n], prob and backoff float32 (the stored model), backoff_f64 (B'); every
+    input n-gram's decision all_ids[n-1] [count_in, n], delta float64 (NaN: takes no part) and kept
+    bool; ``count_in``, ``count_out``, ``n_protected`` [order], ``n_degenerate``, ``tau`` and
+    ``timing_ms`` (the device entry's stages: linearise, decide, renew, compact, copy, -, -, all)."""
+
+    def __init__(self, lib, ptr, order):
+        try:
+            cin, cout, prot = (np.zeros(4, np.int64) for _ in range(3))
+            deg, tau = ctypes.c_int64(), ctypes.c_double()
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            _lib.check(lib.casr_lm_prune_info(ptr, p(cin), p(cout), p(prot), ctypes.byref(deg), ctypes.byref(tau)),
+                       lib=lib)
+            self.order = int(order)
+            self.count_in, self.count_out = cin[:self.order].copy(), cout[:self.order].copy()
+            self.n_protected, self.n_degenerate, self.tau = prot[:self.order].copy(), deg.value, tau.value
+            self.ids, self.prob, self.backoff, self.backoff_f64 = [], [], [], []
+            self.all_ids, self.delta, self.kept = [], [], []
+            for n in range(1, self.order + 1):
+                c, ci = int(cout[n - 1]), int(cin[n - 1])
+                ids, prob, back = np.zeros((c, n), np.int32), np.zeros(c, np.float32), np.zeros(c, np.float32)
+                b64 = np.zeros(c, np.float64)
+                _lib.check(lib.casr_lm_prune_arrays(ptr, n, p(ids), p(prob), p(back), p(b64)), lib=lib)
+                aids, delta, kept = np.zeros((ci, n), np.int32), np.zeros(ci, np.float64), np.zeros(ci, np.uint8)
+                _lib.check(lib.casr_lm_prune_decisions(ptr, n, p(aids), p(delta), p(kept)), lib=lib)
+                for lst, a in zip((self.ids, self.prob, self.backoff, self.backoff_f64, self.all_ids, self.delta, self.kept),
+                                  (ids, prob, back, b64, aids, delta, kept.astype(bool))):
+                    lst.append(a)
+            ms = np.zeros(8, np.float64)
+            _lib.check(lib.casr_lm_prune_timing(ptr, p(ms)), lib=lib)
+            self.timing_ms = ms
+        finally:
+            lib.casr_lm_prune_destroy(ptr)
+
+    def sorted(self):
+        """Every order in ascending key order (what the host entry gives; the device entry's order is
+        unspecified).  Returns self."""
+        for n in range(self.order):
+            ix = np.lexsort(self.ids[n].T[::-1])
+            for lst in (self.ids, self.prob, self.backoff, self.backoff_f64):
+                lst[n] = np.ascontiguousarray(lst[n][ix])
+            ix = np.lexsort(self.all_ids[n].T[::-1])
+            for lst in (self.all_ids, self.delta, self.kept):
+                lst[n] = np.ascontiguousarray(lst[n][ix])
+        return self
 
 
 # ---------------------------------------------------------------------------- estimation

@@ -226,6 +226,7 @@ struct casr_handle {
   DevBuf mbrws;   // casr_beam_mbr: lists, weights and the byte distances (carve_mbr)
   DevBuf eaws;    // casr_edit_align: direction bits and the tile hand-offs (edit_align_plan)
   DevBuf estws;   // casr_lm_estimate: the counting tables (lm_estimate_plan.h est_carve)
+  DevBuf prunews; // casr_lm_prune: the per-slot arrays and the dense result (lm_prune_plan.h lmp_carve)
   DevBuf cnws;    // casr_confusion, casr_beam_nbest, casr_beam_confusion: lists, units, votes (carve_confusion)
   // hipGraph replay of the launch-bound loops (per-layer recurrence, decode loop)
   // casr_set_graphs bits: 1 = the decode loop replays as a hipGraph, 2 = the per-step recurrence
@@ -244,6 +245,8 @@ struct casr_lm {
   int device = -1;
   NgramTables host;
   NgramSuccTables succ;  // the successor lists (ngram_succ.h): casr_lm_terms, casr_beam_lm
+  int64_t count[NGRAM_MAX_ORDER] = {};  // n-grams per order as given (casr_lm_prune's size plan)
+  bool unk_given = false;               // the <unk> unigram was given, not defaulted
   void* dev[11] = {};    // uni, redirect, tab[0..2]; succ: list[0..2], dir, ctab[0..1]
   NgramView dview{};
   NgramSuccView dsucc{};
@@ -610,7 +613,7 @@ void casr_destroy(casr_handle* h) {
   for (DevBuf* b : {&h->gin, &h->out0, &h->out1, &h->hbuf, &h->cst, &h->hfin, &h->keysT, &h->lens, &h->feat, &h->fstat, &h->hx, &h->x16, &h->gflags, &h->fe_const,
                     &h->st, &h->logits, &h->small, &h->bp, &h->tk, &h->rec, &h->gout, &h->wfold, &h->wfold32, &h->coldbuf,
                     &h->egates, &h->fgates, &h->wq16, &h->wih16km, &h->ksbuf, &h->asbuf, &h->scorebuf, &h->cvt_peak,
-                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->eaws, &h->biasws, &h->cnws, &h->gramws, &h->estws})
+                    &h->seg_q, &h->seg_hist, &h->lmws, &h->mbrws, &h->eaws, &h->biasws, &h->cnws, &h->gramws, &h->estws, &h->prunews})
     b->release();
   for (casr_handle::ResampleTable* t : h->rs_tables) {
     t->dev.release();
@@ -1433,6 +1436,8 @@ int casr_lm_create(int device, int order, int vocab, const int64_t* count, const
     return fail(nullptr, rc, "casr_lm_create: %s", why.c_str());
   }
   ngram_succ_build(lm->host, count, ids, prob, &lm->succ);
+  for (int n = 0; n < order; ++n) lm->count[n] = count[n];
+  for (int64_t i = 0; i < count[0]; ++i) lm->unk_given = lm->unk_given || ids[0][i] == vocab + 2;
   lm->device = device;
   if (device >= 0) {
     const NgramTables& t = lm->host;
@@ -1614,6 +1619,103 @@ int casr_lm_estimate_timing(const casr_lm_est* est, double* ms) {
 void casr_lm_estimate_destroy(casr_lm_est* est) { delete est; }
 
 int64_t casr_lm_estimate_workspace_bytes(int order, int64_t positions) { return est_workspace_bytes(order, positions); }
+
+// ---- relative-entropy pruning (lm_prune_plan.h; the kernels in lm_prune.hip)
+struct casr_lm_pruned {
+  casr::LmpResult r;
+};
+
+static LmpDims lm_prune_dims(const casr_lm* lm) { return lmp_dims(lm->host, lm->succ, lm->count, lm->unk_given); }
+
+int casr_lm_prune_host(const casr_lm* lm, double theta, casr_lm_pruned** out) {
+  if (out) *out = nullptr;
+  if (!lm || !out) return fail(nullptr, CASR_ERR_ARG, "casr_lm_prune_host: NULL argument");
+  if (!(theta >= 0.0) || !isfinite(theta)) return fail(nullptr, CASR_ERR_ARG, "casr_lm_prune_host: theta %g", theta);
+  casr_lm_pruned* o = new casr_lm_pruned();
+  if (!lmp_prune_host(lm->host, lm->succ, lm_prune_dims(lm), theta, &o->r)) {
+    delete o;
+    return fail(nullptr, CASR_ERR_ARG, "casr_lm_prune_host: the LM object is inconsistent");
+  }
+  *out = o;
+  return CASR_OK;
+}
+
+int casr_lm_prune(casr_handle* h, const casr_lm* lm, double theta, void* stream, casr_lm_pruned** out) {
+  if (out) *out = nullptr;
+  if (!h || !lm || !out) return fail(h, CASR_ERR_ARG, "casr_lm_prune: NULL argument");
+  if (!(theta >= 0.0) || !isfinite(theta)) return fail(h, CASR_ERR_ARG, "casr_lm_prune: theta %g", theta);
+  const int rc = lm_matches_handle(h, lm, "casr_lm_prune");
+  if (rc) return rc;
+  HIP_OK(h, hipSetDevice(h->device));
+  const LmpDims d = lm_prune_dims(lm);
+  HIP_OK(h, h->prunews.ensure((size_t)lmp_carve(nullptr, d, nullptr, nullptr, nullptr)));
+  casr_lm_pruned* o = new casr_lm_pruned();
+  uint32_t flags = 0;
+  const hipError_t e = run_lm_prune(lm->host, lm->dview, lm->dsucc, d, theta, h->prunews.p, (hipStream_t)stream, &o->r, &flags);
+  if (e != hipSuccess || flags) {
+    delete o;
+    if (e != hipSuccess) return fail(h, CASR_ERR_HIP, "casr_lm_prune: %s", hipGetErrorString(e));
+    return fail(h, CASR_ERR_ARG, "casr_lm_prune: the LM object is inconsistent");
+  }
+  *out = o;
+  return CASR_OK;
+}
+
+int casr_lm_prune_info(const casr_lm_pruned* p, int64_t* count_in, int64_t* count_out, int64_t* n_protected,
+                       int64_t* n_degenerate, double* tau) {
+  if (!p) return fail(nullptr, CASR_ERR_ARG, "casr_lm_prune_info: NULL object");
+  const LmpResult& r = p->r;
+  for (int m = 0; m < NGRAM_MAX_ORDER; ++m) {
+    if (count_in) count_in[m] = (int64_t)r.key[m].size();
+    if (count_out) count_out[m] = r.count_out[m];
+    if (n_protected) n_protected[m] = r.n_protected[m];
+  }
+  if (n_degenerate) *n_degenerate = r.n_degenerate;
+  if (tau) *tau = r.tau;
+  return CASR_OK;
+}
+
+int casr_lm_prune_arrays(const casr_lm_pruned* p, int n, int32_t* ids, float* prob, float* backoff,
+                         double* backoff_f64) {
+  if (!p || n < 1 || n > p->r.order)
+    return fail(nullptr, CASR_ERR_ARG, "casr_lm_prune_arrays: NULL object or n outside 1..order");
+  const LmpResult& r = p->r;
+  size_t at = 0;
+  for (size_t i = 0; i < r.key[n - 1].size(); ++i) {
+    if (!r.kept[n - 1][i]) continue;
+    if (ids) lmp_key_ids(r.key[n - 1][i], n, ids + at * n);
+    if (prob) prob[at] = r.prob[n - 1][i];
+    if (backoff) backoff[at] = r.out_backoff[n - 1][i];
+    if (backoff_f64) backoff_f64[at] = r.out_b64[n - 1][i];
+    ++at;
+  }
+  return CASR_OK;
+}
+
+int casr_lm_prune_decisions(const casr_lm_pruned* p, int n, int32_t* ids, double* delta, uint8_t* kept) {
+  if (!p || n < 1 || n > p->r.order)
+    return fail(nullptr, CASR_ERR_ARG, "casr_lm_prune_decisions: NULL object or n outside 1..order");
+  const LmpResult& r = p->r;
+  for (size_t i = 0; i < r.key[n - 1].size(); ++i) {
+    if (ids) lmp_key_ids(r.key[n - 1][i], n, ids + i * n);
+    if (delta) delta[i] = r.delta[n - 1][i];
+    if (kept) kept[i] = r.kept[n - 1][i];
+  }
+  return CASR_OK;
+}
+
+int casr_lm_prune_timing(const casr_lm_pruned* p, double* ms) {
+  if (!p || !ms) return fail(nullptr, CASR_ERR_ARG, "casr_lm_prune_timing: NULL argument");
+  for (int i = 0; i < 8; ++i) ms[i] = p->r.stage_ms[i];
+  return CASR_OK;
+}
+
+void casr_lm_prune_destroy(casr_lm_pruned* p) { delete p; }
+
+int64_t casr_lm_prune_workspace_bytes(const casr_lm* lm) {
+  if (!lm) return -1;
+  return lmp_carve(nullptr, lm_prune_dims(lm), nullptr, nullptr, nullptr);
+}
 
 int casr_beam_rescore(casr_handle* h, const casr_lm* lm, double lm_weight, double length_weight,
                       int32_t* best_tokens, int32_t* best_len, float* best_score, float* best_lm, float* rec_lm,

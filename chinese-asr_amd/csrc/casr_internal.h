@@ -12,6 +12,7 @@
 #include "encode_plan.h"
 #include "grammar_plan.h"
 #include "lm_estimate_plan.h"
+#include "lm_prune_plan.h"
 #include "ngram_succ.h"
 #include "ngram_table.h"
 #include "resample_design.h"
@@ -485,6 +486,11 @@ hipError_t launch_lm_score(const NgramView& m, const int32_t* tokens, const int3
 // without the LDS combining (the same result)
 hipError_t run_lm_estimate(int order, int V, const int32_t* tokens, const int64_t* offsets, int64_t n, int64_t total,
                            void* ws, int combine, int32_t* err, hipStream_t s, EstResult* out, uint32_t* flags);
+// lm_prune.hip: relative-entropy pruning of the LM whose device views are dm and ds (host: its host tables,
+// for the unigrams of the result) over the workspace ws of lmp_carve(d); synchronises the stream.  *flags:
+// LMP_FLAG_INCONSISTENT where the result is refused (*out is then untouched)
+hipError_t run_lm_prune(const NgramTables& host, const NgramView& dm, const NgramSuccView& ds, const LmpDims& d,
+                        double theta, void* ws, hipStream_t s, LmpResult* out, uint32_t* flags);
 // the second pass over the beam tree run_beam left (one workgroup per utterance); the beam
 // weights are casr_beam's own, for its unfinished fallback.  rescore_supported: its LDS fits
 bool rescore_supported(int max_len, int k);

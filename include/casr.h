@@ -582,6 +582,76 @@ void casr_lm_estimate_destroy(casr_lm_est* est);
  * outside 1..4 or P outside [1, 2^28].  The dense result arrays (32 bytes per n-gram) come on top. */
 int64_t casr_lm_estimate_workspace_bytes(int order, int64_t positions);
 
+/* Making an n-gram LM smaller: relative-entropy pruning (Stolcke 1998; SRILM's -prune) of ANY backoff
+ * model a casr_lm holds, an estimate of ours or a third party's ARPA file.  As with casr_lm_* the
+ * operation is DEFINED BY THE FORMULAS BELOW, not by another tool's output.
+ *   Linear    every stored value goes through P = exp10(prob), B = exp10(backoff) in float64 (lmp_exp10
+ *             below).  An n-gram without a backoff has B = 1, and so has an absent context.
+ *   Query     Q(w | c) is the "Word" rule above in the linear domain: m = the largest order whose n-gram
+ *             (c[-(m-1):], w) is present; start from P_m; for j = m .. len(c) multiply by B(c[-j:])
+ *             where that j-gram is present.  Float64 multiplications in that order.
+ *   Part      an n-gram holding a word without a unigram passes through untouched: it is in no sum, is
+ *             never removed, and its backoff stays as given.  Unigrams are never removed.
+ *   ph        for a context h = h_1 .. h_{n-1}: ph(h) = the product over i, ascending from 1, of
+ *             Q(h_i | h_1 .. h_{i-1}); where h_i = <s> the factor is P_1(</s>) (the model stores -99 for
+ *             <s>; every sentence has one of each, so their marginals are equal).
+ *   sum       sum(x_0 .. x_{m-1}) has one association: 64 partials s_l = x_l + x_{l+64} + .. ascending,
+ *             then for d = 32, 16, 8, 4, 2, 1: s_l = s_l + s_{l+d} for l < d; the result is s_0 (0 for an
+ *             empty list).  A wave computes exactly this; the host loops it.
+ *   Context   for n = 2..N and every context h with order-n successors v (ascending v):
+ *             num = 1 - sum P_n(h v), den = 1 - sum Q(v | h') with h' = h without its oldest word,
+ *             a = B(h) as stored.
+ *   Decision  for the n-gram (h, w): p = P_n(h w), q = Q(w | h'), a' = (num + p) / (den + q),
+ *             dH = -ph ( (p ((L(q) + L(a')) - L(p))) + (num (L(a') - L(a))) ), L the natural log
+ *             (lmp_log), every operation one IEEE operation as bracketed, nothing contracted.  Where p,
+ *             q, a, num + p and den + q are not all positive and finite, dH = +inf.  With tau =
+ *             L(1 + theta) the n-gram is REMOVABLE iff dH < tau (SRILM's exp(dH) - 1 < theta).
+ *   Kept      orders n = N down to 2: an n-gram that is the prefix of a kept (n + 1)-gram is PROTECTED
+ *             and stays (the result is prefix-closed); every other removable n-gram goes.  All decisions
+ *             read the model as given; only protection couples the orders.
+ *   Backoffs  if nothing was removed the output equals the input bit for bit.  Otherwise, for n = 2..N
+ *             ascending, every kept (n - 1)-gram h that takes part gets B'(h) = num' / den': the sums as
+ *             above over its KEPT successors (each successor keeps its place l in h's list; a removed
+ *             one adds nothing), Q evaluated in the pruned model (present = kept) with the backoffs
+ *             already renewed below.  B' = 1 where h has no kept successor.  Where num', den' or their
+ *             quotient is not positive and finite the context is DEGENERATE: B' = 0, stored as -99.
+ *   Stored    kept probs are the input's f32 bits; a renewed backoff is f32(log10 B'), 0 at the top
+ *             order; the log10 and the rounding happen on the host for both entries.
+ *   lmp_exp10, lmp_log: written out in csrc/lm_prune_plan.h from IEEE + - * / alone (integer range
+ *             reduction, a fixed polynomial in Horner form), because two libms do not agree in the last
+ *             bit: absolute error <= 1e-12 max(1, |ln x|) and relative error <= 1e-12 over [-99, 0],
+ *             four orders below what f32 storage can express.
+ * Both entries run one text (csrc/lm_prune_plan.h) and agree bit for bit on dH, the kept flags, B' and the
+ * stored values.  casr_lm_prune_host: any LM object, no GPU; within an order the n-grams come out in
+ * ascending key order.  casr_lm_prune: the LM's device copy must serve the handle (casr_lm_score's
+ * rules); needs no weights and no encode; synchronous; the order within an order is unspecified; the
+ * workspace (casr_lm_prune_workspace_bytes) stays with the handle.  Stages: linearise (one work item per
+ * slot), decide (orders N..2, one wave per context: the two sums, then one lane per n-gram), renew
+ * (orders 2..N, one wave per context), compact (one cursor add per wave).  Every probe loop is bounded
+ * by the capacity; no float atomics; nothing depends on scheduling.
+ * CASR_ERR_ARG: theta negative or not finite, a NULL argument; for the device entry also an LM that is
+ * host-only, on another device or of another vocabulary.  Nothing is launched or written on an error. */
+typedef struct casr_lm_pruned casr_lm_pruned;
+int casr_lm_prune_host(const casr_lm* lm, double theta, casr_lm_pruned** out);
+int casr_lm_prune(casr_handle* h, const casr_lm* lm, double theta, void* stream, casr_lm_pruned** out);
+/* count_in, count_out, n_protected [4]: n-grams per order before and after, and those kept only because
+ * they were protected (0 above N); n_degenerate: the degenerate contexts; tau.  Any output may be NULL. */
+int casr_lm_prune_info(const casr_lm_pruned* p, int64_t* count_in, int64_t* count_out, int64_t* n_protected,
+                       int64_t* n_degenerate, double* tau);
+/* The KEPT n-grams of order n, HOST outputs, any NULL: ids [count_out][n], prob and backoff (what
+ * casr_lm_create takes), backoff_f64 (B'; exp10 of the stored backoff where it was not renewed).
+ * casr_lm_prune_decisions: EVERY n-gram of order n of the input: ids [count_in][n], delta (dH; NaN for
+ * an n-gram that takes no part, unigrams included), kept.  casr_lm_prune_timing: milliseconds of the
+ * device entry's stages (linearise, decide, renew, compact, copy, 0, 0, all); zeros from the host entry.
+ * CASR_ERR_ARG: a NULL object, n outside 1..N. */
+int casr_lm_prune_arrays(const casr_lm_pruned* p, int n, int32_t* ids, float* prob, float* backoff,
+                         double* backoff_f64);
+int casr_lm_prune_decisions(const casr_lm_pruned* p, int n, int32_t* ids, double* delta, uint8_t* kept);
+int casr_lm_prune_timing(const casr_lm_pruned* p, double* ms);
+void casr_lm_prune_destroy(casr_lm_pruned* p);
+/* Bytes of casr_lm_prune's workspace for this LM (the plan; no GPU): -1 for NULL. */
+int64_t casr_lm_prune_workspace_bytes(const casr_lm* lm);
+
 /* Hotword (contextual) biasing: the caller lists phrases (names, product terms, addresses) and the beam
  * search favours hypotheses that spell them WHILE it searches.  An n-gram LM cannot do this: the words
  * that need the help are the ones its training text never saw.  The reference has no such pass; like
