@@ -208,7 +208,10 @@ class Engine:
         B = len(utts)
         utts = [u.contiguous().to(self.device, torch.float32) for u in utts]
         Tp = int(max(int(u.shape[0]) for u in utts)) if Tp is None else Tp
-        ptrs = torch.tensor([u.data_ptr() for u in utts], dtype=torch.int64, device=self.device)
+        # the pointer array goes up from pinned memory, stream-ordered: a copy from pageable memory would
+        # make the host wait for everything already enqueued on the caller's stream
+        ptrs = torch.tensor([u.data_ptr() for u in utts], dtype=torch.int64).pin_memory()
+        ptrs = ptrs.to(self.device, non_blocking=True)
         lens_d = lens.to(self.device, torch.int32).contiguous()
         feat = torch.empty(B, Tp, self.cfg.feat_dim, device=self.device, dtype=torch.float32)
         _lib.check(self.lib.casr_gather_utterances(self.handle, _ptr(ptrs), _ptr(lens_d), B, Tp, _ptr(feat),

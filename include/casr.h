@@ -16,6 +16,33 @@
  *     where noted (the beam/greedy calls return after enqueueing);
  *   - one handle per device; a handle is not thread-safe; workspaces are owned by the
  *     handle and grow on demand (first call at a new size allocates).
+ *
+ * The stream contract (tests/test_gpu_streams.py holds every entry that takes a `stream` to it, on a
+ * caller's own non-blocking stream; tests/stream_cases.py has the cases)
+ *   - Order.  A call's device work, whatever it launches, copies or replays and on whichever stream of
+ *     its own (the graph replays run on the handle's private streams, fenced by events both ways), is
+ *     ordered after everything already enqueued on `stream`, and its results are visible to everything
+ *     enqueued on `stream` afterwards.  So inputs may still be in the making on `stream` when the call
+ *     is issued, outputs may be consumed on `stream` without a host synchronisation in between, and an
+ *     input buffer may be overwritten on `stream` right after the call.  The legacy null stream is a
+ *     valid `stream`.
+ *   - Host synchronisation.  Three entries wait for `stream`: casr_lm_estimate and casr_lm_prune
+ *     (synchronous: they return with the result on the host) and casr_device_flags (it returns the
+ *     words).  Every other entry returns after enqueueing once it is warm.
+ *   - First use.  The first call at a new size, rate, precision or graph mode may allocate or free a
+ *     workspace, capture a graph, or build and upload a table or a weight image (the f32 folded image
+ *     and the guard words on the null stream, which the call then waits for; a resample table from
+ *     pageable host memory on `stream`).  Any of these may wait for the device, `stream` included; none
+ *     changes the order above, and a guard bit raised by a handle's very first call is not lost.  A
+ *     repeated call at a size, rate and mode already seen does none of it.
+ *   - One handle, one stream at a time.  A handle's workspaces, its encode and beam state, its guard
+ *     words and the events that fence its graph replays are shared by all its calls and are not
+ *     versioned per stream: calls on one handle must be issued on one stream, or be ordered by the
+ *     caller (the second stream waits for an event recorded on the first after the earlier call).
+ *     Nothing orders two calls of one handle on two unordered streams.  For work in flight side by side
+ *     use one handle per stream (casr.pipeline.StreamPipeline); handles share nothing but what is
+ *     immutable: the packed weight blob and the casr_lm, casr_bias and casr_grammar objects, which any
+ *     number of handles may read on any streams at once.
  */
 #ifndef CASR_H
 #define CASR_H
